@@ -10,13 +10,19 @@ surface normals, batch 32, bf16, one MI355X).  With N > 1 every rank owns a repl
 packed once on rank 0 and broadcast over RCCL/xGMI) and its own batch; there is no collective in
 the timed loop (weak scaling).  Rank 0 prints ONE JSON line.
 
-The line also carries
+A plain run sets up, warms up, times the K steps (`value`, `ms_per_step`), writes the last step's outputs if
+--dump-outputs DIR is given, and prints the line.  Everything else is measured only with --full:
+  schedule_ab  : the other schedule (two forwards in flight / one at a time) timed in the same process
+  telemetry    : GPU clock / power / temperature sampled during each timed loop
   roofline     : MFMA roofline of the dominant kernel family (the implicit-GEMM MFMA kernel that
                  runs every conv / linear).  achieved = algorithmic FLOPs routed through it per
                  forward / its summed launch durations, measured with HIP events on the forward's
                  stream in profiled forwards run right after the timed region.
   cpu_baseline : the CPU fp32 oracle (oracle/dpt_oracle.py, a port of the reference forward) timed
                  on this host's cores on a bounded sample (rank 0, N = 1 only).
+  parity       : the benched dtype and the parity mode against that oracle, the parity mode's img/s.
+  also         : short runs of the other BASELINE.json configurations (depth, dual-task bf16 / fp8 / mixed).
+--measure-traffic and --profile-dump ask for the roofline measurement without the rest of --full.
 """
 import argparse
 import json
@@ -37,6 +43,34 @@ GEMM_GMAC_PER_IMAGE = {"normal": 121.487, "depth": 121.478, "dual": 179.153}  # 
 GFLOP_LARGE = {"normal": 516.43, "depth": 516.41}
 GEMM_GMAC_LARGE = {"normal": 241.855, "depth": 241.845}
 PEAK_TFLOPS = 2500.0                                           # dense bf16/fp16 MFMA, MI355X_MICROARCH.md
+DUMP_BYTES = 64 * 10 ** 6                                      # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outputs, out_dir, budget=DUMP_BYTES, seed=0):
+    """--dump-outputs: every output of the last timed step ({name: [B, ...] tensor}, the first axis the image) goes to
+    out_dir/<name>.npy in float32.  When all of them together do not fit in `budget` bytes, each file holds the same fixed
+    subset of the images: the first k of a permutation seeded with `seed`, in ascending order, k as large as fits.
+    Returns {name: {"shape": [...], "images": "all" or the image indices}} for the result line."""
+    import numpy as np
+    batches = {int(t.shape[0]) for t in outputs.values()}
+    if len(batches) != 1:
+        raise ValueError(f"dump_outputs: the outputs do not share one batch axis: {sorted(batches)}")
+    B = batches.pop()
+    per_image = sum(4 * (t.numel() // B) for t in outputs.values())
+    keep = min(B, (budget - 4096 * len(outputs)) // per_image)   # 4 KB per file for the .npy header
+    if keep < 1:
+        raise ValueError(f"dump_outputs: one image's outputs ({per_image} bytes) exceed the {budget}-byte budget")
+    idx = None
+    if keep < B:
+        idx = torch.randperm(B, generator=torch.Generator().manual_seed(seed))[:keep].sort().values
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, t in outputs.items():
+        a = t.detach() if idx is None else t.detach()[idx.to(t.device)]
+        a = a.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": list(a.shape), "images": "all" if idx is None else idx.tolist()}
+    return info
 
 
 def free_port():
@@ -142,28 +176,36 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else the line can carry: the other schedule, telemetry, roofline "
+                         "and kernel breakdown, the CPU oracle baseline, parity against it, the secondary configurations under 'also' "
+                         "(default: off -- a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32; <name> = normal / depth), at most "
+                         f"{DUMP_BYTES // 10 ** 6} MB in all: a larger output is cut to a fixed, seeded subset of its images")
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
     ap.add_argument("--task", default="normal", choices=["normal", "depth", "dual"])
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "bf16x3", "fp16x3", "mixed", "fp8"])
     ap.add_argument("--x3-groups", default="", help="dtype mixed: layer groups that run 3 MFMAs per product, e.g. resnet+embed "
                                                     "(default: everything but the ViT blocks)")
-    ap.add_argument("--parity-dtype", default="mixed", help="mode timed and checked against the fp32 oracle next to --dtype "
-                                                            "(N = 1 only); 'none' skips it")
+    ap.add_argument("--parity-dtype", default="mixed", help="--full: mode timed and checked against the fp32 oracle next to "
+                                                            "--dtype (N = 1 only); 'none' skips it")
     ap.add_argument("--parity-x3-groups", default="")
     ap.add_argument("--io", default="fp32", choices=["fp32", "bf16", "fp16"], help="element type of the caller-side image and "
                     "result tensors (SURVEY.md 8d config 2 feeds bf16; fp32 is the reference's drop-in convention)")
     ap.add_argument("--backbone", default="vitb_rn50_384", choices=["vitb_rn50_384", "vitl16_384"],
                     help="vitb_rn50_384 = DPT-Hybrid (BASELINE.json's configuration, the default); vitl16_384 = DPT-Large")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the short secondary measurements (depth, dual-task bf16 / fp8) "
-                                                            "that the default N = 1 normal-head run appends under 'also'")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle (and the parity legs that use it)")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the short secondary measurements (depth, dual-task bf16 / "
+                                                            "fp8) that the N = 1 normal-head run appends under 'also'")
     ap.add_argument("--inflight", type=int, default=None,
                     help="batches in flight per GPU in the HEADLINE loop.  Default (not given): 1 = what the drop-in call `model(x)` / "
                          "`torch.hub.load(...)(x)` delivers -- one forward at a time, stream-ordered.  n > 1: omnidata_amd/pipeline.py "
                          "ForwardPipeline (that many handles, one stream each, one shared copy of the weights; every step is still one "
-                         "forward of one batch of --batch images; batch latency ~ n x ms_per_step, n arenas).  At N = 1 BOTH schedules "
-                         "are timed in the same process and reported as value_inflight1 / value_inflight2; `value` is the headline's")
-    ap.add_argument("--no-schedule-ab", action="store_true", help="skip the other schedule's loop (rocprofv3 passes: one schedule per trace)")
+                         "forward of one batch of --batch images; batch latency ~ n x ms_per_step, n arenas).  At N = 1 with --full BOTH "
+                         "schedules are timed in the same process and reported as value_inflight1 / value_inflight2; `value` is the headline's")
+    ap.add_argument("--no-schedule-ab", action="store_true", help="--full: skip the other schedule's loop (rocprofv3 passes: one "
+                                                                  "schedule per trace)")
     ap.add_argument("--profile-steps", type=int, default=3)
     ap.add_argument("--measure-traffic", action="store_true",
                     help="N = 1: measure roofline.traffic in THIS run -- two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; separate "
@@ -182,6 +224,8 @@ def main():
                     help="launch the N ranks, count them with one all-reduce (gloo, no GPU touched), print {n_gpus, ranks_seen} "
                          "and exit: the CPU test of the --gpus N launch path")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     inflight_explicit = args.inflight is not None
     if args.inflight is None:
         args.inflight = 1
@@ -258,9 +302,11 @@ def main():
         else:
             dist.init_process_group(args.dist_backend)
 
-    from omnidata_amd.build import build
-    if rank == 0 or not os.path.exists(os.path.join(ROOT, "omnidata_amd", "libdptx.so")):
-        build()
+    # the library build() left is used as it is: load_library() checks its embedded source hash and rebuilds only a missing or
+    # stale one, so a run on a tree it may not write to works (build() itself always takes a lock file in the object directory)
+    from omnidata_amd.engine import load_library
+    if rank == 0:
+        load_library()
     if world > 1:
         dist.barrier()
     from omnidata_amd.dist import build_replicated_engine
@@ -306,13 +352,16 @@ def main():
     # the timed loop: K steps, each ONE forward of one batch; with --inflight n > 1 consecutive steps go to n handles on n
     # streams (one copy of the weights) and overlap -- every step is enqueued inside the timed region and complete at its end
     from omnidata_amd.pipeline import ForwardPipeline
-    from omnidata_amd.telemetry import GpuTelemetry
-    tele = GpuTelemetry(local_rank) if rank == 0 else None
+    tele = None
+    if rank == 0 and args.full:
+        from omnidata_amd.telemetry import GpuTelemetry
+        tele = GpuTelemetry(local_rank)
     tele_idle = tele.read_once() if tele is not None else None
     tele_log = {}
 
     def timed(e_, inflight, steps, warmup, x_, y_, dual_=False, y2_=None, tag=None):
-        """seconds for `steps` forwards of x_ on engine e_ (weights loaded) with `inflight` forwards in flight, all finite?
+        """seconds for `steps` forwards of x_ on engine e_ (weights loaded) with `inflight` forwards in flight, all finite?, and
+        the output tensors of the last step ((out,) or (out_normal, out_depth)).
         tag: record the GPU's clock / power / temperature over the timed region under tele_log[tag] (sampling thread, no GPU work)"""
         pipe = ForwardPipeline.from_engine(e_, depth=inflight) if inflight > 1 else None
         ys_ = [y_] + [torch.empty_like(y_) for _ in range(inflight - 1)]
@@ -344,7 +393,8 @@ def main():
         ok_ = all(bool(torch.isfinite(t.float()).all()) for t in ys_)
         if pipe is not None:
             pipe.close()
-        return dt_, ok_
+        k_ = (steps - 1) % inflight
+        return dt_, ok_, ((ys_[k_], y2s_[k_]) if dual_ else (ys_[k_],))
 
     # n forwards in flight need n activation arenas next to the model's own (ForwardPipeline.from_engine): refuse what does not
     # fit instead of dying in hipMalloc halfway through the run
@@ -361,14 +411,20 @@ def main():
     # that the engine's internal streams exist before the pipeline's: measured the other way round -- lease r5l3 -- the
     # one-forward-at-a-time loop ran at 1993 instead of ~2600 images/s; HIP maps streams onto a small number of hardware queues.)
     schedule_ab = None
-    if rank == 0 and world == 1 and not args.no_schedule_ab and (args.inflight > 1 or pipeline_fits(2)[0]):
+    if rank == 0 and world == 1 and args.full and not args.no_schedule_ab and (args.inflight > 1 or pipeline_fits(2)[0]):
         other = 1 if args.inflight > 1 else 2
-        dt_o, _ = timed(eng, other, args.steps, args.warmup, x, y, dual, y2 if dual else None, tag=f"inflight{other}")
+        dt_o, _, _ = timed(eng, other, args.steps, args.warmup, x, y, dual, y2 if dual else None, tag=f"inflight{other}")
         schedule_ab = {"inflight": other, "value": round(args.batch * args.steps / dt_o, 2), "unit": "images/s",
                        "ms_per_step": round(1e3 * dt_o / args.steps, 3),
                        "note": "same process, same weights, measured right before the headline loop"}
-    elapsed, finite = timed(eng, args.inflight, args.steps, args.warmup, x, y, dual, y2 if dual else None, tag=f"inflight{args.inflight}")
+    elapsed, finite, last = timed(eng, args.inflight, args.steps, args.warmup, x, y, dual, y2 if dual else None,
+                                  tag=f"inflight{args.inflight}")
     assert finite
+    # the last timed step's results, before any later forward reuses the buffers (rank 0's batch)
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(dict(zip(("normal", "depth"), last)) if dual else {args.task: last[0]}, args.dump_outputs)
+        dumped = {"dir": args.dump_outputs, "outputs": dumped}
     # what proves that N ranks ran, each on its own GPU: an all-reduce of 1, every rank's device index and own clock
     ranks_seen, rank_devices, per_rank = 1, [local_rank], [args.batch * args.steps / elapsed]
     if world > 1:
@@ -387,7 +443,7 @@ def main():
     # ---- roofline of the dominant kernel family: HIP events around every launch, separate passes
     roofline = None
     breakdown = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.measure_traffic or args.profile_dump):
         eng.set_profiling(True)
         acc = {}
         for _ in range(max(1, args.profile_steps)):
@@ -453,7 +509,7 @@ def main():
     cpu_baseline = None
     parity = None
     oracle_ref = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle.dpt_oracle import dpt_forward, dpt_forward_dual, dpt_forward_vitl16
         sd = make_sd()
         if large:
@@ -514,8 +570,8 @@ def main():
                         x3_groups=args.parity_x3_groups, backbone=args.backbone)
             pe.load_state_dict(sd)
             pm = max_abs(pe, oracle_ref)
-            pdt1, _ = timed(pe, 1 if args.inflight > 1 else 2, args.steps, args.warmup, x, y, dual, y2 if dual else None)
-            pdt, _ = timed(pe, args.inflight, args.steps, args.warmup, x, y, dual, y2 if dual else None)   # the headline's schedule
+            pdt1, _, _ = timed(pe, 1 if args.inflight > 1 else 2, args.steps, args.warmup, x, y, dual, y2 if dual else None)
+            pdt, _, _ = timed(pe, args.inflight, args.steps, args.warmup, x, y, dual, y2 if dual else None)   # the headline's schedule
             parity["parity_mode"] = {"dtype": args.parity_dtype,
                                      "x3_groups": args.parity_x3_groups or "default (all layer groups but the ViT blocks)",
                                      "value": round(args.batch * args.steps / pdt, 2), "unit": "images/s",
@@ -531,7 +587,7 @@ def main():
                 for k in (("scratch.output_conv.0.weight", "depth.scratch.output_conv.0.weight") if dual else ("scratch.output_conv.0.weight",)):
                     pe.set_layer_precision(k, 2)
                 pm2 = max_abs(pe, oracle_ref)
-                pdt, _ = timed(pe, args.inflight, args.steps, args.warmup, x, y, dual, y2 if dual else None)
+                pdt, _, _ = timed(pe, args.inflight, args.steps, args.warmup, x, y, dual, y2 if dual else None)
                 parity["parity_mode_head0_2mfma"] = {"dtype": "mixed", "layer_precision": {"scratch.output_conv.0.weight": 2},
                                                      "value": round(args.batch * args.steps / pdt, 2), "unit": "images/s",
                                                      "ms_per_step": round(1e3 * pdt / args.steps, 3), "max_abs": round(pm2, 6),
@@ -542,7 +598,7 @@ def main():
     # ---- BASELINE.json configs[2] and configs[4] next to the headline (configs[1]): short runs of the depth head and of the
     # dual-task forward (bf16 and with the fp8 decoder) under the same protocol, so that the driver's one default call sees them
     also = None
-    if rank == 0 and world == 1 and not args.no_also and args.task == "normal" and not large and args.dtype == "bf16":
+    if rank == 0 and world == 1 and args.full and not args.no_also and args.task == "normal" and not large and args.dtype == "bf16":
         from omnidata_amd.engine import Engine
         also = []
         # (dtype2 "fp8": the default preset -- six decoder convolutions on e4m3, within 2 x the bf16 mode's angular error;
@@ -563,8 +619,8 @@ def main():
             if dtype2.startswith("fp8"):
                 e2.calibrate_fp8(x2)
             n2 = max(4, min(args.steps, 20))
-            dt2o, _ = timed(e2, 1 if args.inflight > 1 else 2, n2, 3, x2, ya, d2, yb if d2 else None)   # the other schedule
-            dt2, _ = timed(e2, args.inflight, n2, 3, x2, ya, d2, yb if d2 else None)    # the headline's schedule
+            dt2o, _, _ = timed(e2, 1 if args.inflight > 1 else 2, n2, 3, x2, ya, d2, yb if d2 else None)   # the other schedule
+            dt2, _, _ = timed(e2, args.inflight, n2, 3, x2, ya, d2, yb if d2 else None)    # the headline's schedule
             max_abs2 = None
             if dtype2 == "mixed" and not args.no_cpu_baseline:   # the dual-task parity mode against the oracle (2 images, both heads)
                 from oracle.dpt_oracle import dpt_forward_dual, oracle_threads
@@ -616,10 +672,12 @@ def main():
             "value_inflight2": (round(value, 2) if args.inflight == 2 else ((schedule_ab or {}).get("value") if args.inflight == 1 else None)) if world == 1 else None,
             "headline_schedule": (f"--inflight {args.inflight} given explicitly" if inflight_explicit else
                                   "default: inflight 1 = the drop-in call model(x), one forward at a time"),
-            "telemetry": {"idle_before": tele_idle, **tele_log,
-                          "note": "GPU shader clock / board power / temperature sampled from sysfs by a host thread during each timed "
-                                  "loop (omnidata_amd/telemetry.py): the chip is power-managed, a number is comparable across boxes "
-                                  "and rounds only together with the clock it ran at"},
+            "telemetry": None if tele is None else {
+                "idle_before": tele_idle, **tele_log,
+                "note": "GPU shader clock / board power / temperature sampled from sysfs by a host thread during each timed "
+                        "loop (omnidata_amd/telemetry.py): the chip is power-managed, a number is comparable across boxes "
+                        "and rounds only together with the clock it ran at"},
+            "full": bool(args.full), "dumped_outputs": dumped,
             "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": args.dtype, "io_dtype": args.io,
             "data": "synthetic 384x384 inputs resident in HBM; seeded random weights",

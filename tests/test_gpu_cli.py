@@ -68,7 +68,7 @@ def test_hub_model_and_batch_sizes():
 def test_bench_two_ranks_share_one_gpu_over_gloo():
     r = _run(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
               "--master-port", "29577", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-              "--batch", "4", "--dist-backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--profile-steps", "1"])
+              "--batch", "4", "--dist-backend", "gloo", "--share-gpu", "--full", "--no-cpu-baseline", "--profile-steps", "1"])
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 8 and line["scaling"] == "weak"
@@ -103,3 +103,73 @@ def test_bench_dist_selftest_runs_the_rccl_start_up_path_on_one_gpu():
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     wb = line["config"]["weight_broadcast"]
     assert line["n_gpus"] == 1 and wb["backend"] == "nccl" and wb["bytes"] > 200e6 and "selftest" in wb
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures the headline and nothing of --full; --dump-outputs writes the
+    last timed step's result: the same bits from run to run, and the bits a caller of the engine gets for the bench's input."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["PYTHONPATH"] = ROOT
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "4", "--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "images/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "bf16" and "surface-normal" in line["metric"]
+    assert abs(line["value"] - 4 * 1e3 / line["ms_per_step"]) < 0.01 * line["value"]
+    for k in ("roofline", "cpu_baseline", "parity", "also", "telemetry", "kernel_breakdown", "value_inflight2"):
+        assert line[k] is None, k
+    assert line["config"]["schedule_ab"] is None
+    assert line["dumped_outputs"]["outputs"] == {"normal": {"shape": [4, 3, 384, 384], "images": "all"}}
+    a = np.load(tmp_path / "a" / "normal.npy")
+    assert a.dtype == np.float32 and a.shape == (4, 3, 384, 384) and np.isfinite(a).all()
+    assert np.array_equal(a, np.load(tmp_path / "b" / "normal.npy"))
+    from omnidata_amd.engine import Engine
+    from omnidata_amd.weights import random_state_dict, synthetic_input
+    e = Engine(num_channels=3, max_batch=4, dtype="bf16", device_id=0)
+    e.load_state_dict(random_state_dict(0, 3))
+    y = e.forward(synthetic_input(1000, 4, "normal").to("cuda:0")).cpu().numpy()
+    e.close()
+    assert np.array_equal(a, y)
+
+
+def test_bench_plain_run_writes_nothing_into_a_read_only_tree(tmp_path):
+    """The benchmark may run as a user who cannot write to the tree build() left: it must use the current library as it is
+    (no lock file, no object directory, no rebuild) -- the files of the tree are the same before and after the run."""
+    import shutil
+    import stat
+    from omnidata_amd.engine import load_library
+    load_library()   # the library of this tree, current
+    tree = tmp_path / "tree"
+    tree.mkdir()
+    shutil.copy2(os.path.join(ROOT, "bench.py"), tree)
+    shutil.copytree(os.path.join(ROOT, "include"), tree / "include")
+    shutil.copytree(os.path.join(ROOT, "omnidata_amd"), tree / "omnidata_amd",
+                    ignore=shutil.ignore_patterns("build", "build_*", "__pycache__", "libdptx_*.so"))
+
+    def files():
+        return sorted((str(p.relative_to(tree)), p.stat().st_mtime_ns) for p in tree.rglob("*"))
+
+    before = files()
+    dirs = [tree] + [p for p in tree.rglob("*") if p.is_dir()]
+    for d in dirs:
+        d.chmod(d.stat().st_mode & ~(stat.S_IWUSR | stat.S_IWGRP | stat.S_IWOTH))
+    try:
+        env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+        env["PYTHONPATH"] = str(tree)
+        env["PYTHONDONTWRITEBYTECODE"] = "1"
+        r = subprocess.run([sys.executable, str(tree / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4",
+                            "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, env=env, cwd=str(tmp_path),
+                           timeout=600)
+    finally:
+        for d in dirs:
+            d.chmod(d.stat().st_mode | stat.S_IWUSR)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["value"] > 0 and (tmp_path / "out" / "normal.npy").exists()
+    assert files() == before

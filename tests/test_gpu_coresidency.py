@@ -17,7 +17,7 @@ the one computed alone, bit for bit.
 
 Positive control: a library built with -DDPTX_LN_PACKED_FMA (round 3's arithmetic; `python tests/test_gpu_coresidency.py
 --build-control` builds omnidata_amd/libdptx_lnpk.so) must SHOW the effect in the same loop -- otherwise a green run proves
-nothing.  It runs in a child process (DPTX_LIB is read at load time); without that library the control is skipped.
+nothing.  It runs in a child process (DPTX_LIB is read at load time); a missing or stale control library is built first.
 """
 import json
 import os
@@ -162,14 +162,16 @@ def test_positive_control_packed_fold_shows_the_effect():
     """The same loop on round 3's arithmetic (-DDPTX_LN_PACKED_FMA build) must find mismatches: the test can see what it guards
     against.  xfail (not fail) when the control stays clean -- the effect is a hardware behaviour, absent e.g. on another
     firmware; the product assertions above do not depend on it."""
-    if not os.path.exists(CONTROL_LIB):
-        pytest.skip("no control library: python tests/test_gpu_coresidency.py --build-control")
     # a control library left over from older sources lacks entry points the bindings expect (round 6: it failed the suite that
-    # way once): it must carry the hash of TODAY's sources under the control's flags
+    # way once): it must carry the hash of TODAY's sources under the control's flags.  A missing or stale one is built here
+    # (a git-ignored build product: a fresh checkout has none)
     from omnidata_amd.build import source_hash
     from omnidata_amd.engine import _embedded_hash
-    if _embedded_hash(CONTROL_LIB) != source_hash(CONTROL_FLAGS.split()):
-        pytest.skip("stale control library (built from other sources): python tests/test_gpu_coresidency.py --build-control")
+    if not os.path.exists(CONTROL_LIB) or _embedded_hash(CONTROL_LIB) != source_hash(CONTROL_FLAGS.split()):
+        b = subprocess.run([sys.executable, os.path.abspath(__file__), "--build-control"], capture_output=True, text=True,
+                           env=dict(os.environ, PYTHONPATH=ROOT), cwd=ROOT, timeout=1800)
+        assert b.returncode == 0, b.stdout[-3000:] + b.stderr[-3000:]
+    assert _embedded_hash(CONTROL_LIB) == source_hash(CONTROL_FLAGS.split()), "the control library was not rebuilt"
     env = dict(os.environ, DPTX_LIB=CONTROL_LIB, PYTHONPATH=ROOT)
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--control"], capture_output=True, text=True, env=env, cwd=ROOT,
                        timeout=900)
