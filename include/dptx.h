@@ -337,7 +337,7 @@ int dptx_op_stem_conv(int32_t dtype, const float* x, const void* Wt, void* y, in
 /* qkv[B*S,3*H*64] packed (which, head, dim) -> out[B*S,H*64]; softmax(q k^T / 8) v. */
 int dptx_op_attention(int32_t dtype, const void* qkv, void* out, int32_t B, int32_t S,
                       int32_t heads, void* stream);
-/* y16[M,768] = LayerNorm(x32[M,768]; gamma, beta, eps) */
+/* y16[M,C] = LayerNorm(x32[M,C]; gamma, beta, eps), C = 768 or 1024 */
 int dptx_op_layernorm(int32_t dtype, const float* x, const float* gamma, const float* beta,
                       void* y, int32_t M, int32_t C, float eps, void* stream);
 /* GroupNorm(32) (+ optional residual R, + optional ReLU) on NHWC 16-bit, out of place.  scratch_f32 receives the
@@ -345,6 +345,16 @@ int dptx_op_layernorm(int32_t dtype, const float* x, const float* gamma, const f
 int dptx_op_groupnorm(int32_t dtype, const void* X, const float* gamma, const float* beta,
                       const void* R, void* Y, int32_t B, int32_t HW, int32_t C, int32_t relu,
                       float eps, void* scratch_f32, void* stream);
+/* The stem's GroupNorm(32) + ReLU + MaxPool2dSame(3, 2) on NHWC 16-bit: Y[B,H/2,W/2,C] = maxpool(relu(gn(X[B,H,W,C]))) with
+ * SAME padding (0, 1) of -inf.  H and W even (odd sizes -> DPTX_E_INVALID); scratch_f32 as for dptx_op_groupnorm. */
+int dptx_op_gn_relu_maxpool(int32_t dtype, const void* X, const float* gamma, const float* beta, void* Y, int32_t B,
+                            int32_t H, int32_t W, int32_t C, float eps, void* scratch_f32, void* stream);
+/* The cls rows of the token stream (vit.py:141-147): row b*S of X (fp32, may be NULL) = cls + pos[0..C); X16 (optional): its
+ * 16-bit copy; row_stats (optional): its (sum, sum of squares) per 128-column block as float2 records row_stats[b*S][0 .. C/128)
+ * (row stride 8 records, so C <= 1024 with row_stats); X8 (optional): its e4m3 copy of (value * q_scale).  C % 128 == 0.  Other
+ * rows are not touched. */
+int dptx_op_cls_rows(int32_t dtype, const float* cls, const float* pos, float* X, int32_t B, int32_t S, int32_t C, void* X16,
+                     float* row_stats, void* X8, float q_scale, void* stream);
 /* Debug: s_memtime stamps of the GEMM k-loop (block 0, lane 0 of each wave; [wave][64 k-tiles][4 phases] int64) into a
  * device buffer of 8*64*4 int64 for every following GEMM launch; NULL switches it off (tools/gpu/gemm_trace.py). */
 int dptx_debug_set_trace(void* dev_buf);

@@ -2093,6 +2093,27 @@ int dptx_op_groupnorm(int32_t dtype, const void* X, const float* gamma, const fl
   return launch_gn_apply(dtype, g, g_op_planes, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
 }
 
+// the stem's GroupNorm + ReLU + MaxPool2dSame(3, 2): the stats pass, then the fused apply / pool.  Odd H / W are refused by
+// launch_gn_relu_maxpool itself -- the guard the forward relies on -- and deliberately not here, so that the op-level test
+// reaches it (the stats pass before it is harmless at any size).
+int dptx_op_gn_relu_maxpool(int32_t dtype, const void* X, const float* gamma, const float* beta, void* Y, int32_t B, int32_t H,
+                            int32_t W, int32_t C, float eps, void* scratch_f32, void* stream) {
+  if (scratch_f32 == nullptr) return DPTX_E_INVALID;
+  hipError_t r = launch_gn_stats(dtype, X, (float*)scratch_f32, B, H * W, C, g_op_planes, (hipStream_t)stream);
+  if (r != hipSuccess) return DPTX_E_HIP;
+  return launch_gn_relu_maxpool(dtype, X, Y, gamma, beta, (const float*)scratch_f32, B, H, W, C, eps, g_op_planes,
+                                (hipStream_t)stream) == hipSuccess
+             ? DPTX_OK
+             : DPTX_E_HIP;
+}
+
+int dptx_op_cls_rows(int32_t dtype, const float* cls, const float* pos, float* X, int32_t B, int32_t S, int32_t C, void* X16,
+                     float* row_stats, void* X8, float q_scale, void* stream) {
+  if (row_stats != nullptr && C > 8 * 128) return DPTX_E_INVALID;  // records have a row stride of 8: C <= 1024
+  return launch_cls_rows(dtype, cls, pos, X, B, S, C, X16, row_stats, (hipStream_t)stream, X8, q_scale) == hipSuccess ? DPTX_OK
+                                                                                                                      : DPTX_E_HIP;
+}
+
 // ---- arena debugging (tests/test_gpu_poison.py): a forward must not read an arena byte it did not write itself
 int dptx_debug_arena_fill(dptx_handle h, int32_t byte_value) {
   if (!h) return DPTX_E_INVALID;

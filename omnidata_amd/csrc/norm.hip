@@ -286,6 +286,8 @@ __global__ __launch_bounds__(256) void gn_relu_maxpool_kernel(const uint16_t* __
 
 hipError_t launch_gn_relu_maxpool(int mode, const void* X, void* Y, const float* gamma, const float* beta,
                                   const float* partial, int B, int H, int W, int C, float eps, Planes pl, hipStream_t stream) {
+  // the kernel pads (0, 1): SAME padding of an odd size is (1, 1), which it does not implement
+  if ((H & 1) || (W & 1) || C % 64 != 0 || C > 1024) return hipErrorInvalidValue;
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   const int total = Ho * Wo * (C / 8);
   // few, fat blocks: every block re-reduces the chunk partials of its image in its prologue

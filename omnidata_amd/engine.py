@@ -83,6 +83,8 @@ ABI = [
     ("dptx_op_attention", C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("dptx_op_layernorm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp]),
     ("dptx_op_groupnorm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp]),
+    ("dptx_op_gn_relu_maxpool", C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp]),
+    ("dptx_op_cls_rows", C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, C.c_float, _vp]),
     ("dptx_debug_set_trace", C.c_int, [_vp]),
     ("dptx_debug_set_gemm_flags", C.c_int, [C.c_int32]),
     ("dptx_debug_arena_fill", C.c_int, [_vp, _i32]),

@@ -87,3 +87,75 @@ class PlaneArena:
 
     def release(self):
         load_library().dptx_op_set_planes(0, 0)
+
+
+# ------------------------------------------------------------------ inputs whose statistics differ row by row / group by group
+# Normalisation kernels that apply one row's (group's, image's) statistics to another pass on inputs whose statistics are the
+# same everywhere: the output moves by less than the 16-bit tolerance.  These generators give every row and every (image,
+# group) pair statistics of its own, so that any such mix-up moves the output by many tolerances.  CPU tensors, fp32 (rows)
+# or fp64 (NHWC); deterministic in `seed`.
+
+def rows_with_stats(M, C, r_values=(0.0, 1.0, 8.0), outliers=False, near_constant=True, seed=0):
+    """x [M, C] fp32 with statistics of its own in every row, and r = |mean| / std of every row (fp64, measured on x).
+
+    Row m: a standardised Gaussian scaled by sigma_m = 2^e_m, e_m = (7 m mod 13) - 6 +- 1/4 (over [-6, 6], not monotonic;
+    adjacent rows differ by a factor of 2^5.5 at least), plus mean_m = +-r_m sigma_m with r_m cycling through `r_values`.  outliers: 1-4 channels of every row then sit at
+    30-300 sigma_m (either sign).  near_constant: row M // 2 becomes mean 3, sigma 3e-3 (r = 1000) without outliers.
+    max |x| < 2^6.25 (max r + 300): inside fp16 for max r <= 64."""
+    g = torch.Generator().manual_seed(seed)
+    e = (7 * torch.arange(M) % 13 - 6).double() + 0.5 * torch.rand(M, generator=g, dtype=torch.float64) - 0.25
+    sigma = torch.exp2(e)
+    r = torch.tensor(r_values, dtype=torch.float64)[torch.arange(M) % len(r_values)]
+    sign = torch.where(torch.rand(M, generator=g) < 0.5, -1.0, 1.0).double()
+    z = torch.randn(M, C, generator=g, dtype=torch.float64)
+    z = (z - z.mean(1, keepdim=True)) / z.std(1, unbiased=False, keepdim=True)
+    if outliers:
+        for m in range(M):
+            k = int(torch.randint(1, 5, (1,), generator=g))
+            ch = torch.randperm(C, generator=g)[:k]
+            z[m, ch] = (30.0 + 270.0 * torch.rand(k, generator=g, dtype=torch.float64)) * torch.where(
+                torch.rand(k, generator=g) < 0.5, -1.0, 1.0).double()
+    if near_constant:
+        m = M // 2
+        z[m] = torch.randn(C, generator=g, dtype=torch.float64)
+        sigma[m], r[m], sign[m] = 3e-3, 1000.0, 1.0
+    x = ((sign * r * sigma).unsqueeze(1) + sigma.unsqueeze(1) * z).float()
+    xd = x.double()
+    return x, xd.mean(1).abs() / xd.std(1, unbiased=False)
+
+
+def nhwc_with_group_stats(B, HW, C, groups=32, seed=0):
+    """X [B, HW, C] fp64 with statistics of its own for every (image, group) pair of GroupNorm(groups).
+
+    sigma[b, g] = 2^((5 g + 3 b) % 7 - 3): any two adjacent groups, and the same group of adjacent images, differ by a factor
+    of 2 at least (5 and 3 are nonzero mod 7).  mean[b, g] = (-1)^(g + b) 1.5 sigma[b, g]: adjacent means have opposite signs,
+    so they lie 1.5 (sigma + sigma') apart.  Values within 2^3 * 6 of zero: inside fp16 and its hi / lo planes."""
+    g = torch.Generator().manual_seed(seed)
+    cpg = C // groups
+    gi = torch.arange(groups).view(1, groups)
+    bi = torch.arange(B).view(B, 1)
+    sigma = torch.exp2(((5 * gi + 3 * bi) % 7 - 3).double())                  # [B, G]
+    mean = torch.where((gi + bi) % 2 == 0, 1.5, -1.5).double() * sigma
+    z = torch.randn(B, HW, groups, cpg, generator=g, dtype=torch.float64).clamp(-4.0, 4.0)
+    x = mean.view(B, 1, groups, 1) + sigma.view(B, 1, groups, 1) * z
+    return x.reshape(B, HW, C)
+
+
+def group_max(t, groups=32):
+    """max |t| of every (image, group) of an NHWC [B, ..., C] tensor -> [B, groups] (fp64)."""
+    B, C = t.shape[0], t.shape[-1]
+    return t.double().abs().reshape(B, -1, groups, C // groups).transpose(1, 2).reshape(B, groups, -1).amax(-1)
+
+
+def per_group_err(got, ref, groups=32, scale=None):
+    """max |got - ref| / scale of every (image, group) of NHWC [B, ..., C] tensors -> [B, groups] (fp64); scale [B, groups]
+    defaults to the group's max |ref|.  Behind a ReLU, pass the group's scale BEFORE the ReLU: a group the ReLU clips almost
+    to zero keeps the absolute rounding of its pre-activation."""
+    d = group_max(got.double() - ref.double(), groups)
+    return d / (group_max(ref, groups) if scale is None else scale).clamp_min(1e-30)
+
+
+def per_row_err(got, ref):
+    """max |got - ref| / max |ref| of every row of [M, N] tensors -> [M] (fp64)."""
+    d = (got.double() - ref.double()).abs().amax(-1)
+    return d / ref.double().abs().amax(-1).clamp_min(1e-30)

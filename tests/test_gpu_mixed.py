@@ -143,6 +143,13 @@ def test_fp16x3_norms_attention():
         ar.release()
 
 
+def test_fp16x3_norms_per_row_and_group_statistics():
+    """the fp16 hi / lo planes of tests/test_gpu_x3.py's plane_norms_per_stats (the stem's GroupNorm + ReLU + MaxPool2dSame runs
+    in this mode under the default `mixed` policy)"""
+    from tests.test_gpu_x3 import plane_norms_per_stats
+    plane_norms_per_stats(F16X3, torch.float16, TOL)
+
+
 # (dtype, x3_groups, max-abs bar): the first two are parity modes (north_star 1e-3); the third shows what the policy that
 # only protects the ResNet stages buys (emulated floor 1.5e-3 on these weights, oracle/precision_policy.py)
 POLICIES = [("mixed", 0, 1e-3), ("fp16x3", 0, 1e-3), ("mixed", "resnet", 2.5e-3)]

@@ -6,7 +6,8 @@ import torch.nn.functional as F
 
 from omnidata_amd.engine import load_library
 from omnidata_amd.model import DPTDepthModel
-from tests.gpu_util import PlaneArena, ptr, rel_err, stream
+from tests.gpu_util import (PlaneArena, group_max, nhwc_with_group_stats, per_group_err, per_row_err, ptr, rel_err, rows_with_stats,
+                            stream)
 from tests.test_gpu_e2e import oracle_case
 from oracle.dpt_oracle import mean_angular_error_deg, ssi_align
 
@@ -101,6 +102,69 @@ def test_x3_norms_and_upsample():
         assert rel_err(ar.value(V), ref) < TOL
     finally:
         ar.release()
+
+
+def plane_norms_per_stats(mode, dtype, tol):
+    """LayerNorm, GroupNorm and the stem's GroupNorm + ReLU + MaxPool2dSame on inputs with statistics of their own in every row /
+    (image, group) (tests/gpu_util.py), in a hi / lo plane mode: against fp64 of the stored hi + lo values, row by row and group
+    by group (tests/test_gpu_ops.py has the 16-bit modes and the bars' derivation)."""
+    from tests.test_gpu_ops import GN_CASES, groupnorm_ref, ln_row_bar, maxpool_same_ref
+    lib = load_library()
+    worst = {}
+    for C in (768, 1024):
+        for fam in (dict(r_values=(0.0, 1.0, 8.0)), dict(r_values=(0.0, 1.0), outliers=True)):
+            M = 1155
+            x, r = rows_with_stats(M, C, seed=100 + C, **fam)
+            x = x.to(DEV)
+            ar = PlaneArena(M * C + 4096, dtype=dtype)
+            try:
+                gm, bt = torch.randn(C, device=DEV), torch.randn(C, device=DEV)
+                y = ar.empty(M, C)
+                assert lib.dptx_op_layernorm(mode, ptr(x), ptr(gm), ptr(bt), ptr(y), M, C, 1e-6, stream()) == 0
+                err = per_row_err(ar.value(y), F.layer_norm(x.double(), (C,), gm.double(), bt.double(), 1e-6)).cpu()
+                bar = ln_row_bar(tol, r)
+                worst["layernorm"] = max(worst.get("layernorm", 0.0), float((err / bar).max()))
+                assert (err <= bar).all(), (C, fam, torch.nonzero(err > bar)[:5, 0].tolist())
+            finally:
+                ar.release()
+    for B, HW, C, relu, res in GN_CASES:
+        ar = PlaneArena(3 * B * HW * C + 4096, dtype=dtype)
+        try:
+            X = ar.put(nhwc_with_group_stats(B, HW, C, seed=110 + C))
+            R = ar.put(g(B, HW, C, seed=111)) if res else None
+            Y = ar.empty(B, HW, C)
+            gm, bt = torch.randn(C, device=DEV), torch.randn(C, device=DEV)
+            pix = min(max(16384 // C, 16), 256)
+            scratch = torch.empty(B * ((HW + pix - 1) // pix) * 64, device=DEV)
+            assert lib.dptx_op_groupnorm(mode, ptr(X), ptr(gm), ptr(bt), ptr(R), ptr(Y), B, HW, C, relu, 1e-5, ptr(scratch), stream()) == 0
+            Rv = None if R is None else ar.value(R)
+            err = per_group_err(ar.value(Y), groupnorm_ref(ar.value(X), gm, bt, Rv, relu),
+                                scale=group_max(groupnorm_ref(ar.value(X), gm, bt, Rv, 0)))
+            worst["groupnorm"] = max(worst.get("groupnorm", 0.0), float(err.max()) / tol)
+            assert (err < tol).all(), ((B, HW, C), torch.nonzero(err >= tol)[:5].tolist())
+        finally:
+            ar.release()
+    C = 64
+    for B, H, W in ((1, 192, 192), (3, 32, 48), (2, 144, 224)):
+        ar = PlaneArena(2 * B * H * W * C + 4096, dtype=dtype)
+        try:
+            X = ar.put(nhwc_with_group_stats(B, H * W, C, seed=120 + H).view(B, H, W, C))
+            Y = ar.empty(B, H // 2, W // 2, C)
+            gm, bt = torch.randn(C, device=DEV), torch.randn(C, device=DEV)
+            scratch = torch.empty(B * ((H * W + 255) // 256) * 64, device=DEV)
+            assert lib.dptx_op_gn_relu_maxpool(mode, ptr(X), ptr(gm), ptr(bt), ptr(Y), B, H, W, C, 1e-5, ptr(scratch), stream()) == 0
+            y = groupnorm_ref(ar.value(X).view(B, H * W, C), gm, bt, None, 0)
+            ref = maxpool_same_ref(F.relu(y).view(B, H, W, C))
+            err = per_group_err(ar.value(Y).view(B, -1, C), ref.reshape(B, -1, C), scale=group_max(y))
+            worst["gn_relu_maxpool"] = max(worst.get("gn_relu_maxpool", 0.0), float(err.max()) / tol)
+            assert (err < tol).all(), ((B, H, W), torch.nonzero(err >= tol)[:5].tolist())
+        finally:
+            ar.release()
+    print(f"\n[plane mode {mode}] worst err / bar: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+
+
+def test_x3_norms_per_row_and_group_statistics():
+    plane_norms_per_stats(X3, torch.bfloat16, TOL)
 
 
 @pytest.mark.parametrize("task,C,seed,B", [("normal", 3, 0, 1), ("depth", 1, 0, 1), ("normal", 3, 1, 2)])

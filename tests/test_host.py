@@ -558,3 +558,45 @@ def test_eval_checkpoint_tool_host_side(tmp_path):
         torch.save({"state_dict": {}}, tmp_path / "c.ckpt")
         with pytest.raises(RuntimeError, match="no CPU fallback"):
             ec.evaluate("normal", str(tmp_path / "c.ckpt"), [str(tmp_path / "i.png")])
+
+
+def test_stat_generators_make_every_mixup_visible():
+    """tests/gpu_util.py's inputs with per-row / per-(image, group) statistics, checked on the fp64 reference itself: applying a
+    neighbour's statistics -- row m's to row m + 1, a swap of two adjacent groups, of two channels across a group boundary, of
+    two images -- must move the normalised output of the rows / groups it touches by far more than the 16-bit tolerance
+    (6e-3 of the row's / group's own max, tests/gpu_util.py OUT_TOL), or the GPU tests built on them could not see it."""
+    import torch.nn.functional as F
+    from tests.gpu_util import nhwc_with_group_stats, per_group_err, per_row_err, rows_with_stats
+    big = 50 * 6e-3
+    for outliers in (False, True):
+        x, r = rows_with_stats(301, 768, outliers=outliers, seed=3)
+        assert x.dtype == torch.float32 and torch.isfinite(x).all() and x.abs().max() < 60000
+        xd = x.double()
+        sig = xd.std(1, unbiased=False)
+        assert sig.max() / sig.min() > 2 ** 11 and r.max() > 500                  # spread over 2^12, one near-constant row
+        assert not (sig[1:] >= sig[:-1]).all() and not (sig[1:] <= sig[:-1]).all()
+        ref = F.layer_norm(xd, (768,))
+        mu, rs = xd.mean(1, keepdim=True), sig.unsqueeze(1).reciprocal()
+        shifted = (xd[1:] - mu[:-1]) * rs[:-1]                                    # row m + 1 with row m's statistics
+        assert per_row_err(shifted, ref[1:]).min() > big
+    for B, HW, C in ((3, 100, 64), (2, 36, 128), (3, 17, 256), (2, 9, 1024)):
+        X = nhwc_with_group_stats(B, HW, C, seed=B + C)
+        assert X.abs().max() < 60000
+        ref = F.group_norm(X.permute(0, 2, 1), 32).permute(0, 2, 1)
+        cpg = C // 32
+        for g in range(31):
+            Xs = X.clone()                                                        # swap groups g and g + 1
+            Xs[..., g * cpg:(g + 1) * cpg], Xs[..., (g + 1) * cpg:(g + 2) * cpg] = X[..., (g + 1) * cpg:(g + 2) * cpg], X[..., g * cpg:(g + 1) * cpg]
+            got = F.group_norm(Xs.permute(0, 2, 1), 32).permute(0, 2, 1)
+            # the output channel of group g now holds values normalised with the statistics of group g + 1's data
+            assert per_group_err(got, ref)[:, g].min() > big
+            Xc = X.clone()                                                        # swap the channels either side of the boundary
+            c = (g + 1) * cpg
+            Xc[..., c - 1], Xc[..., c] = X[..., c], X[..., c - 1]
+            got = F.group_norm(Xc.permute(0, 2, 1), 32).permute(0, 2, 1)
+            assert per_group_err(got, ref)[:, g].min() > big
+        for b in range(B - 1):                                                    # images b and b + 1 with each other's statistics
+            mu = X.view(B, HW, 32, cpg).mean((1, 3), keepdim=True)
+            sd = X.view(B, HW, 32, cpg).std((1, 3), unbiased=False, keepdim=True)
+            wrong = ((X.view(B, HW, 32, cpg)[b] - mu[b + 1]) / sd[b + 1]).reshape(1, HW, C)
+            assert per_group_err(wrong, ref[b:b + 1]).min() > big
