@@ -369,12 +369,8 @@ int dptx_debug_arena_layout(dptx_handle h, char* dst, size_t capacity);
 /* One 64-bit word sum per arena buffer, sub-batch region and plane of the layout the LAST forward used, computed on `stream`
  * behind that forward: out_dev[(plane * regions + region) * nbuf + buf] (uint64, device memory), buffers in the order of
  * dptx_debug_arena_layout.  Returns the number of sums; with out_dev = NULL the capacity needed.  Two forwards of one input
- * must give the same vector; the first entry that differs names the tensor (tools/gpu/r4_hunt.py). */
+ * must give the same vector; the first entry that differs names the tensor. */
 int dptx_debug_arena_checksums(dptx_handle h, void* out_dev, int32_t capacity, void* stream);
-/* Word sums of the ViT buffers {lnst, Hn, QKV, AO, F1} after every launch of the ViT blocks of the following single-stream
- * forwards: dev_buf[launch * 5 + buffer] (uint64 device memory, capacity entries; launch 0 = after the cls rows, then qkv /
- * attention / proj / fc1 / fc2 per block).  NULL switches it off. */
-int dptx_debug_set_launch_sums(dptx_handle h, void* dev_buf, int32_t capacity);
 /* Debug / tests: switches (per calling host thread) of the 256x256 GEMM kernel's launch form -- 1: staged epilogue instead of the
  * register-direct one, 2: one block per tile instead of the persistent tile loop, 4: the lockstep loop instead of the ping-pong
  * schedule in the two-plane 128x128 kernel.  Results do not depend on them. */

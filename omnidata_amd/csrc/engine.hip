@@ -444,14 +444,10 @@ struct dptx_engine {
   }
   void* q8(const void* p) const { return d_arena + arena_single + ((const char*)p - d_arena) / 2; }  // e4m3 copy of an arena tensor
   // fused head tail (head.hip): no stage taps wanted; a 3-MFMA second head conv has its fused form for fp16 planes only
-  // (head_tail_x3_kernel: "mixed", fp16x3); DPTX_HEAD_FUSED=0 keeps the three launches (DPTX_HEAD_FUSED_X3=0: for the x3 form only)
+  // (head_tail_x3_kernel: "mixed", fp16x3)
   bool head_fused(bool conv2_x3) const {
-    static int env = -1, env3 = -1;
-    if (env < 0) { const char* t = getenv("DPTX_HEAD_FUSED"); env = (t && t[0] == '0') ? 0 : 1; }
-    if (env3 < 0) { const char* t = getenv("DPTX_HEAD_FUSED_X3"); env3 = (t && t[0] == '0') ? 0 : 1; }
-    if (env != 1 || taps_on) return false;
-    if (!conv2_x3) return true;
-    return env3 == 1 && (cfg.dtype == DPTX_DTYPE_MIXED || cfg.dtype == DPTX_DTYPE_FP16X3);
+    if (taps_on) return false;
+    return !conv2_x3 || cfg.dtype == DPTX_DTYPE_MIXED || cfg.dtype == DPTX_DTYPE_FP16X3;
   }
   size_t tok_tap_stride = 0;      // floats per token-stream snapshot
   float* d_tok_taps = nullptr;  // [13][max_batch*(max tokens)*768] fp32 copies of the token stream (taps_on)
@@ -459,9 +455,6 @@ struct dptx_engine {
   double exec_macs = 0.0;
   int last_batch = 0;
   int last_regions = 1;  // sub-batch regions the last forward used (1: the whole-batch plan)
-  // debug (dptx_debug_set_launch_sums): word sums of the ViT buffers after every launch of the ViT blocks, [launch][5] uint64
-  unsigned long long* d_lsums = nullptr;
-  int lsum_cap = 0, lsum_n = 0;
   // optional per-launch timing (one event after every launch; kernels are serialized on the stream)
   bool profiling = false;
   std::vector<hipEvent_t> events;
@@ -825,6 +818,12 @@ struct Run {
       e->event_name.emplace_back(w);
     }
   }
+  // one GEMM of the schedule: its MACs per image (executed and algorithmic), then the launch
+  void gemm(int mode, const GemmParams& p, const char* name) {
+    exec_macs += (double)p.M / B * p.N * p.K;
+    cat_macs[0] += (double)p.M / B * p.N * p.K;
+    chk(launch_gemm(mode, p, st), name, 0);
+  }
   // MIXED dtype, decoder groups: which arena tensors currently have a valid lo plane (set by their producers)
   std::unordered_map<const void*, bool> lo_valid_;
   bool has_lo(const void* p) const {
@@ -873,8 +872,6 @@ struct Run {
       p.A = e->q8(in); p.W = e->w8(wkey); p.a_bytes /= 2; p.a_relu = 0;
       p.out_scale = 1.0f / q8_scale_of(in); p.out_scale_v = e->wscale(wkey);
     }
-    exec_macs += (double)p.M / B * p.N * p.K;
-    cat_macs[0] += (double)p.M / B * p.N * p.K;
     int mode = f8 ? MODE_FP8 : dt;
     if (out_lo >= 0 && e->mixed()) {  // per-layer policy
       const bool x3 = e->layer_x3(wkey, cur_group), a_lo = e->layer_reads_lo(wkey, cur_group);
@@ -889,17 +886,13 @@ struct Run {
       p.epi2 = (!x3 && (out_lo || r1lo || r2lo)) ? 1 : 0;
       mark_lo(out, out_lo != 0);
     }
-    chk(launch_gemm(mode, p, st), wkey.c_str(), 0);
+    gemm(mode, p, wkey.c_str());
     if (slot >= 0) q8_measure(out, (size_t)p.M * p.N, q == 2, slot);
   }
 
   // GroupNorm statistics come out of the producing conv's epilogue when an image's rows are whole 32-row MFMA blocks
-  // (always at 384x384; DPTX_GN_FUSED=0 keeps the separate statistics launch for A/B runs)
-  static bool gn_fusable(int HW) {
-    static int env = -1;
-    if (env < 0) { const char* t = getenv("DPTX_GN_FUSED"); env = (t && t[0] == '0') ? 0 : 1; }
-    return env == 1 && HW % 32 == 0;
-  }
+  // (always at 384x384)
+  static bool gn_fusable(int HW) { return HW % 32 == 0; }
   void gn_stats(const void* X, float* part, int HW, int C) { chk(launch_gn_stats(dt, X, part, B, HW, C, e->pl, st), "gn_stats", 2); }
   void gn_apply(void* X, const std::string& nkey, float* part, int HW, int C, int relu, const void* R = nullptr,
                 const std::string& rkey = "", const float* rpart = nullptr) {
@@ -1036,9 +1029,7 @@ int Run::forward(const void* x, void* y, void* y2) {
     // fp8 ViT (DPTX_FLAG_FP8_VIT): block 0's qkv multiplies the e4m3 copy of the stream
     hn_slot = E->fp8_use(vp + "blocks.0.attn.qkv.weight") ? q8_produce(A(E->Hn)) : -1;
     if (hn_slot >= 0) { p.C8 = E->q8(A(E->Hn)); p.q_relu = 0; p.q_scale = E->act_scale[hn_slot]; }
-    exec_macs += (double)NP * D_VIT * Kp;
-    cat_macs[0] += (double)NP * D_VIT * Kp;
-    chk(launch_gemm(dt, p, st), "patch_embed.proj", 0);
+    gemm(dt, p, "patch_embed.proj");
   }
   chk(launch_cls_rows(E->mode_of(DPTX_GROUP_VIT), E->f(vp + "cls_token"), pos, s16 ? nullptr : X, B, S, D_VIT,
                       E->ln_fold ? A(E->Hn) : nullptr, E->ln_fold ? lnst : nullptr, st,
@@ -1059,29 +1050,15 @@ int Run::forward(const void* x, void* y, void* y2) {
     E->taps[name] = TapInfo{dst, {B, S, D_VIT, 1}, true, dt};
   };
   tok_tap(0, "tok0");
-  // debug: word sums of {lnst, Hn, QKV, AO, F1} after a launch (single-stream forwards only; tools/gpu/r4_hunt3.py)
-  auto vit_sums = [&]() {
-    if (!E->d_lsums || half) return;
-    const Buf* bufs[5] = {&E->lnst, &E->Hn, &E->QKV, &E->AO, &E->F1};
-    const size_t bytes[5] = {(size_t)M * 8 * 8, tok_elems * 2, (size_t)M * 3 * D_VIT * 2, tok_elems * 2, (size_t)M * D_MLP * 2};
-    if (E->lsum_n + 5 > E->lsum_cap) return;
-    for (int i = 0; i < 5; ++i) {
-      const hipError_t r = launch_checksum(A(*bufs[i]), bytes[i], E->d_lsums + E->lsum_n + i, st);
-      if (err == hipSuccess && r != hipSuccess) { err = r; where = "vit_sums"; }
-    }
-    E->lsum_n += 5;
-  };
-  if (E->d_lsums) { E->lsum_n = 0; (void)hipMemsetAsync(E->d_lsums, 0, (size_t)E->lsum_cap * 8, st); }
-  vit_sums();
 
   // ln: 0 plain; 1 consumer of the folded LayerNorm (qkv, fc1); 2 producer (proj, fc2: 16-bit copy + row statistics)
   // q8_out (fp8 ViT): the consumer of C multiplies on e4m3 operands -- the epilogue also writes C's e4m3 copy (one calibrated
   // power-of-two scale per tensor, like the decoder's: Run::conv)
-  auto dense = [&](const void* A, int a_fp32, const std::string& wkey, int N, int K, void* C, int c_fp32, const float* bias,
+  auto dense = [&](const void* A, const std::string& wkey, int N, int K, void* C, int c_fp32, const float* bias,
                    int act, const void* R1, int r1_fp32, int ln = 0, const float* ln_colsum = nullptr, bool q8_out = false) {
     GemmParams p;
     gemm_params_dense(p, M, N, K);
-    p.A = A; p.a_fp32 = a_fp32; p.W = E->w(wkey); p.C = C; p.c_fp32 = c_fp32; p.bias = bias; p.act = act;
+    p.A = A; p.W = E->w(wkey); p.C = C; p.c_fp32 = c_fp32; p.bias = bias; p.act = act;
     p.R1 = R1; p.r1_fp32 = r1_fp32; p.planes = E->pl;
     if (ln == 1) { p.ln_stats = lnst; p.ln_colsum = ln_colsum; p.ln_nblk = ln_nblk; p.ln_eps = 1e-6f; p.ln_inv_dim = 1.0f / (float)K; }
     if (ln == 2) { p.C16 = this->A(E->Hn); p.row_stats = lnst; p.stats_nblk = 8; }
@@ -1100,9 +1077,7 @@ int Run::forward(const void* x, void* y, void* y2) {
       slot = q8_produce(p.C);
       p.C8 = E->q8(p.C); p.q_relu = 0; p.q_scale = E->act_scale[slot];
     }
-    exec_macs += (double)S * N * K;
-    cat_macs[0] += (double)S * N * K;
-    chk(launch_gemm(mode, p, st), wkey.c_str(), 0);
+    gemm(mode, p, wkey.c_str());
     if (slot >= 0) q8_measure(p.C, (size_t)M * N, 0, slot);
   };
 
@@ -1130,18 +1105,14 @@ int Run::forward(const void* x, void* y, void* y2) {
     p.ksz = 1; p.stride = 1;
     p.c_rpi = NP; p.c_img_rows = NP; p.c_row_off = 0; p.ldc = D_VIT;
     p.bias = clsb; p.bias_per_img = 1; p.act = 2;
-    exec_macs += (double)NP * D_VIT * D_VIT;
-    cat_macs[0] += (double)NP * D_VIT * D_VIT;
-    chk(launch_gemm(dt, p, st), "readout", 0);
+    gemm(dt, p, "readout");
     if (n <= 2) {
       const int f = n == 1 ? 256 : 512, k = n == 1 ? 4 : 2;
       conv(R, gh, gw, D_VIT, pp + "3.weight", 1, 1, 0, 0, gh, gw, f, A(E->T4), E->f(pp + "3.bias"), 0, 0);
       GemmParams d;
       gemm_params_dense(d, B * NP, k * k * f, f);
       d.A = A(E->T4); d.W = E->w(pp + "4.weight"); d.C = A(E->F1); d.bias = E->f(pp + "4.bias"); d.planes = E->pl;
-      exec_macs += (double)NP * k * k * f * f;
-      cat_macs[0] += (double)NP * k * k * f * f;
-      chk(launch_gemm(dt, d, st), "reassemble.deconv", 0);
+      gemm(dt, d, "reassemble.deconv");
       chk(launch_depth_to_space(dt, A(E->F1), A(E->S[n - 1]), B, gh, gw, k, f, E->pl, st), "reassemble.d2s");
       tap(n == 1 ? "l1" : "l2", A(E->S[n - 1]), gh * k, gw * k, f);
     } else if (n == 3) {
@@ -1165,21 +1136,16 @@ int Run::forward(const void* x, void* y, void* y2) {
     const std::string pn = vp + "blocks." + std::to_string(l + 1) + ".";
     const bool q_fc1 = E->fp8_use(p + "mlp.fc1.weight"), q_fc2 = E->fp8_use(p + "mlp.fc2.weight");
     const bool q_next = l + 1 < E->depth && E->fp8_use(pn + "attn.qkv.weight");
-    dense(A(E->Hn), 0, p + "attn.qkv.weight", 3 * D_VIT, D_VIT, A(E->QKV), 0, E->f(p + "attn.qkv.bias"), 0, nullptr, 0, lf ? 1 : 0,
+    dense(A(E->Hn), p + "attn.qkv.weight", 3 * D_VIT, D_VIT, A(E->QKV), 0, E->f(p + "attn.qkv.bias"), 0, nullptr, 0, lf ? 1 : 0,
           lf ? E->f(p + "attn.qkv.lnsum") : nullptr);
-    vit_sums();
     chk(launch_attention(dt, A(E->QKV), A(E->AO), B, S, N_HEADS, E->pl, st), "attention", 1);
-    vit_sums();
     exec_macs += 2.0 * N_HEADS * (double)S * S * 64;
     cat_macs[1] += 2.0 * N_HEADS * (double)S * S * 64;
-    dense(A(E->AO), 0, p + "attn.proj.weight", D_VIT, D_VIT, X, 1, E->f(p + "attn.proj.bias"), 0, X, 1, lf ? 2 : 0, nullptr, q_fc1);
-    vit_sums();
+    dense(A(E->AO), p + "attn.proj.weight", D_VIT, D_VIT, X, 1, E->f(p + "attn.proj.bias"), 0, X, 1, lf ? 2 : 0, nullptr, q_fc1);
     if (!lf) chk(launch_layernorm(dt, X, E->f(p + "norm2.weight"), E->f(p + "norm2.bias"), A(E->Hn), M, D_VIT, 1e-6f, E->pl, st), "ln2", 2);
-    dense(A(E->Hn), 0, p + "mlp.fc1.weight", D_MLP, D_VIT, A(E->F1), 0, E->f(p + "mlp.fc1.bias"), 2, nullptr, 0, lf ? 1 : 0,
+    dense(A(E->Hn), p + "mlp.fc1.weight", D_MLP, D_VIT, A(E->F1), 0, E->f(p + "mlp.fc1.bias"), 2, nullptr, 0, lf ? 1 : 0,
           lf ? E->f(p + "mlp.fc1.lnsum") : nullptr, q_fc2);
-    vit_sums();
-    dense(A(E->F1), 0, p + "mlp.fc2.weight", D_VIT, D_MLP, X, 1, E->f(p + "mlp.fc2.bias"), 0, X, 1, lf ? 2 : 0, nullptr, q_next);
-    vit_sums();
+    dense(A(E->F1), p + "mlp.fc2.weight", D_VIT, D_MLP, X, 1, E->f(p + "mlp.fc2.bias"), 0, X, 1, lf ? 2 : 0, nullptr, q_next);
     {
       char nm[16];
       snprintf(nm, sizeof nm, "blk%d", l);
@@ -1393,16 +1359,11 @@ int dptx_create(dptx_handle* out, const dptx_config* cfg) {
     // (dptx_set_layer_precision(h, "scratch.output_conv.0.weight", 2): the weights keep their lo plane, the input is rounded
     // once) is +3.9 % (1636 -> 1700 img/s) for rms 1.07e-4 -> 1.19e-4; the worst of the 14.2 M outputs of a B = 32 batch moves
     // from 6.3e-4 to 7.6e-4 -- inside north_star's 1e-3, but with 1.3x instead of 1.6x margin (profiles/r04_experiments.md).
-    // DPTX_HEAD0_MFMAS = 1 / 2 / 3 sets the layer for A/B runs of one binary.
-    const char* t2 = getenv("DPTX_HEAD0_MFMAS");
-    if (t2 && atoi(t2) >= 1 && atoi(t2) <= 3) e->layer_prec["scratch.output_conv.0.weight"] = atoi(t2);
   }
   {
-    // fused schedules (include/dptx.h DPTX_FLAG_*; the environment variables are for A/B runs of one binary)
-    const char* t = getenv("DPTX_LN_FOLD");
-    e->ln_fold = !(cfg->flags & DPTX_FLAG_NO_LN_FOLD) && !(t && t[0] == '0') && !mode_is_x3(e->mode_of(DPTX_GROUP_VIT));
-    t = getenv("DPTX_STREAM16");
-    e->stream16 = e->ln_fold && !(cfg->flags & DPTX_FLAG_FP32_STREAM) && !(t && t[0] == '0') &&
+    // fused schedules (include/dptx.h DPTX_FLAG_*)
+    e->ln_fold = !(cfg->flags & DPTX_FLAG_NO_LN_FOLD) && !mode_is_x3(e->mode_of(DPTX_GROUP_VIT));
+    e->stream16 = e->ln_fold && !(cfg->flags & DPTX_FLAG_FP32_STREAM) &&
                   (cfg->dtype == DPTX_DTYPE_BF16 || cfg->dtype == DPTX_DTYPE_FP16 || cfg->dtype == DPTX_DTYPE_FP8);
   }
   {
@@ -1644,19 +1605,13 @@ static int run_forward(dptx_handle h, const void* x, int io, void* y, void* y2, 
   // half-batch qkv, proj and fc2 GEMMs then take the ping-pong kernel) -- with the lockstep-epilogue kernel of the first half
   // of round 3 0.7 was the optimum (+1.2 %) and 0.5 lost; with the persistent, register-direct form 0.5 wins on boxes that
   // are not power-bound (+1.3 ... 2.9 % together with the 1.5 x per-tile advantage in launch_dt) and is neutral on those
-  // that are.  Scaled narrow-tile thresholds lose.  DPTX_CU_SHARE / DPTX_CU_SHARE_SMALL override (1 = tile every launch for
-  // the whole chip, as rounds 1-2 did)
-  static float share_env = -1.f, share_small_env = -1.f;
-  if (share_env < 0.f) { const char* t = getenv("DPTX_CU_SHARE"); share_env = t ? (float)atof(t) : 0.f; }
-  if (share_small_env < 0.f) { const char* t = getenv("DPTX_CU_SHARE_SMALL"); share_small_env = t ? (float)atof(t) : 0.f; }
+  // that are.  Scaled narrow-tile thresholds lose.
   // whatever path leaves this function (HIPCHK returns included), the thread's tile-selection state is back at "whole chip"
   struct ShareReset { ~ShareReset() { gemm_set_cu_share(1.0f); } } share_reset;
   if (!split) {
-    // DPTX_CU_SHARE_WHOLE (A/B runs): tile selection of a whole-batch run that shares the GPU with another handle's forward
-    // (omnidata_amd/pipeline.py) -- measured neutral, profiles/r05_experiments.md
-    static float whole_env = -1.f;
-    if (whole_env < 0.f) { const char* t = getenv("DPTX_CU_SHARE_WHOLE"); whole_env = t ? (float)atof(t) : 0.f; }
-    gemm_set_cu_share(whole_env > 0.f ? whole_env : 1.0f);
+    // (a whole-batch run that shares the GPU with another handle's forward -- omnidata_amd/pipeline.py -- is tiled for the
+    // whole chip too: scaling it was measured neutral, profiles/r05_experiments.md)
+    gemm_set_cu_share(1.0f);
     Run run{h, batch, stream, h->cfg.dtype, height, width, io};
     const int rc = run.forward(x, y, y2);
     h->launches = run.launches;
@@ -1667,7 +1622,7 @@ static int run_forward(dptx_handle h, const void* x, int io, void* y, void* y2, 
     return rc;
   }
   const int nr = batch < h->n_streams ? batch : h->n_streams;  // sub-batches: the first (batch % nr) get one image more
-  gemm_set_cu_share(share_env > 0.f ? share_env : 1.0f / (float)nr, share_small_env > 0.f ? share_small_env : 1.0f);
+  gemm_set_cu_share(1.0f / (float)nr);
   {
     const int rs = ensure_sub_streams(h);
     if (rs != DPTX_OK) return rs;
@@ -1999,7 +1954,7 @@ int dptx_op_gemm(int32_t dtype, const void* A, const void* W, const float* bias,
   return launch_gemm(dtype, p, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
 }
 
-// dense GEMM with the LayerNorm fold's CONSUMER epilogue (tools/gpu/r4_micro.py, tests): C = act((A W^T - mu colsum) rstd + bias),
+// dense GEMM with the LayerNorm fold's CONSUMER epilogue (tests/test_gpu_coresidency.py): C = act((A W^T - mu colsum) rstd + bias),
 // (mu, rstd) of row m from the (sum, sum of squares) records ln_stats[m][0 .. ln_nblk) (row stride 8 records)
 int dptx_op_gemm_ln(int32_t dtype, const void* A, const void* W, const float* bias, void* C, int32_t M, int32_t N, int32_t K,
                     int32_t act, const float* ln_stats, const float* ln_colsum, int32_t ln_nblk, float ln_eps, void* stream) {
@@ -2170,7 +2125,7 @@ int dptx_debug_arena_layout(dptx_handle h, char* dst, size_t capacity) {
 // One 64-bit word sum (order-independent) per arena buffer, sub-batch region and plane of the layout the LAST forward used, on
 // `stream` (i.e. behind that forward): out_dev[(plane * regions + region) * nbuf + buf], buffers in dptx_debug_arena_layout
 // order.  Returns the number of sums (or the capacity needed when out_dev is null).  Comparing the vectors of two forwards of
-// the same input names the first tensor that differs (tools/gpu/r4_hunt.py).
+// the same input names the first tensor that differs (round 4's hunt, profiles/history.md section 10).
 int dptx_debug_arena_checksums(dptx_handle h, void* out_dev, int32_t capacity, void* stream) {
   if (!h) return DPTX_E_INVALID;
   const auto bufs = arena_buf_list(h);
@@ -2199,17 +2154,6 @@ int dptx_debug_arena_checksums(dptx_handle h, void* out_dev, int32_t capacity, v
         HIPCHK(h, launch_checksum(base, end - off, (unsigned long long*)out_dev + ((size_t)pl * regions + r) * nbuf + order[k].second, st));
       }
   return total;
-}
-
-// debug: word sums of {lnst, Hn, QKV, AO, F1} after every launch of the ViT blocks of the following single-stream forwards go to
-// dev_buf[launch * 5 + buffer] (uint64; launch 0 = after the cls rows, then qkv / attention / proj / fc1 / fc2 per block);
-// NULL switches it off.  The first entry that differs between two forwards of one input names the launch whose output differs.
-int dptx_debug_set_launch_sums(dptx_handle h, void* dev_buf, int32_t capacity) {
-  if (!h) return DPTX_E_INVALID;
-  h->d_lsums = (unsigned long long*)dev_buf;
-  h->lsum_cap = dev_buf ? capacity : 0;
-  h->lsum_n = 0;
-  return DPTX_OK;
 }
 
 int dptx_debug_set_trace(void* dev_buf) {

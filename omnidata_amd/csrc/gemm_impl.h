@@ -64,8 +64,9 @@ __device__ __forceinline__ float2 ln_mu_rstd(float sm, float sq, float inv_dim, 
 // v_pk_fma_f32 ... op_sel:[0,1,0]: both lanes of the packed op take rstd from the HIGH dword of the (mu, rstd) register pair
 // the table entry was loaded into.  On MI355X that form returned `bias` -- a product of zero -- in the LOW lane for work-items
 // 48..63 of a wave, a few times per thousand launches, whenever the stem convolution of ANOTHER stream shared the CU
-// (tools/gpu/r4_micro.py reproduces it in seconds: 224-445 of 2400 launches with the packed form, 0 of 2400 with this one;
-// operands recorded in the kernel were right).  It was round 3's "nondeterminism" of the multi-stream forward.
+// (round 4's reproducer, now tests/test_gpu_coresidency.py: 224-445 of 2400 launches with the packed form, 0 of 2400 with
+// this one; operands recorded in the kernel were right).  It was round 3's "nondeterminism" of the multi-stream
+// forward.
 // The empty asm keeps the SLP vectoriser from pairing the elements; tests/test_build_quality.py checks the compiled ISA for
 // packed fp32 operations whose low lane reads a high dword.
 __device__ __forceinline__ float ln_fold_fma(float acc, float mu, float rstd, float colsum, float bias) {
@@ -156,7 +157,6 @@ __device__ __forceinline__ void mma_tile(const char* sa, const char* sb, int a_l
   } else {
     // hi/lo planes, 3 MFMAs per product.  The fragment reads run one k-step ahead of the MFMAs (two fragment sets): the
     // 2 (TM + TN) ds_read_b128 of k-step ks+1 are in flight under the 3 TM TN MFMAs of k-step ks
-    // (DPTX_X3_NOPIPE: read, then multiply, per k-step -- the round-1 form, for A/B runs)
     // XT == 2 (GemmParams::a_hi_only): the activations contribute their hi plane only -- a_hi w_lo + a_hi w_hi, two MFMAs;
     // the A lo tile is neither loaded nor read
     u32x4_t af[2][TM], bf[2][TN], al[2][TM], bl[2][TN];
@@ -192,10 +192,6 @@ __device__ __forceinline__ void mma_tile(const char* sa, const char* sb, int a_l
         }
       }
     };
-#ifdef DPTX_X3_NOPIPE
-#pragma unroll
-    for (int ks = 0; ks < BK / 16; ++ks) { read(0, ks); mma(0); }
-#else
     read(0, 0);
 #pragma unroll
     for (int ks = 0; ks < BK / 16; ++ks) {
@@ -204,7 +200,6 @@ __device__ __forceinline__ void mma_tile(const char* sa, const char* sb, int a_l
       mma(ks & 1);
       __builtin_amdgcn_sched_barrier(0);
     }
-#endif
   }
 }
 
@@ -223,16 +218,12 @@ __device__ __forceinline__ void mma_tile(const char* sa, const char* sb, int a_l
 // statistics are bit-identical run to run and at every batch size (needs rows-per-image % 32 == 0; the engine falls
 // back to the gn_stats kernel otherwise).
 //
-// ILV (gemm_ph_kernel, 256x256, 2 x 4 waves): a wave's 4 x 2 MFMA blocks are interleaved over the tile -- row block i of
-// wave row wm sits at tile row (i>>1)*128 + wm*64 + (i&1)*32, column block j of wave column wn at j*128 + wn*32 -- so that
-// the four 128-row half-tiles of a k-tile are needed one phase after the other.
-//
 // WP (wave-private staging; gemm_pp_kernel): every wave transposes its own 32 x 64 block of a slab through its own 9 KB of
 // LDS and writes its own 32 rows x 128 bytes -- no block barrier inside the epilogue, so one wave's LDS round trip runs
 // under another's arithmetic and stores instead of all eight waves marching through write / barrier / read / compute /
 // store in step (a plain bias epilogue took 17.6 k cycles per tile that way for ~4 k cycles of LDS time and ~2.5 k of
 // VALU time: profiles/r03_experiments.md).  Not with row_stats (a record sums 128 columns: two waves).
-template <int DT, int BM, int BN, int TM, int TN, int PL = 1, int NT = 256, int SLABS = 1, bool ILV = false, bool WP = false>
+template <int DT, int BM, int BN, int TM, int TN, int PL = 1, int NT = 256, int SLABS = 1, bool WP = false>
 __device__ __forceinline__ void epilogue(const GemmParams& p, char* smem, int m0, int n0, int wm, int wn, int lr, int lh,
                                          int tid, f32x16_t (&acc)[TM][TN], int row_pitch = 0, bool dma_in_flight = false,
                                          int trace_row = -1, const char* lds_ln = nullptr) {
@@ -244,8 +235,7 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, char* smem, int m0
   // row_pitch != 0 (gemm_halo_kernel): the tile is 8 image rows x 32 pixels -- tile row R is GEMM row
   // m0 + (R >> 5) * row_pitch + (R & 31)
   static_assert(SLABS == 1 || SLABS == TM, "one slab, or one per MFMA row tile");
-  static_assert(!ILV || (SLABS == TM && TM == 4 && TN == 2 && BM == 256 && BN == 256), "interleaved mapping: the phased kernel");
-  static_assert(!WP || (SLABS == TM && TN == 2 && !ILV), "wave-private staging: one 32 x 64 block per wave and slab");
+  static_assert(!WP || (SLABS == TM && TN == 2), "wave-private staging: one 32 x 64 block per wave and slab");
   constexpr int CT_PITCH = WP ? 72 : BN + 4;  // floats (WP: 4 rows apart = 32 banks apart)
   constexpr int CT_ROWS = WP ? 32 : BM / SLABS;
   constexpr int NCH = WP ? 8 : BN / 8;       // 8-column chunks per staged row
@@ -277,7 +267,7 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, char* smem, int m0
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       // first GEMM row of this wave's i-th 32-row block
-      const int mb = m0 + (ILV ? (i >> 1) * 128 + wm * 64 + (i & 1) * 32 : (wm * TM + i) * 32);
+      const int mb = m0 + (wm * TM + i) * 32;
       const int img = mb / gn_hw;
       const int blk = (mb - img * gn_hw) >> 5;
 #pragma unroll
@@ -289,7 +279,7 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, char* smem, int m0
         sq += __shfl_xor(sq, 32, 64);
         for (int o = 1; o < cpg; o <<= 1) { sm += __shfl_xor(sm, o, 64); sq += __shfl_xor(sq, o, 64); }
         if (lh == 0 && (lr & (cpg - 1)) == 0 && mb < p.M) {
-          const int g = (n0 + (ILV ? j * 128 + wn * 32 : (wn * TN + j) * 32) + lr) >> cpg_sh;
+          const int g = (n0 + (wn * TN + j) * 32 + lr) >> cpg_sh;
           float2* dst = (float2*)p.gn_part + ((long long)img * p.gn_blocks + blk) * 32 + g;
           *dst = make_float2(sm, sq);
         }
@@ -378,7 +368,6 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, char* smem, int m0
         const int row = rr + (gi * GR + it) * RPP;
         int R = WP           ? wm * (TM * 32) + s * 32 + row
                 : SLABS == 1 ? row
-                : ILV        ? (s >> 1) * 128 + (row >> 5) * 64 + (s & 1) * 32 + (row & 31)
                              : (row >> 5) * (TM * 32) + s * 32 + (row & 31);
         if (LNF) ln_R[it] = R;  // tile row: index into the LDS table of (mu, rstd)
         if (row_pitch) R = (R >> 5) * row_pitch + (R & 31);
@@ -443,7 +432,7 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, char* smem, int m0
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int ml = (WP ? 0 : SLABS == 1 ? wm * (TM * 32) + i * 32 : wm * 32) + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const int nl = (WP ? j * 32 : ILV ? j * 128 + wn * 32 : wn * (TN * 32) + j * 32) + lr;
+            const int nl = (WP ? j * 32 : wn * (TN * 32) + j * 32) + lr;
             ct[ml * CT_PITCH + nl] = acc[i][j][r];
           }
       }
@@ -474,7 +463,9 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, char* smem, int m0
             // compiler fuses "x * rstd + bias" at one call site and not at another (1-ulp differences, which the
             // batch-invariance test caught)
             const float2 ms = lnrow[ln_R[it]];  // (mu, rstd) of this row: one LDS broadcast read per 32 threads
-#ifdef DPTX_LN_PACKED_FMA   /* round 3's form, for tools/gpu/r4_micro.py: hipcc turns this into v_pk_fma_f32 ... op_sel:[0,1,0] */
+            // round 3's form, built only by the positive control of tests/test_gpu_coresidency.py: hipcc turns it into
+            // v_pk_fma_f32 ... op_sel:[0,1,0]
+#ifdef DPTX_LN_PACKED_FMA
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = fmaf(fmaf(-ms.x, ln_c[e], v[e]), ms.y, bias_c[e]);
 #else
@@ -1241,17 +1232,12 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
 #else
       const int trow = -1;
 #endif
-#ifdef DPTX_NO_WP   // A/B builds: block-wide staging everywhere
-      constexpr bool wp_ok = false;
-#else
-      constexpr bool wp_ok = true;
-#endif
       if constexpr (DIRECT) {
-        (void)trow; (void)wp_ok;
+        (void)trow;
         epilogue_direct<DT, DIRECT - 1>(p, smem + 4 * HALF, em0, en0, ewm, ewn, elr, elh, etid, acc, more,
                             p.ln_stats != nullptr ? smem + LN_LDS : nullptr);
-      } else if (wp_ok && p.row_stats == nullptr)
-        epilogue<DT, BM, BN, TM, TN, PLE, NT, SLABS, false, true>(p, smem + 4 * HALF, em0, en0, ewm, ewn, elr, elh, etid, acc, 0, more, trow,
+      } else if (p.row_stats == nullptr)
+        epilogue<DT, BM, BN, TM, TN, PLE, NT, SLABS, true>(p, smem + 4 * HALF, em0, en0, ewm, ewn, elr, elh, etid, acc, 0, more, trow,
                                                                   p.ln_stats != nullptr ? smem + LN_LDS : nullptr);
       else  // the producer side of the LayerNorm fold reduces 128 columns of a row: block-wide staging
         epilogue<DT, BM, BN, TM, TN, PLE, NT, SLABS>(p, smem + 4 * HALF, em0, en0, ewm, ewn, elr, elh, etid, acc, 0, more, trow);
@@ -1287,8 +1273,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const GemmParams p) {
 //     slot 2:  group 0 multiplies tile t                         |  group 1 issues A rows 0..63 hi / lo of tile t+1 (4 pieces)
 // with the same who-reads-what-first argument.  Stage image: [A0 hi | A0 lo | A1 hi | A1 lo | W hi | W lo] (64 + 64 + 64 + 64 +
 // 128 + 128 rows).  One block per tile (no persistent loop), the epilogue is gemm_glds_kernel's.  XT == 2 (a_hi_only): the A lo
-// pieces are not issued (10 + 2 per wave) and not read.  DPTX_PP2=0: the lockstep kernel (A/B runs; bit-identical results --
-// the MFMAs of an accumulator run in the same order).  Same box, single-stream per-launch events: output_conv.0 2.15 -> 1.92 ms,
+// pieces are not issued (10 + 2 per wave) and not read.  Against the lockstep kernel (bit-identical results -- the MFMAs of
+// an accumulator run in the same order), same box, single-stream per-launch events: output_conv.0 2.15 -> 1.92 ms,
 // layer2_rn 0.538 -> 0.480, the ResNetV2 3x3 / 1x1 convolutions -8 ... -13 %; 0.63 ms of the 21.8 ms launch sum, parity mode
 // 1646 -> 1667 img/s in the two-stream schedule.
 template <int DT, bool RELU_A, int XT = 3>
@@ -1589,32 +1575,12 @@ constexpr size_t gemm_smem_bytes() {
 template <typename K>
 static void set_smem_attr(K k, size_t smem) { ensure_dyn_smem((const void*)k, smem); }
 
-// A/B experiments: DPTX_GEMM=reg forces the register-staged kernel; DPTX_XCD=0 disables the 2-D XCD
-// partition of the tile grid.
-static int gemm_variant() {
-  static int v = -1;
-  if (v < 0) {
-    const char* s = getenv("DPTX_GEMM");
-    v = (s && s[0] == 'r') ? 1 : 0;
-  }
-  return v;
-}
-static int xcd_partition_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* s = getenv("DPTX_XCD");
-    v = (s && s[0] == '0') ? 0 : 1;
-  }
-  return v;
-}
-
 // Chooses the XCD grid (xm x xn, xm*xn = 8) for a tile grid: XCD (xi, xj) owns the m-tiles of slice xi
 // and the n-tiles of slice xj, so per XCD only A/xm and W/xn are touched.  Objective: HBM/MALL-side
 // traffic xn*A_bytes + xm*W_bytes, subject to the XCD's W slice fitting comfortably in its 4 MB L2
 // (otherwise W is re-fetched for every m-tile) and xn dividing the n-tile count.
 static void choose_xcd_grid(const GemmParams& p, int tiles_m, int tiles_n, int& xm, int& xn) {
   xm = 8; xn = 1;
-  if (!xcd_partition_enabled()) return;
   const double a_bytes = (double)p.M * p.K * 2.0, w_bytes = (double)p.N * p.K * 2.0;
   double best = -1.0;
   const int cand[4] = {1, 2, 4, 8};
@@ -1640,15 +1606,12 @@ static hipError_t launch_cfg(const GemmParams& p, hipStream_t stream) {
                        p.M < (1 << 23);
   if (PL == 2 && !glds_ok) return hipErrorInvalidValue;  // the 3-pass mode exists only on the direct-to-LDS path
   if constexpr (DT != DT_FP8 && PL == 1 && BM == 256 && BN == 256) {
-    constexpr bool pp = true;
-    if (pp && glds_ok) {  // ping-pong schedule of the two wave groups (gemm_pp_kernel)
+    if (glds_ok) {  // ping-pong schedule of the two wave groups (gemm_pp_kernel)
       // persistent launch: at most 32 blocks per XCD (one per CU), each looping over its XCD slice's tiles; the epilogue's
-      // LDS tile sits behind stage 0 (which receives the next tile's first k-tile meanwhile).  DPTX_PERSIST=0: one block per
-      // tile (A/B runs; same kernel, same results); DPTX_PERSIST=n: n blocks per XCD
-      static int per_xcd = -1;
-      if (per_xcd < 0) { const char* e = getenv("DPTX_PERSIST"); per_xcd = e ? atoi(e) : 32; }
-      const int ltot = tiles / 8;
-      const int grid = per_xcd > 0 && ltot > per_xcd && !(p.debug_flags & 2) ? 8 * per_xcd : tiles;
+      // LDS tile sits behind stage 0 (which receives the next tile's first k-tile meanwhile).  debug flag 2: one block per tile
+      // (same kernel, same results)
+      constexpr int per_xcd = 32;
+      const int grid = tiles / 8 > per_xcd && !(p.debug_flags & 2) ? 8 * per_xcd : tiles;
       // (wave-private staging: 8 waves x 32 rows x 72 floats; block-wide staging of the row_stats launches: 64 x 260 floats)
       constexpr size_t smem_pp = (size_t)256 * 256 + (size_t)8 * 32 * 72 * 4 + (size_t)BM * 8 + (size_t)BM * 64;  // + the statistics records
       static_assert((size_t)8 * 32 * 72 * 4 >= (size_t)64 * (BN + 4) * 4, "the block-wide slab fits too");
@@ -1658,16 +1621,13 @@ static hipError_t launch_cfg(const GemmParams& p, hipStream_t stream) {
         hipLaunchKernelGGL(k, dim3(grid), dim3(512), smem_pp, stream, q);
       };
       // plain epilogue (bias, LayerNorm fold, activation, one 16-bit plane): the transposed-accumulator form that stores
-      // straight from the registers.  DPTX_DIRECT=0: the staged epilogue everywhere (A/B runs; results agree bit for bit)
-      static int direct_on = -1;
-      if (direct_on < 0) { const char* e = getenv("DPTX_DIRECT"); direct_on = e ? atoi(e) : 2; }
-      const bool direct_any = direct_on && !(p.debug_flags & 1) && PLE == 1 && !p.bias_per_img && p.c_rpi == 0x7fffffff &&
+      // straight from the registers.  debug flag 1: the staged epilogue everywhere (results agree bit for bit)
+      const bool direct_any = !(p.debug_flags & 1) && PLE == 1 && !p.bias_per_img && p.c_rpi == 0x7fffffff &&
                               p.C8 == nullptr && p.gn_part == nullptr && p.out_scale == 0.f;
       const bool direct = direct_any && p.R1 == nullptr && p.R2 == nullptr && p.row_stats == nullptr && !p.c_fp32 && p.C16 == nullptr;
       // round 6: residuals and the producer side of the LayerNorm fold in the direct form (epilogue_direct RES 1, 2): proj / fc2
       // on the 16-bit token stream, the second convolution of a RCU with and without the fusion path.
-      // DPTX_DIRECT=1: round 5's set only
-      const bool direct_res = direct_any && direct_on >= 2 && p.R1 != nullptr && !p.a_relu && p.ln_stats == nullptr;
+      const bool direct_res = direct_any && p.R1 != nullptr && !p.a_relu && p.ln_stats == nullptr;
       const int res = !direct_res ? 0
                       : (!p.r1_fp32 && !p.c_fp32 && p.C16 == nullptr && p.R2 == nullptr) ? 1
                       : (!p.r1_fp32 && !p.c_fp32 && p.C16 == nullptr && p.R2 != nullptr && !p.r2_fp32 && !p.r2_bcast && p.row_stats == nullptr) ? 2
@@ -1687,12 +1647,10 @@ static hipError_t launch_cfg(const GemmParams& p, hipStream_t stream) {
     }
   }
   if constexpr (DT != DT_FP8 && PL == 2 && PLE == 2 && BM == 128 && BN == 128 && WM_ == 2 && WN_ == 4) {
-    // the two-plane 128x128 tile: ping-pong schedule of the two wave groups (gemm_pp2_kernel).  DPTX_PP2=0: lockstep loop
-    static int pp2 = -1;
-    if (pp2 < 0) { const char* e = getenv("DPTX_PP2"); pp2 = e ? atoi(e) : 1; }
+    // the two-plane 128x128 tile: ping-pong schedule of the two wave groups (gemm_pp2_kernel).  debug flag 4: lockstep loop
     // (not with the pre-activation on the A fragments: its VALU work sits inside the MFMA slot, and the two RCU convolutions
     // that have it were 8-9 % SLOWER than with the lockstep loop: profiles/r04_experiments.md)
-    if (pp2 && !(p.debug_flags & 4) && p.K >= 2 * BK && !p.a_relu) {
+    if (!(p.debug_flags & 4) && p.K >= 2 * BK && !p.a_relu) {
       auto k = gemm_pp2_kernel<DT, false, XT>;
       set_smem_attr(k, smem);
       hipLaunchKernelGGL(k, dim3(tiles), dim3(512), smem, stream, q);
@@ -1706,7 +1664,7 @@ static hipError_t launch_cfg(const GemmParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(k, dim3(tiles), dim3(64 * WM_ * WN_), smem, stream, q);
     return hipGetLastError();
   } else
-  if (glds_ok && (PL == 2 || gemm_variant() != 1)) {
+  if (glds_ok) {
     if (p.a_relu) {
       auto k = gemm_glds_kernel<DT, BM, BN, WM_, WN_, true, PL, PLE, XT>;
       set_smem_attr(k, smem);
@@ -1744,17 +1702,9 @@ static hipError_t launch_dt(const GemmParams& p, hipStream_t stream) {
   const long long m128 = (p.M + 127) / 128, m256 = (p.M + 255) / 256;
   // cu_share: the part of the chip this launch can count on -- 1/n when the forward runs as n sub-batches on n streams (the
   // other streams' launches occupy the rest), so that a half-batch GEMM is tiled for half the CUs instead of being judged
-  // too small for the wide tiles: CU slots and tile-count thresholds scale with it
+  // too small for the wide tiles: CU slots and the 256x256 threshold scale with it (scaled narrow-tile thresholds lose)
   const double sh = p.cu_share > 0.f ? (double)p.cu_share : 1.0;
-  const double shs = p.cu_share_small > 0.f ? (double)p.cu_share_small : sh;  // for the narrow-tile thresholds
   const long long cu1 = (long long)(256 * sh + 0.5), cu2 = (long long)(512 * sh + 0.5);  // slots at 1 / 2 blocks per CU
-  static int forced = -1;  // DPTX_TILE=128 disables the 256x256 tile; 12864 / 6464 force a tile shape (tools/gemm_bench.py)
-  if (forced < 0) { const char* t = getenv("DPTX_TILE"); forced = t ? atoi(t) : 0; }
-  {
-    if (forced == 128128 && p.N % 128 == 0) return launch_cfg<DT, PL, 128, 128, 2, 2, PLE, XT>(p, stream);
-    if (forced == 12864 && p.N % 64 == 0) return launch_cfg<DT, PL, 128, 64, 2, 2, PLE, XT>(p, stream);
-    if (forced == 6464 && p.N % 64 == 0) return launch_cfg<DT, PL, 64, 64, 2, 2, PLE, XT>(p, stream);
-  }
   // 256x256 (8 waves, 1 block/CU; 16-bit modes: the ping-pong kernel): half the DMA issues and 3/4 of the LDS reads per MFMA
   // of the 128x128 tile, but no second block to hide prologue/epilogue and a coarser tail.  Chosen when its estimated
   // efficiency wins: fill of the last round of CUs (256 slots) x 1.5 (the per-tile advantage at K >= 512: 1.25 with round 2's
@@ -1762,29 +1712,27 @@ static hipError_t launch_dt(const GemmParams& p, hipStream_t stream) {
   // against the fill of the 128x128 grid (512 slots).  That picks
   // it for the ViT GEMMs, patch-embed and the 3x3 convs at 1/4 resolution and keeps 128x128 for the small maps.
   if constexpr (PL == 1) {
-    const bool glds_ok = !p.a_fp32 && p.a_bytes > 0 && p.a_bytes < (1ll << 31) && p.M < (1 << 23) && gemm_variant() != 1;
-    if (forced != 128 && glds_ok && p.N % 256 == 0 && p.K >= 512) {
+    const bool glds_ok = !p.a_fp32 && p.a_bytes > 0 && p.a_bytes < (1ll << 31) && p.M < (1 << 23);
+    if (glds_ok && p.N % 256 == 0 && p.K >= 512) {
       const long long t256 = m256 * (p.N / 256), r256 = (t256 + cu1 - 1) / cu1;
       const long long t128 = m128 * (p.N / 128), r128 = (t128 + cu2 - 1) / cu2;
       const double fill256 = (double)t256 / (double)(r256 * cu1), fill128 = (double)t128 / (double)(r128 * cu2);
-      static double adv = -1.0;  // DPTX_PP_ADV: the per-tile advantage assumed for the 256x256 kernel (A/B runs)
-      if (adv < 0.0) { const char* e = getenv("DPTX_PP_ADV"); adv = e ? atof(e) : 1.5; }
-      if (t256 >= 200 * sh && fill256 * adv >= fill128) return launch_cfg<DT, PL, 256, 256, 2, 4, PLE, XT>(p, stream);
+      if (t256 >= 200 * sh && fill256 * 1.5 >= fill128) return launch_cfg<DT, PL, 256, 256, 2, 4, PLE, XT>(p, stream);
     }
   }
   if constexpr (PL == 2) {
     // 3-MFMA modes are one block per CU (two planes of two stages = 128 KB of LDS); eight waves (2 x 4, wave tile
     // 64 x 32) instead of four put two waves on every SIMD, so that one's fragment reads overlap the other's MFMAs:
     // GEMM family 32.7 -> 30.5 ms per fp16x3 forward (profiles/r02_experiments.md)
-    if (p.N % 128 == 0 && m128 * (p.N / 128) >= 200 * shs) return launch_cfg<DT, PL, 128, 128, 2, 4, PLE, XT>(p, stream);
+    if (p.N % 128 == 0 && m128 * (p.N / 128) >= 200) return launch_cfg<DT, PL, 128, 128, 2, 4, PLE, XT>(p, stream);
   }
   // (row_stats -- the producer side of the LayerNorm fold -- reduces 128-column blocks inside a tile: never narrower tiles)
   // 128x128 from 256 tiles up (one block on every CU): at 288 tiles (M = 18432, N = 256) it still beats 576 tiles of
   // 128x64 by 2..10 %, whose second round is nearly empty
-  if (p.N % 128 == 0 && (m128 * (p.N / 128) >= 256 * shs || p.row_stats != nullptr)) return launch_cfg<DT, PL, 128, 128, 2, 2, PLE, XT>(p, stream);
+  if (p.N % 128 == 0 && (m128 * (p.N / 128) >= 256 || p.row_stats != nullptr)) return launch_cfg<DT, PL, 128, 128, 2, 2, PLE, XT>(p, stream);
   if (p.N == 32) return launch_cfg<DT, PL, 256, 32, 4, 1, PLE, XT>(p, stream);
-  if (PL == 1 && p.N % 64 == 0 && p.N < 128 && m256 * (p.N / 64) >= 448 * shs) return launch_cfg<DT, PL, 256, 64, 4, 1, PLE, XT>(p, stream);
-  if (p.N % 64 == 0 && m128 * (p.N / 64) >= 448 * shs) return launch_cfg<DT, PL, 128, 64, 2, 2, PLE, XT>(p, stream);
+  if (PL == 1 && p.N % 64 == 0 && p.N < 128 && m256 * (p.N / 64) >= 448) return launch_cfg<DT, PL, 256, 64, 4, 1, PLE, XT>(p, stream);
+  if (p.N % 64 == 0 && m128 * (p.N / 64) >= 448) return launch_cfg<DT, PL, 128, 64, 2, 2, PLE, XT>(p, stream);
   if (p.N % 64 == 0) return launch_cfg<DT, PL, 64, 64, 2, 2, PLE, XT>(p, stream);
   return hipErrorInvalidValue;
 }

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(HT_THREADS) void head_tail_kernel(const uint16_t* _
 // two phases one after the other in all waves (one 161 KB block with channel halves, then two 78.5 KB blocks per CU): 1.53 -
 // 1.67 ms per launch at B = 32 -- the phases of co-resident blocks did not overlap by themselves.  This form: 1.43 ms;
 // with the MFMA phase removed 0.95 ms, with the window build removed 0.94 ms, without the weight DMA 1.38 ms
-// (tools/gpu/r4_headx3_bench.py, DPTX_HX_DBG).  Both halves sit at twice their own floor: the multipliers read one 1 KB
+// (profiles/r04_headx3_bench.txt, profiles/r04_experiments.md section 2).  Both halves sit at twice their own floor: the multipliers read one 1 KB
 // fragment from LDS per MFMA (w_hi, w_lo, and hi / lo of two rows for six MFMAs), which is the LDS port's rate, and the
 // builders' ds_write_b128 share that port -- a deeper register blocking (four rows per wave) needs a 16-row window that does
 // not fit two stages.  The weights are re-streamed per tile (147 KB per 8 x 32 pixels, ~21 MB per CU and forward out of L2).
@@ -274,8 +274,7 @@ __global__ __launch_bounds__(HX_THREADS) void head_tail_x3_kernel(const uint16_t
                                                                   const float* __restrict__ b2, const float* __restrict__ w4,
                                                                   const float* __restrict__ b4, void* __restrict__ y, int io, int B,
                                                                   int Hs, int Ws, int C, int relu_out, int ntiles, long long plane,
-                                                                  long long wplane, int dbg) {
-  // dbg (DPTX_HX_DBG, timing ablations only -- results are wrong): 1 no MFMA phase, 2 no window build, 4 no weight DMA
+                                                                  long long wplane) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -306,15 +305,13 @@ __global__ __launch_bounds__(HX_THREADS) void head_tail_x3_kernel(const uint16_t
     for (int g = 0; g < G; ++g) {
       const int quarter = g & 3;
       char* Wl = smem + (g & 1) * HX_STAGE;
-      if (!(dbg & 4)) {
 #pragma unroll 6
-        for (int q = 0; q < 36; ++q) {
-          const int pl = q / 18, r = 16 * (q % 18) + (lane >> 2);
-          const int tap = r >> 5, n = r & 31;
-          const int sch = (lane & 3) ^ ((n >> 2) & 3);
-          const unsigned off = (unsigned)(((long long)pl * wplane + n * 1152 + tap * 128 + quarter * 32 + sch * 8) * 2);
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcW, (__attribute__((address_space(3))) void*)(Wl + q * 1024), 16, off, 0, 0, 0);
-        }
+      for (int q = 0; q < 36; ++q) {
+        const int pl = q / 18, r = 16 * (q % 18) + (lane >> 2);
+        const int tap = r >> 5, n = r & 31;
+        const int sch = (lane & 3) ^ ((n >> 2) & 3);
+        const unsigned off = (unsigned)(((long long)pl * wplane + n * 1152 + tap * 128 + quarter * 32 + sch * 8) * 2);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcW, (__attribute__((address_space(3))) void*)(Wl + q * 1024), 16, off, 0, 0, 0);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       asm volatile("s_barrier" ::: "memory");   // B_g
@@ -335,7 +332,7 @@ __global__ __launch_bounds__(HX_THREADS) void head_tail_x3_kernel(const uint16_t
       char* P = smem + (g & 1) * HX_STAGE + 2 * HX_WPL;
       const int b = t / tpi, rem = t - b * tpi, ty = rem / tiles_x, tx = rem - ty * tiles_x;
       const int oy0 = ty * 8, ox0 = tx * 32;
-      if (item < 2 * 136 && !(dbg & 2)) {
+      if (item < 2 * 136) {
         const int ox = ox0 - 1 + wx;
         const bool vx = ox >= 0 && ox < Wo;
         const float sx = rx * (float)(vx ? ox : 0);
@@ -434,21 +431,19 @@ __global__ __launch_bounds__(HX_THREADS) void head_tail_x3_kernel(const uint16_t
         q[i][1] = *(const u32x4_t*)(pr + HX_PPL);
       }
     };
-    if (!(dbg & 1)) {
-      read_ks(0, 0, wf[0], pf[0]);
+    read_ks(0, 0, wf[0], pf[0]);
 #pragma unroll
-      for (int ks = 0; ks < 18; ++ks) {
-        if (ks + 1 < 18) read_ks((ks + 1) >> 1, (ks + 1) & 1, wf[(ks + 1) & 1], pf[(ks + 1) & 1]);
-        __builtin_amdgcn_sched_barrier(0);
-        // (the two rows alternate: consecutive MFMAs never share an accumulator)
-        acc[0] = T16<DT>::mfma32(wf[ks & 1][0], pf[ks & 1][0][1], acc[0]);   // w_hi * a_lo
-        acc[1] = T16<DT>::mfma32(wf[ks & 1][0], pf[ks & 1][1][1], acc[1]);
-        acc[0] = T16<DT>::mfma32(wf[ks & 1][1], pf[ks & 1][0][0], acc[0]);   // w_lo * a_hi
-        acc[1] = T16<DT>::mfma32(wf[ks & 1][1], pf[ks & 1][1][0], acc[1]);
-        acc[0] = T16<DT>::mfma32(wf[ks & 1][0], pf[ks & 1][0][0], acc[0]);   // w_hi * a_hi
-        acc[1] = T16<DT>::mfma32(wf[ks & 1][0], pf[ks & 1][1][0], acc[1]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+    for (int ks = 0; ks < 18; ++ks) {
+      if (ks + 1 < 18) read_ks((ks + 1) >> 1, (ks + 1) & 1, wf[(ks + 1) & 1], pf[(ks + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);
+      // (the two rows alternate: consecutive MFMAs never share an accumulator)
+      acc[0] = T16<DT>::mfma32(wf[ks & 1][0], pf[ks & 1][0][1], acc[0]);   // w_hi * a_lo
+      acc[1] = T16<DT>::mfma32(wf[ks & 1][0], pf[ks & 1][1][1], acc[1]);
+      acc[0] = T16<DT>::mfma32(wf[ks & 1][1], pf[ks & 1][0][0], acc[0]);   // w_lo * a_hi
+      acc[1] = T16<DT>::mfma32(wf[ks & 1][1], pf[ks & 1][1][0], acc[1]);
+      acc[0] = T16<DT>::mfma32(wf[ks & 1][0], pf[ks & 1][0][0], acc[0]);   // w_hi * a_hi
+      acc[1] = T16<DT>::mfma32(wf[ks & 1][0], pf[ks & 1][1][0], acc[1]);
+      __builtin_amdgcn_sched_barrier(0);
     }
     if (quarter == 3) {
       const int b = t / tpi, rem = t - b * tpi, ty = rem / tiles_x, tx = rem - ty * tiles_x;
@@ -506,10 +501,8 @@ hipError_t launch_head_tail(int mode, const void* H0, const void* W2, const floa
     auto k = head_tail_x3_kernel<DT_FP16>;
     ensure_dyn_smem((const void*)k, HX_SMEM);
     const int grid2 = grid;   // one block per CU
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("DPTX_HX_DBG"); dbg = e ? atoi(e) : 0; }
     hipLaunchKernelGGL(k, dim3(grid2), dim3(HX_THREADS), HX_SMEM, stream, (const uint16_t*)H0, (const uint16_t*)W2, b2, w4, b4, y, io, B,
-                       Hs, Ws, C, relu_out, ntiles, pl.act, pl.w, dbg);
+                       Hs, Ws, C, relu_out, ntiles, pl.act, pl.w);
     return hipGetLastError();
   }
   if (mode == MODE_BF16) {

@@ -64,7 +64,7 @@ def test_no_scratch_no_spills(src, tmp_path):
 def test_no_packed_fp32_op_reads_a_high_dword_in_its_low_lane(src, tmp_path):
     """Round 4 root cause of the 'nondeterministic' multi-stream forward: v_pk_fma_f32 ... op_sel:[0,1,0] (hipcc's packed form
     of the LayerNorm-fold epilogue: both lanes take rstd from the HIGH dword of a register pair) returned a product of zero in
-    the low lane for work-items 48..63 whenever the stem convolution of another stream shared the CU (tools/gpu/r4_micro.py:
+    the low lane for work-items 48..63 whenever the stem convolution of another stream shared the CU (round 4's reproducer:
     224-445 of 2400 launches; the scalar form: 0).  No kernel of the library may contain a packed fp32 operation with an
     op_sel swizzle on the low lane (op_sel_hi -- the HIGH lane reading a low dword, what a splat compiles to -- is what
     the GELU polynomial uses and never showed the effect)."""

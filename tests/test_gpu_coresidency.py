@@ -4,7 +4,7 @@ Round 3's multi-stream "nondeterminism" was one instruction form: hipcc's packed
 (`v_pk_fma_f32 ... op_sel:[0,1,0]`) returned a zero product in its low lane, a few times per thousand launches, whenever the
 STEM CONVOLUTION of another stream shared the CU.  The fix (scalar fmas, gemm_impl.h ln_fold_fma) is pinned statically by
 tests/test_build_quality.py (ISA scan for that form); THIS file is the dynamic half -- the op-level victim x aggressor loop
-of tools/gpu/r4_micro.py as a test, against every kernel form that can serve a LayerNorm-fold consumer (qkv / fc1):
+of round 4's reproducer as a test, against every kernel form that can serve a LayerNorm-fold consumer (qkv / fc1):
 
     staged        gemm_glds_kernel, 128x128 tile, block-wide LDS epilogue            (small M)
     wave-private  gemm_pp_kernel, 256x256 tile, per-wave LDS epilogue                (large M, debug flag 1: no direct form)

@@ -1,5 +1,5 @@
 """Per-shape micro-benchmark of the implicit-GEMM kernel on the DPT-Hybrid layer shapes (B=32).
-Usage (GPU box): python tools/gemm_bench.py [--dtype bf16] ; DPTX_GEMM=reg selects the register-staged variant."""
+Usage (GPU box): python tools/gemm_bench.py [--dtype bf16]"""
 import argparse
 import os
 import sys
@@ -62,7 +62,6 @@ def main():
     fp8 = args.dtype == "fp8"
     dt, tdt = DTYPES[args.dtype], (torch.bfloat16 if args.dtype in ("bf16", "fp8") else torch.float16)
     st = torch.cuda.current_stream().cuda_stream
-    print(f"variant={os.environ.get('DPTX_GEMM', 'glds')} dtype={args.dtype}")
     tot_ms, tot_flop = 0.0, 0.0
     # the ViT GEMMs run with the epilogue the engine gives them: fc1 bias + GELU; proj / fc2 bias + in-place fp32 residual
     EPI = {"vit.fc1": (2, False), "vit.proj": (0, True), "vit.fc2": (0, True)}
