@@ -75,6 +75,9 @@ ABI = [
     ("dptx_postprocess_normal_u8", C.c_int, [_vp, _vp, _vp]),
     ("dptx_postprocess_depth", C.c_int, [_vp, _vp, _vp]),
     ("dptx_resample_coeffs", C.c_int, [_i32, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i32, C.POINTER(C.c_int32)]),
+    ("dptx_refocus_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64p]),
+    ("dptx_refocus_quantiles", C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_refocus", C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
     ("dptx_op_set_planes", C.c_int, [C.c_int64, C.c_int64]),
     ("dptx_op_gemm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_op_conv", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp] + [_i32] * 13 + [_vp]),

@@ -12,7 +12,8 @@ import torch.nn.functional as F
 from PIL import Image
 
 
-def resize_shorter(img: Image.Image, size: int) -> Image.Image:
+def resize_shorter(img: Image.Image, size: int, resample=Image.BILINEAR) -> Image.Image:
+    """torchvision Resize(size, resample) of a PIL image: the shorter side becomes `size`."""
     w, h = img.size
     if (w <= h and w == size) or (h <= w and h == size):
         return img
@@ -20,7 +21,7 @@ def resize_shorter(img: Image.Image, size: int) -> Image.Image:
         ow, oh = size, int(size * h / w)
     else:
         oh, ow = size, int(size * w / h)
-    return img.resize((ow, oh), Image.BILINEAR)
+    return img.resize((ow, oh), resample)
 
 
 def center_crop(img: Image.Image, size: int) -> Image.Image:
