@@ -328,6 +328,51 @@ int dptx_refocus(const float* rgb, const float* depth, int32_t B, int32_t C, int
                  const float* qvals, const float* focus /*[B]*/, const float* aperture /*[B]*/,
                  float* out, int64_t* segments /*nullable*/, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- MiDaS depth loss (omnidata_tools/torch/losses/midas_loss.py; no handle; DEVICE pointers) ----
+ * Stream-ordered on `stream`, on the caller's workspace only: no allocation, no host synchronisation, no host read of any
+ * count or median (graph-capturable).  No float atomics: results are bitwise reproducible and every per-image statistic
+ * is the same alone and inside any batch.  pred, target [B][H][W] fp32 and mask [B][H][W] uint8 (0 / 1) contiguous;
+ * shapes B >= 1, 1 <= H, W <= 8192, H*W <= 2^24, 1 <= scales <= 8.  Anything else -> DPTX_E_INVALID.
+ * terms, an OR of:
+ *   DPTX_MIDAS_SSI      the scale-and-shift-invariant MAE of SSIMAE (:104-111, :33-56): lower nanmedian t, s = sum |x - t| /
+ *                       (n + 1), (x - t) / (s + 1e-6), masked L1 over the batch;
+ *   DPTX_MIDAS_GRAD     the gradient-matching term of GradientMatchingTerm (:83-101, :114-134) over `scales` levels;
+ *   DPTX_MIDAS_ALIGN    the gradient term sees scale * x + shift, least squares on the mask (compute_scale_and_shift, :10-30);
+ *   DPTX_MIDAS_INVERSE  the gradient term and the alignment see 1 / (x + 1e-6) of prediction and target (:147-148).
+ * MidasLoss = all four (DPTX_MIDAS_ALL).  Numerics: fp32 per-pixel values rounded step by step as the reference's fp32
+ * tensors, fp64 sums and 2x2 solve; det == 0 exactly (e.g. a constant prediction on the mask) gives scale = shift = 0.
+ * Host-only (no GPU needed): the workspace of all three calls, with A(x) = x rounded up to a multiple of 256 and
+ * nblk = min(ceil(H*W / 4096), 1024):
+ *   *bytes = A(256 + 8256 B) + A(80 B) + A(256 B) + A(128 B) + A(128 B nblk). */
+#define DPTX_MIDAS_SSI 1
+#define DPTX_MIDAS_GRAD 2
+#define DPTX_MIDAS_ALIGN 4
+#define DPTX_MIDAS_INVERSE 8
+#define DPTX_MIDAS_ALL 15
+#define DPTX_MIDAS_RECORD_DOUBLES 32 /* per image */
+#define DPTX_MIDAS_STATS 8           /* floats per image of dptx_midas_stats */
+int dptx_midas_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t scales, int64_t* bytes);
+/* losses [3] fp32 = (total, ssi, reg): total = ssi + alpha * reg with both terms, else the one term (0 for the absent one).
+ * reduction: image_based != 0 -> mean over images of L_k,b / M_k,b (MidasLoss's default), 0 -> sum L / sum M (batch-based).
+ * record (nullable): [B][DPTX_MIDAS_RECORD_DOUBLES] per-image coefficients of the gradient, owned by the caller until the
+ * matching dptx_midas_loss_backward; computed only when given.  alpha > 0 (the reference raises otherwise). */
+int dptx_midas_loss(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W, int32_t terms,
+                    int32_t scales, int32_t image_based, float alpha, float* losses, double* record /*nullable*/, void* ws,
+                    int64_t ws_bytes, void* stream);
+/* grad_pred [B][H][W] = d(g0 total + g1 ssi + g2 reg) / d pred for grad_losses = (g0, g1, g2) [3] fp32 on the device, from the
+ * record of the forward on the same inputs and arguments.  d|x| / dx = sign(x) with sign(0) = 0; the median passes its
+ * gradient to the lowest linear index of a valid pixel holding the median value (-0.0 = +0.0); nothing flows through scale /
+ * shift where det == 0.  No workspace. */
+int dptx_midas_loss_backward(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W,
+                             int32_t terms, int32_t scales, int32_t image_based, float alpha, const double* record,
+                             const float* grad_losses, float* grad_pred, void* stream);
+/* Per-image statistics, stats [B][DPTX_MIDAS_STATS] fp32: t_p, t_g, s_p, s_g, n, scale, shift, argmedian of pred (-1: none).
+ * terms: DPTX_MIDAS_SSI (medians and s; 0 otherwise) and / or DPTX_MIDAS_ALIGN (+ DPTX_MIDAS_INVERSE) (scale and shift; 0
+ * otherwise).  pred_aligned / target_aligned (nullable, SSI): (x - t) / (s + 1e-6) at every pixel (masked_shift_and_scale). */
+int dptx_midas_stats(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W, int32_t terms,
+                     float* stats, float* pred_aligned /*nullable*/, float* target_aligned /*nullable*/, void* ws,
+                     int64_t ws_bytes, void* stream);
+
 /* ---- op-level entry points (unit tests + micro-benchmarks of the individual kernels) ----
  * dtype: DPTX_DTYPE_*.  All pointers are device pointers; row-major / NHWC. */
 

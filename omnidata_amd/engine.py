@@ -78,6 +78,10 @@ ABI = [
     ("dptx_refocus_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64p]),
     ("dptx_refocus_quantiles", C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
     ("dptx_refocus", C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_midas_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i32, _i64p]),
+    ("dptx_midas_loss", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_midas_loss_backward", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp]),
+    ("dptx_midas_stats", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
     ("dptx_op_set_planes", C.c_int, [C.c_int64, C.c_int64]),
     ("dptx_op_gemm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_op_conv", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp] + [_i32] * 13 + [_vp]),
