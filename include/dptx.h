@@ -373,6 +373,60 @@ int dptx_midas_stats(const float* pred, const float* target, const uint8_t* mask
                      float* stats, float* pred_aligned /*nullable*/, float* target_aligned /*nullable*/, void* ws,
                      int64_t ws_bytes, void* stream);
 
+/* ---- virtual normal loss (omnidata_tools/torch/losses/virtual_normal_loss.py, VNL_Loss; no handle; DEVICE pointers) ----
+ * The third term of the reference's depth objective (train_depth.py:268-279).  Stream-ordered on `stream`, on the caller's
+ * buffers only: no allocation, no host synchronisation, no host read of K or of the cut value.  Integer atomics only and
+ * every floating-point sum in fp64 in a fixed order: results are bitwise reproducible, and the per-triple outputs of an
+ * image are the same alone and inside any batch.
+ * first, second [B][H][W] fp32 contiguous: the two arguments of VNL_Loss.forward in its order (the reference names them
+ * gt_depth, pred_depth, and train_depth.py passes the prediction FIRST).  p1, p2, p3 [n] int32: linear pixel indices
+ * y * W + x of the three points of every triple, shared by all images.  A triple with an index outside [0, H*W) reads
+ * nothing and is dropped (not kept, no gradient): a non-zero return would need a synchronisation.
+ * Per triple, in fp32 with every step rounded on its own as the reference's fp32 tensors:
+ *   points   (x, y, z) = ((u - W/2) |d| / fx, (v - H/2) |d| / fy, d) (:44-50, integer W/2, H/2);
+ *   kept     by the FIRST argument only (:95-128 with the constants of the call, :136-140): all three z > delta_z, and not
+ *            (for each of x, y, z some pairwise difference is below 0.005 in magnitude), and not more than 3 of the 9 entries
+ *            of <d_i, d_j> / (|d_i| |d_j| + 1e-8) over d = (P2-P1, P3-P1, P3-P2) beyond +-0.867;
+ *   :144     on the SECOND argument: where point j (0, 1, 2) has z == 0, COORDINATE row j (x, y, z) of all three points
+ *            becomes 0.0001 (the reference's index lands on that axis), and no gradient flows into those entries;
+ *   normals  cross(P2-P1, P3-P1) / norm, a norm of exactly 0 replaced by 0.01; loss = sum_c |n_first,c - n_second,c|.
+ * K = the number of kept triples of the batch.  select != 0: the int(K * 0.25) smallest losses are dropped and the rest
+ * averaged; among kept triples whose loss EQUALS the cut value, the earliest in (image, triple) order are dropped first
+ * (the order of a stable sort; the reference's torch.sort leaves it unspecified).  select == 0: the mean of all K.
+ * K == 0 gives NaN and an all-zero gradient.  The masks, the 0.01 / 0.0001 replacements and the cut are piecewise constant:
+ * no gradient through them; d|x| / dx = sign(x) with sign(0) = 0.
+ * Shapes: B >= 1, 1 <= H, W <= 8192, H*W <= 2^24, 1 <= n <= 2^29, B*n < 2^31.  Anything else -> DPTX_E_INVALID.
+ * Host-only (no GPU needed): the workspace of dptx_vnl_prepare (any B >= 1) and dptx_vnl_loss, with A(x) = x rounded up
+ * to a multiple of 256, nblk = min(ceil(B n / 1024), 1024) and snb = min(ceil(3 n / 1024), 512):
+ *   *bytes = 2 A(12 n) + A(1024 snb) + 4352 + A(40) + A(4 nblk) + A(8 nblk) + A(4 B n) + A(B n). */
+#define DPTX_VNL_RECORD_HEADER 64 /* bytes */
+int dptx_vnl_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t n, int64_t* bytes);
+/* The inverse index of one draw of triples, for the backward: inverse, uint32 [H*W + 6 n], owned by the caller and kept
+ * with the indices: [H*W] 1 + the slot of the pixel's first entry (0: no triple uses it), then [3 n] pixels and [3 n]
+ * entries 3 i + position, sorted by pixel and, within a pixel, ascending (a stable radix sort of the 3 n indices). */
+int dptx_vnl_prepare(const int32_t* p1, const int32_t* p2, const int32_t* p3, int32_t n, int32_t H, int32_t W, uint32_t* inverse,
+                     void* ws, int64_t ws_bytes, void* stream);
+/* loss_out [1] fp32.  record (nullable; needed by the backward): [DPTX_VNL_RECORD_HEADER + B n] bytes owned by the caller
+ * until the matching dptx_vnl_loss_backward: uint32 K, uint32 number dropped, uint32 bits of the cut value, uint32 number
+ * dropped among the triples at the cut value, fp64 sum of the averaged losses, fp64 their number, fp32 loss; from byte
+ * DPTX_VNL_RECORD_HEADER on, uint8 [B][n]: 1 where the triple is kept and not dropped. */
+int dptx_vnl_loss(const float* first, const float* second, int32_t B, int32_t H, int32_t W, float fx, float fy, float delta_z,
+                  const int32_t* p1, const int32_t* p2, const int32_t* p3, int32_t n, int32_t select, float* loss_out,
+                  uint8_t* record /*nullable*/, void* ws, int64_t ws_bytes, void* stream);
+/* grad_first / grad_second [B][H][W] fp32 (either may be null, not both) = grad_out[0] * d loss / d argument, from the record
+ * of the forward on the same inputs and the inverse index of the same triples.  One thread per (image, pixel) adds the
+ * closed-form gradients of the pixel's entries in the inverse index's order, in fp64 (the exact-zero-norm and z == 0
+ * decisions are the forward's fp32 ones); pixels that no kept triple uses get 0.  No workspace. */
+int dptx_vnl_loss_backward(const float* first, const float* second, int32_t B, int32_t H, int32_t W, float fx, float fy,
+                           const int32_t* p1, const int32_t* p2, const int32_t* p3, int32_t n, const uint8_t* record,
+                           const uint32_t* inverse, const float* grad_out, float* grad_first /*nullable*/,
+                           float* grad_second /*nullable*/, void* stream);
+/* Per-triple outputs for tests and debugging: keep uint8 [B][n], loss fp32 [B][n] (0 where not kept), normals (nullable)
+ * fp32 [B][n][2][3]: the unit normals of the first and of the second argument.  No workspace. */
+int dptx_vnl_triples(const float* first, const float* second, int32_t B, int32_t H, int32_t W, float fx, float fy, float delta_z,
+                     const int32_t* p1, const int32_t* p2, const int32_t* p3, int32_t n, uint8_t* keep, float* loss,
+                     float* normals /*nullable*/, void* stream);
+
 /* ---- op-level entry points (unit tests + micro-benchmarks of the individual kernels) ----
  * dtype: DPTX_DTYPE_*.  All pointers are device pointers; row-major / NHWC. */
 

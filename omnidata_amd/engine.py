@@ -82,6 +82,14 @@ ABI = [
     ("dptx_midas_loss", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, C.c_int64, _vp]),
     ("dptx_midas_loss_backward", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp]),
     ("dptx_midas_stats", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_vnl_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i32, _i64p]),
+    ("dptx_vnl_prepare", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_vnl_loss", C.c_int, [_vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp, _i32, _i32, _vp, _vp,
+                                _vp, C.c_int64, _vp]),
+    ("dptx_vnl_loss_backward", C.c_int, [_vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
+                                         _vp, _vp]),
+    ("dptx_vnl_triples", C.c_int, [_vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                   _vp]),
     ("dptx_op_set_planes", C.c_int, [C.c_int64, C.c_int64]),
     ("dptx_op_gemm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_op_conv", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp] + [_i32] * 13 + [_vp]),

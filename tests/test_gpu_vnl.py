@@ -1,0 +1,406 @@
+"""Virtual normal loss on the GPU (omnidata_amd/virtual_normal_loss.py, csrc/vnl_loss.hip) against the restatement
+(tests/vnl_restatement.py) and the reference's goldens (tools/make_vnl_golden.py).  pytest -m gpu."""
+import glob
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import vnl_restatement as rs
+from omnidata_amd import virtual_normal_loss as vl
+from omnidata_amd.midas_loss import MidasLoss
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "vnl_*.npz")))
+IDS = [os.path.basename(p)[4:-4] for p in GOLDEN]
+P_KEYS = ("p1_x", "p1_y", "p2_x", "p2_y", "p3_x", "p3_y")
+
+
+def ulps(a, b):
+    """fp32 ulp distance elementwise (-0 = +0; NaN = NaN)"""
+    def ordered(x):
+        i = np.ascontiguousarray(torch.as_tensor(x).float().cpu().numpy()).view(np.int32).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+    a32, b32 = torch.as_tensor(a).float().cpu(), torch.as_tensor(b).float().cpu()
+    d = np.abs(ordered(a32) - ordered(b32))
+    both_nan = (torch.isnan(a32) & torch.isnan(b32)).numpy()
+    return np.where(both_nan, 0, d)
+
+
+def smooth(gen, B, H, W, lo, hi, k=5):
+    g = torch.rand(B, 1, k, k, generator=gen)
+    f = torch.nn.functional.interpolate(g, size=(H, W), mode="bilinear", align_corners=True)
+    f = (f - f.amin((2, 3), keepdim=True)) / (f.amax((2, 3), keepdim=True) - f.amin((2, 3), keepdim=True)).clamp_min(1e-12)
+    return (lo + (hi - lo) * f).float().contiguous()
+
+
+def depths(B, H, W, seed, lo=0.05, hi=1.0):
+    """two depth maps [B,1,H,W] fp32 (CPU): a smooth one, and it plus another smooth field and noise"""
+    gen = torch.Generator().manual_seed(seed)
+    t = smooth(gen, B, H, W, lo, hi)
+    p = (0.8 * t + 0.2 * smooth(gen, B, H, W, lo, hi) + 0.01 * (hi - lo) * torch.randn(B, 1, H, W, generator=gen)).clamp(lo / 2, hi * 1.5)
+    return t, p.float().contiguous()
+
+
+def draw(H, W, seed, ratio=0.15):
+    np.random.seed(seed)
+    return vl.VNL_Loss(1.0, 1.0, (H, W), sample_ratio=ratio).select_index()
+
+
+def golden(path):
+    z = np.load(path)
+    g = {k: z[k] for k in z.files}
+    H, W = g["first"].shape[-2:]
+    return dict(g=g, first=torch.from_numpy(g["first"]), second=torch.from_numpy(g["second"]), p123={k: g[k] for k in P_KEYS},
+                fx=float(g["fx"]), fy=float(g["fy"]), dz=float(g["delta_z"]), select=bool(g["select"]),
+                mod=vl.VNL_Loss(float(g["fx"]), float(g["fy"]), (H, W), delta_z=float(g["delta_z"])))
+
+
+def restate(first, second, p123, fx=1.0, fy=1.0, dz=0.0001, select=True, keep=None):
+    p = rs.linear_indices(p123, first.shape[-1])
+    return p, rs.forward(first[:, 0], second[:, 0], p, fx, fy, dz, select, keep_on_borderline=keep)
+
+
+def check_triples(mod, first, second, p123, fx=1.0, fy=1.0, dz=0.0001, golden_mask=None):
+    """keep flags equal the restatement's (and the golden's) except on borderline triples (at most 0.1 %); normals and
+    losses of kept triples within 2 ulps.  Returns (triples, restatement that adopts the kernel's borderline decisions)."""
+    got = mod.triples(first.cuda(), second.cuda(), p123)
+    keep = got["keep"].cpu()
+    p, ref = restate(first, second, p123, fx, fy, dz)
+    border = ref["borderline"]
+    nb, nflip = int(border.sum()), int((keep != ref["keep"]).sum())
+    print(f"borderline triples: {nb} of {border.numel()}, {nflip} decided the other way")
+    assert nb <= 0.001 * border.numel()
+    assert torch.equal(keep[~border], ref["keep"][~border])
+    if golden_mask is not None:
+        assert torch.equal(keep[~border], golden_mask[~border])
+    both = keep & ref["keep"]
+    for k in ("normal_first", "normal_second"):
+        d = ulps(got[k].cpu()[both], ref[k][both])
+        print(f"{k}: max {d.max() if d.size else 0} ulps over {int(both.sum())} kept triples")
+        assert d.size == 0 or d.max() <= 2
+    d = ulps(got["loss"].cpu()[both], ref["loss"][both])
+    assert d.size == 0 or d.max() <= 2
+    assert not got["loss"].cpu()[~keep].any()
+    return got, keep
+
+
+def run(mod, first, second, p123, select=True, wrt=(True, True), scale=1.0):
+    """the public forward + backward on the GPU -> loss (0-d CPU), grad_first, grad_second ([B,H,W] CPU or None)"""
+    a = first.cuda().requires_grad_(wrt[0])
+    b = second.cuda().requires_grad_(wrt[1])
+    loss = mod(a, b, select=select, p123=p123)
+    assert loss.dim() == 0
+    if wrt[0] or wrt[1]:
+        (scale * loss).backward()
+    return loss.detach().cpu(), (a.grad[:, 0].cpu() if wrt[0] else None), (b.grad[:, 0].cpu() if wrt[1] else None)
+
+
+def check_gradients(first, second, p, ref, got, bounds, what="", cap=True):
+    """elementwise against fp64 autograd of the restatement on its fixed masks; kink pixels exempt (cap: at most 1 % of the
+    pixels with a gradient)"""
+    g64 = rs.fp64_gradients(first[:, 0], second[:, 0], p, ref["fx"], ref["fy"], ref)
+    kink = rs.kink_pixels(p, ref, first[:, 0].shape)
+    for name, g, want, bound in (("first", got[0], g64[0], bounds[0]), ("second", got[1], g64[1], bounds[1])):
+        if g is None:
+            continue
+        nz = want != 0
+        assert not cap or int((kink & nz).sum()) <= 0.01 * max(int(nz.sum()), 1)
+        gmax = want.abs().max().item()
+        e = (g.double() - want)[~kink].abs().max().item() / gmax if gmax > 0 else (g.double() - want).abs().max().item()
+        print(f"{what} grad_{name}: max|d| / max|g| {e:.3e} (bound {bound:.3e}), max|g| {gmax:.3e}, {int((kink & nz).sum())} kink pixels")
+        assert e <= bound
+
+
+@pytest.mark.parametrize("path", GOLDEN, ids=IDS)
+def test_triples_vs_restatement_and_golden(path):
+    c = golden(path)
+    check_triples(c["mod"], c["first"], c["second"], c["p123"], c["fx"], c["fy"], c["dz"], torch.from_numpy(c["g"]["mask"]))
+
+
+@pytest.mark.parametrize("path", GOLDEN, ids=IDS)
+def test_loss_vs_golden_and_restatement(path):
+    c = golden(path)
+    g = c["g"]
+    d = c["mod"].diagnostics(c["first"].cuda(), c["second"].cuda(), c["p123"], select=c["select"])
+    keep = c["mod"].triples(c["first"].cuda(), c["second"].cuda(), c["p123"])["keep"].cpu()
+    p, ref = restate(c["first"], c["second"], c["p123"], c["fx"], c["fy"], c["dz"], c["select"], keep)
+    nb = int(ref["borderline"].sum())
+    loss = d["loss"].cpu()
+    print(f"K {d['K']} (golden {int(g['K'])}), borderline {nb}, loss {loss.item():.9g} golden {float(g['loss']):.9g} "
+          f"restatement {ref['value'].item():.9g}")
+    assert nb == 0, "every committed golden is free of borderline triples"
+    assert d["K"] == int(g["K"]) == ref["K"] and d["dropped"] == ref["rank"]
+    want = float(g["loss"])
+    assert (np.isnan(want) and torch.isnan(loss)) or abs(loss.item() - want) <= 1e-5 * abs(want)
+    assert ulps(loss, ref["value"]).max() <= 2
+    assert torch.equal(d["active"].cpu(), ref["active"])
+    if ref["K"] > 0 and c["select"]:
+        assert d["cut"] == ref["cut"]
+
+
+@pytest.mark.parametrize("wrt", [(True, False), (False, True), (True, True)], ids=["first", "second", "both"])
+@pytest.mark.parametrize("path", GOLDEN, ids=IDS)
+def test_gradients_vs_fp64_autograd(path, wrt):
+    """The bound per case and argument is 2 * e_ref, e_ref being the error of the reference's own fp32 autograd against the
+    same fp64 gradient (recorded in the golden), floored at 1e-6."""
+    c = golden(path)
+    g = c["g"]
+    loss, g1, g2 = run(c["mod"], c["first"], c["second"], c["p123"], c["select"], wrt)
+    p, ref = restate(c["first"], c["second"], c["p123"], c["fx"], c["fy"], c["dz"], c["select"])
+    ref["fx"], ref["fy"] = c["fx"], c["fy"]
+    bounds = [max(2 * float(g[f"e_ref_{k}"]), 1e-6) for k in ("first", "second")]
+    print(f"e_ref {float(g['e_ref_first']):.3e} {float(g['e_ref_second']):.3e}")
+    check_gradients(c["first"], c["second"], p, ref, (g1, g2), bounds, os.path.basename(path))
+    if ref["K"] == 0:
+        assert torch.isnan(loss)
+        for gg in (g1, g2):
+            assert gg is None or not gg.any()
+
+
+def synthetic(B, H, W, seed, n=None):
+    first, second = depths(B, H, W, seed)
+    p123 = draw(H, W, seed)
+    if n is not None:
+        p123 = {k: v[:n] for k, v in p123.items()}
+    return first, second, p123
+
+
+def full_check(first, second, p123, select=True, what="", cap=True, focal=1.0):
+    """triples, loss, K, the averaged set and both gradients against the restatement (gradient bound: 1e-6 max|g|, the
+    floor tests/test_gpu_midas.py uses: the backward evaluates in fp64 and rounds once)"""
+    H, W = first.shape[-2:]
+    mod = vl.VNL_Loss(focal, focal, (H, W))
+    _, keep = check_triples(mod, first, second, p123, focal, focal)
+    p, ref = restate(first, second, p123, focal, focal, select=select, keep=keep)
+    ref["fx"] = ref["fy"] = focal
+    loss, g1, g2 = run(mod, first, second, p123, select)
+    d = mod.diagnostics(first.cuda(), second.cuda(), p123, select=select)
+    print(f"{what}: K {d['K']}, dropped {d['dropped']}, loss {loss.item():.9g} (restatement {ref['value'].item():.9g})")
+    assert d["K"] == ref["K"] and d["dropped"] == ref["rank"]
+    assert torch.equal(d["active"].cpu(), ref["active"])
+    assert ulps(loss, ref["value"]).max() <= 2
+    check_gradients(first, second, p, ref, (g1, g2), (1e-6, 1e-6), what, cap)
+    return ref, loss, g1, g2
+
+
+def test_no_triple_survives():
+    first, second, p123 = synthetic(2, 24, 32, 1)
+    ref, loss, g1, g2 = full_check(torch.zeros_like(first), second, p123, what="K = 0")
+    assert ref["K"] == 0 and torch.isnan(loss) and not g1.any() and not g2.any()
+
+
+@pytest.mark.parametrize("K", [1, 2, 3])
+def test_fewer_than_four_kept_triples(K):
+    first, second, p123 = synthetic(1, 32, 40, 2)
+    _, ref = restate(first, second, p123)
+    kept = ref["keep"][0].nonzero()[:K, 0].numpy()
+    assert kept.size == K
+    few = {k: v[kept] for k, v in p123.items()}
+    ref, loss, g1, g2 = full_check(first, second, few, what=f"K = {K}")
+    assert ref["K"] == K and ref["rank"] == 0 and g1.any() and g2.any()
+
+
+def test_one_pixel_repeated_and_one_triple():
+    first, second, p123 = synthetic(2, 24, 32, 3)
+    n = p123["p1_x"].size
+    same = {k: np.full(n, 7 if k.endswith("x") else 5, dtype=np.int64) for k in P_KEYS}
+    ref, loss, g1, g2 = full_check(first, second, same, what="one pixel n times")   # P1 = P2 = P3: nothing kept
+    assert ref["K"] == 0 and torch.isnan(loss)
+    # one pixel at position 1 of every triple: its gradient is a sum over all n triples
+    shared = dict(p123)
+    shared["p1_x"], shared["p1_y"] = same["p1_x"], same["p1_y"]
+    ref, loss, g1, g2 = full_check(first, second, shared, what="one pixel in every triple")
+    assert ref["K"] > 10
+    _, ref1 = restate(first, second, p123)
+    i = int(ref1["keep"][0].nonzero()[0, 0])
+    full_check(first[:1], second[:1], {k: v[i:i + 1] for k, v in p123.items()}, what="n = 1")
+
+
+@pytest.mark.parametrize("shape", [(3, 1, 97), (3, 83, 1), (2, 37, 53)])
+def test_thin_and_odd_images(shape):
+    B, H, W = shape
+    first, second, p123 = synthetic(B, H, W, 4)
+    # one row or one column: every point lies in one plane, every normal is the same axis up to sign, so a component of
+    # n_first - n_second is exactly 0 in many triples (in fp64 too): those count as kinks, without the cap
+    cap = H > 1 and W > 1
+    focal = 1.0 if cap else 60.0    # a long focal length keeps the points of one row / column from looking collinear
+    ref, _, _, _ = full_check(first, second, p123, what=f"{H} x {W}", cap=cap, focal=focal)
+    assert ref["K"] > 0
+    full_check(second, first, p123, select=False, what=f"{H} x {W}, no select, swapped", cap=cap, focal=focal)
+
+
+def test_batch_32_at_384():
+    first, second, p123 = synthetic(32, 384, 384, 5)
+    # no cap on the kink pixels here: at 384 px with fx = 1 and depths <= 1 the triangles are wide and flat, both normals
+    # are (small, small, +-1) and their z components agree to the last fp32 bit in about 5 % of the triples; the cap is a
+    # condition on the goldens' inputs (tools/make_vnl_golden.py); this input is the training size
+    ref, loss, g1, g2 = full_check(first, second, p123, what="B = 32, 384 x 384", cap=False)
+    assert ref["K"] > 1000
+
+
+def test_cut_ties_follow_the_stable_sort():
+    """Image 1 is image 0 again (every kept loss tied across the two) and on the left half of image 2 the two arguments are
+    equal (a block of losses exactly 0): the averaged set, the loss and the pixels that receive gradient are those of the
+    stable sort -- the copy in the EARLIER image is dropped first."""
+    for seed in range(6, 60):   # the first draw whose cut falls INSIDE a pair of tied losses (decided on the CPU)
+        first, second, p123 = synthetic(3, 32, 40, seed)
+        first[1], second[1] = first[0], second[0]
+        second[2, :, :, :20] = first[2, :, :, :20]
+        p, ref = restate(first, second, p123)
+        tied = ref["keep"] & (ref["loss"] == ref["cut"])
+        if int(ref["borderline"].sum()) == 0 and 0 < int((tied & ~ref["active"]).sum()) < int(tied.sum()):
+            break
+    else:
+        raise AssertionError("no draw puts the cut inside a group of tied losses")
+    mod = vl.VNL_Loss(1.0, 1.0, (32, 40))
+    ref["fx"] = ref["fy"] = 1.0
+    assert int(tied.sum()) >= 2 and int((ref["keep"] & (ref["loss"] == 0)).sum()) >= 1
+    d = mod.diagnostics(first.cuda(), second.cuda(), p123)
+    assert torch.equal(d["active"].cpu(), ref["active"]) and d["cut"] == ref["cut"]
+    loss, g1, g2 = run(mod, first, second, p123)
+    assert loss.item() == ref["value"].item()
+    g64 = rs.fp64_gradients(first[:, 0], second[:, 0], p, 1.0, 1.0, ref)
+    kink = rs.kink_pixels(p, ref, first[:, 0].shape)
+    for g, want in ((g1, g64[0]), (g2, g64[1])):
+        assert torch.equal((g != 0)[~kink], (want != 0)[~kink])
+    assert not torch.equal(g1[0] != 0, g1[1] != 0)    # the tie was broken between the two identical images
+    check_gradients(first, second, p, ref, (g1, g2), (1e-6, 1e-6), "ties")
+
+
+def test_repeat_bitwise_and_batch_invariance():
+    first, second, p123 = synthetic(7, 64, 80, 7)
+    mod = vl.VNL_Loss(1.0, 1.0, (64, 80))
+    runs = [run(mod, first, second, p123) for _ in range(3)]
+    for r in runs[1:]:
+        assert torch.equal(r[0], runs[0][0]) and torch.equal(r[1], runs[0][1]) and torch.equal(r[2], runs[0][2])
+    full = mod.triples(first.cuda(), second.cuda(), p123)
+    for b in (0, 3, 6):
+        one = mod.triples(first[b:b + 1].cuda(), second[b:b + 1].cuda(), p123)
+        for k, v in one.items():
+            assert torch.equal(v.cpu(), full[k][b:b + 1].cpu()), (b, k)
+
+
+def test_two_losses_summed_before_one_backward():
+    """What the backward needs belongs to the call: a second forward on the same shape (same cached workspace) with other
+    triples does not disturb the first one's backward."""
+    f1, s1, pa = synthetic(2, 40, 48, 8)
+    f2, s2, pb = synthetic(2, 40, 48, 9)
+    mod = vl.VNL_Loss(1.0, 1.0, (40, 48))
+    a = torch.cat([f1, f2], 1).cuda().requires_grad_(True)
+    l1 = mod(a[:, :1], s1.cuda(), p123=pa)
+    l2 = mod(a[:, 1:], s2.cuda(), p123=pb)
+    (l1 + 2.0 * l2).backward()
+    g = a.grad.cpu()
+    for j, (f, s, pp, w) in enumerate(((f1, s1, pa, 1.0), (f2, s2, pb, 2.0))):
+        p, ref = restate(f, s, pp)
+        want = rs.fp64_gradients(f[:, 0], s[:, 0], p, 1.0, 1.0, ref)[0] * w
+        kink = rs.kink_pixels(p, ref, f[:, 0].shape)
+        assert (g[:, j].double() - want)[~kink].abs().max() <= 1e-6 * want.abs().max()
+
+
+def test_fp16_inputs_get_fp16_gradients():
+    first, second, p123 = synthetic(2, 32, 40, 10)
+    mod = vl.VNL_Loss(1.0, 1.0, (32, 40))
+    a = first.half().cuda().requires_grad_(True)
+    b = second.bfloat16().cuda().requires_grad_(True)
+    mod(a, b, p123=p123).backward()
+    assert a.grad.dtype == torch.float16 and b.grad.dtype == torch.bfloat16
+    f, s = a.detach().float().cpu(), b.detach().float().cpu()
+    p, ref = restate(f, s, p123)
+    want = rs.fp64_gradients(f[:, 0], s[:, 0], p, 1.0, 1.0, ref)
+    kink = rs.kink_pixels(p, ref, f[:, 0].shape)
+    assert (a.grad.float().cpu()[:, 0].double() - want[0])[~kink].abs().max() <= 2e-3 * want[0].abs().max()   # one fp16 rounding
+    assert (b.grad.float().cpu()[:, 0].double() - want[1])[~kink].abs().max() <= 1.6e-2 * want[1].abs().max()  # one bf16 rounding
+
+
+def test_input_contract():
+    first, second, p123 = synthetic(2, 16, 16, 11)
+    a, b = first.cuda(), second.cuda()
+    mod = vl.VNL_Loss(1.0, 1.0, (16, 16))
+    assert mod(a, b).dim() == 0 and mod(a, b, False).dim() == 0           # draws its own triples
+    for bad in ((a.cpu(), b.cpu()), (a[:, 0], b[:, 0]), (a, b[:, :, :8]), (a.double(), b.double()), (a[:, :, :8], b[:, :, :8]),
+                (a.expand(2, 3, 16, 16), b.expand(2, 3, 16, 16))):
+        with pytest.raises(ValueError):
+            mod(*bad)
+    with pytest.raises(ValueError):
+        vl.VNL_Loss(1.0, 1.0, (16, 32))(a, b)                              # the reference fails on a broadcast there
+    with pytest.raises(ValueError):
+        mod(a, b, p123={k: v for k, v in p123.items() if k != "p3_y"})
+    with pytest.raises(ValueError):
+        mod(a, b, p123={k: v + 16 for k, v in p123.items()})
+    with pytest.raises(ValueError):
+        mod(a, b, p123={k: v[:0] for k, v in p123.items()})
+
+
+def test_out_of_range_indices_are_dropped_by_the_library():
+    """Below the Python check: dptx_vnl_* given an index outside [0, H*W) reads nothing and drops the triple."""
+    from omnidata_amd.engine import load_library
+    first, second, p123 = synthetic(1, 16, 16, 12)
+    a, b = first[:, 0].cuda().contiguous(), second[:, 0].cuda().contiguous()
+    lin = torch.stack(rs.linear_indices(p123, 16)).int()
+    good = lin.clone().cuda()
+    bad = lin.clone()
+    bad[0, 0], bad[1, 1], bad[2, 2] = -1, 256, 1 << 30
+    bad = bad.cuda()
+    n = lin.shape[1]
+    outs = []
+    for p in (good, bad):
+        keep = torch.empty(1, n, dtype=torch.uint8, device="cuda")
+        loss = torch.empty(1, n, device="cuda")
+        rc = load_library().dptx_vnl_triples(a.data_ptr(), b.data_ptr(), 1, 16, 16, 1.0, 1.0, 1e-4, p[0].data_ptr(), p[1].data_ptr(),
+                                             p[2].data_ptr(), n, keep.data_ptr(), loss.data_ptr(), None,
+                                             torch.cuda.current_stream().cuda_stream)
+        assert rc == 0
+        outs.append((keep.cpu(), loss.cpu()))
+    assert not outs[1][0][0, :3].any() and not outs[1][1][0, :3].any()
+    assert torch.equal(outs[0][0][0, 3:], outs[1][0][0, 3:]) and torch.equal(outs[0][1][0, 3:], outs[1][1][0, 3:])
+
+
+def test_depth_loss_is_the_sum_of_its_parts():
+    first, second, _ = synthetic(3, 32, 32, 13)
+    mask = torch.rand(3, 1, 32, 32, generator=torch.Generator().manual_seed(13)) < 0.8
+    pred = second.cuda().requires_grad_(True)
+    gt, m = first.cuda(), mask.cuda()
+    np.random.seed(13)
+    out = vl.DepthLoss(image_size=32)(pred, gt, m)
+    assert sorted(out) == ["depth_loss", "reg_loss", "ssi_loss", "vn_loss"]
+    out["depth_loss"].backward()
+    g = pred.grad.clone()
+    pred.grad = None
+    np.random.seed(13)
+    vn = vl.VNL_Loss(1.0, 1.0, (32, 32))(pred, gt)
+    _, ssi, reg = MidasLoss(alpha=0.1)(pred, gt, m)
+    total = ssi + 0.1 * reg + 10 * vn
+    total.backward()
+    assert torch.equal(out["vn_loss"], vn) and torch.equal(out["ssi_loss"], ssi) and torch.equal(out["reg_loss"], reg)
+    assert torch.equal(out["depth_loss"], total) and torch.equal(g, pred.grad)
+    assert vn.item() > 0 and torch.isfinite(total)
+
+
+def test_training_smoke():
+    """A small conv net trained 50 Adam steps on DepthLoss (fresh triples every step, as in train_depth.py): the loss falls
+    to at most half its start."""
+    torch.manual_seed(0)
+    np.random.seed(0)
+    gt, _ = depths(4, 32, 32, 14)
+    mask = torch.rand(4, 1, 32, 32, generator=torch.Generator().manual_seed(14)) < 0.8
+    x = torch.cat([gt, torch.rand_like(gt)], 1).cuda()    # the net sees the target depth and noise
+    net = torch.nn.Sequential(torch.nn.Conv2d(2, 16, 3, padding=1), torch.nn.ReLU(), torch.nn.Conv2d(16, 1, 3, padding=1),
+                              torch.nn.Softplus()).cuda()
+    opt = torch.optim.Adam(net.parameters(), lr=1e-2)
+    loss = vl.DepthLoss(image_size=32)
+    gc, mc = gt.cuda(), mask.cuda()
+    first = None
+    for step in range(50):
+        opt.zero_grad()
+        out = loss(net(x), gc, mc)
+        out["depth_loss"].backward()
+        if step == 0:
+            first = out["depth_loss"].item()
+        opt.step()
+    last = out["depth_loss"].item()
+    print(f"DepthLoss: {first:.5f} -> {last:.5f} after 50 steps")
+    assert np.isfinite(last) and last <= 0.5 * first, (first, last)
