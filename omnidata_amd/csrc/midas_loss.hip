@@ -4,9 +4,9 @@
 //
 //  a. count + select (:33-56): pass 0 counts the valid pixels n, the non-NaN valid values of prediction and target and the
 //     mask of every gradient level (M_k), and histograms the first 8-bit digit of the order-preserving keys; passes 1..3
-//     histogram the next digit of the keys under the prefix selected so far.  Every block derives that prefix itself from the
-//     previous pass's histogram (an inclusive LDS scan) and block 0 of the image records it.  The rank is the lower median
-//     floor((k-1)/2) of the k non-NaN valid values (torch.nanmedian).  Integer atomics only: deterministic.
+//     histogram the next digit of the keys under the prefix selected so far: the radix select of select.h, on both arrays
+//     at once.  The rank is the lower median floor((k-1)/2) of the k non-NaN valid values (torch.nanmedian).  Integer
+//     atomics only: deterministic.
 //  b. stats pass: the median keys, the lowest linear index of a valid pixel with the prediction's median key (the pixel the
 //     median's gradient flows to), per-block fp64 partial sums of |x - t| (prediction, target), sign(p - t_p) and the
 //     alignment system of compute_scale_and_shift (:10-30).
@@ -22,22 +22,19 @@
 // reduction runs in a fixed order, so results are bitwise reproducible and per-image statistics do not depend on the batch.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
 
 #include "../../include/dptx.h"
+#include "select.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int BINS = 256;             // 8-bit digits, 4 passes
-constexpr int NPASS = 4;
-constexpr int MAX_SIDE = 8192;
-constexpr int64_t MAX_HW = 1ll << 24;
+using namespace dptx;
+
 constexpr int MAX_SCALES = 8;
-constexpr int MAX_GRID_Y = 65535;
 constexpr int TPB = 256;
 constexpr int64_t PX_PER_BLOCK = 4096;
 constexpr int64_t MAX_BLOCKS = 1024;
@@ -57,8 +54,6 @@ enum : int { P_UP = 0, P_UG, P_SU, P_A00, P_A01, P_B0, P_B1, P_STATS };
 // loss-pass partials
 enum : int { P_SSI = 0, P_E, P_EU, P_S, P_T, P_L = 5 };
 
-int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
 struct Layout {
   int64_t nblk, per_block;
   int64_t o_gcnt, o_cnt, o_hist, o_state, o_rec, o_tot, o_part, zero_bytes, total;
@@ -69,8 +64,7 @@ bool layout(int32_t B, int32_t H, int32_t W, int32_t scales, Layout& lo) {
   if (B < 1 || H < 1 || W < 1 || H > MAX_SIDE || W > MAX_SIDE || (int64_t)H * W > MAX_HW || scales < 1 || scales > MAX_SCALES)
     return false;
   const int64_t HW = (int64_t)H * W;
-  lo.nblk = std::min<int64_t>((HW + PX_PER_BLOCK - 1) / PX_PER_BLOCK, MAX_BLOCKS);
-  lo.per_block = (HW + lo.nblk - 1) / lo.nblk;
+  split(HW, PX_PER_BLOCK, MAX_BLOCKS, lo.nblk, lo.per_block);
   lo.o_gcnt = 0;                                        // uint64 [1 + MAX_SCALES]: sum n, sum_b M_k
   lo.o_cnt = 256;                                       // uint32 [B][CNT]
   lo.o_hist = lo.o_cnt + (int64_t)B * CNT * 4;          // uint32 [B][NPASS][2][BINS]
@@ -104,87 +98,23 @@ struct Shape {
   uint32_t HW, per_block;
 };
 
-// order-preserving keys; -0.0 and +0.0 are one key (that of +0.0)
-__device__ __forceinline__ uint32_t f2key(float f) {
-  uint32_t u = __float_as_uint(f == 0.0f ? 0.0f : f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
 __device__ __forceinline__ int sgn(float v) { return (v > 0.0f) - (v < 0.0f); }
 
 // x or 1 / (x + 1e-6) (:147-148: reciprocal, correctly rounded)
 __device__ __forceinline__ float xform(float v, bool inv) { return inv ? 1.0f / (v + EPS) : v; }
 
-// sums of NS fp64 values over the block (256 threads) in a fixed order -> dst[0 .. NS)
-template <int NS>
-__device__ __forceinline__ void block_sum(double (&v)[NS], double* red /*LDS [4][NS]*/, double* dst) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int s = 0; s < NS; ++s)
-    for (int o = 32; o > 0; o >>= 1) v[s] += __shfl_down(v[s], o, 64);
-  if ((t & 63) == 0)
-#pragma unroll
-    for (int s = 0; s < NS; ++s) red[(t >> 6) * NS + s] = v[s];
-  __syncthreads();
-  if (t < NS) dst[t] = ((red[t] + red[NS + t]) + red[2 * NS + t]) + red[3 * NS + t];
-  __syncthreads();
-}
-
-// The digit of pass q of the rank-th key (among the keys with the prefix selected before q) of both arrays: inclusive scan
-// of the pass's two histograms.  pre / rank: in = state before pass q, out = state after it (prefix << 8 | digit, rank left).
-__device__ void resolve(const uint32_t* __restrict__ h /*[2][BINS]*/, uint32_t (*sc)[BINS], uint32_t* res /*LDS [4]*/,
-                        const bool has[2], uint32_t pre[2], uint32_t rank[2]) {
-  const int t = threadIdx.x;
-  const uint32_t h0 = h[t], h1 = h[BINS + t];
-  sc[0][t] = h0;
-  sc[1][t] = h1;
-  if (t < 2) {
-    res[2 * t] = pre[t] << 8;
-    res[2 * t + 1] = 0;
-  }
-  __syncthreads();
-  for (int off = 1; off < BINS; off <<= 1) {
-    const uint32_t v0 = t >= off ? sc[0][t - off] : 0u, v1 = t >= off ? sc[1][t - off] : 0u;
-    __syncthreads();
-    sc[0][t] += v0;
-    sc[1][t] += v1;
-    __syncthreads();
-  }
-  const uint32_t inc[2] = {sc[0][t], sc[1][t]}, hv[2] = {h0, h1};
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-    const uint32_t ex = inc[a] - hv[a];
-    if (has[a] && ex <= rank[a] && rank[a] < inc[a]) {  // exactly one bin holds the rank
-      res[2 * a] = (pre[a] << 8) | (uint32_t)t;
-      res[2 * a + 1] = rank[a] - ex;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-    pre[a] = res[2 * a];
-    rank[a] = res[2 * a + 1];
-  }
-  __syncthreads();
-}
-
-// the select state before pass q (q >= 1: derived from pass q - 1's histogram; block 0 records it)
-__device__ void select_state(const Ws& w, int b, int q, uint32_t (*sc)[BINS], uint32_t* res, bool has[2], uint32_t pre[2],
-                             uint32_t rank[2]) {
+// the select state of image b before pass q (select.h); the rank is the lower median (torch.nanmedian)
+__device__ __forceinline__ void select_state(const Ws& w, int b, int q, uint32_t (*sc)[BINS], uint32_t* res, bool (&has)[2],
+                                             uint32_t (&pre)[2], uint32_t (&rank)[2]) {
   const uint32_t* cnt = w.cnt + (int64_t)b * CNT;
   const uint32_t k[2] = {cnt[1], cnt[2]};
-  uint32_t* st = w.state + (int64_t)b * (NPASS + 1) * 4;
+  uint32_t rank0[2];
   for (int a = 0; a < 2; ++a) {
     has[a] = k[a] > 0;
-    pre[a] = q == 1 ? 0u : st[(q - 1) * 4 + 2 * a];
-    rank[a] = q == 1 ? (has[a] ? (k[a] - 1) / 2 : 0u) : st[(q - 1) * 4 + 2 * a + 1];  // lower median (torch.nanmedian)
+    rank0[a] = has[a] ? (k[a] - 1) / 2 : 0u;
   }
-  resolve(w.hist + ((int64_t)b * NPASS + (q - 1)) * 2 * BINS, sc, res, has, pre, rank);
-  if (blockIdx.x == 0 && threadIdx.x < 2) {
-    st[q * 4 + 2 * threadIdx.x] = pre[threadIdx.x];
-    st[q * 4 + 2 * threadIdx.x + 1] = rank[threadIdx.x];
-  }
+  dptx::select_state<2>(w.hist + (int64_t)b * NPASS * 2 * BINS, w.state + (int64_t)b * (NPASS + 1) * 4, q, sc, res, has, rank0, pre,
+                        rank);
 }
 
 // ---------------------------------------------------------------- a. count + digit histograms
@@ -335,8 +265,7 @@ __global__ __launch_bounds__(64) void ml_solve_kernel(Ws w, Shape s, int image_b
         for (int q = 0; q < P_STATS; ++q) v[q] += p[q];
       }
 #pragma unroll
-    for (int q = 0; q < P_STATS; ++q)
-      for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_down(v[q], o, 64);
+    for (int q = 0; q < P_STATS; ++q) v[q] = wave_sum(v[q]);
     if (t == 0) {
       const uint32_t* cnt = w.cnt + (int64_t)b * CNT;
       double* r = w.rec + (int64_t)b * REC;
@@ -518,8 +447,7 @@ __global__ __launch_bounds__(64) void ml_reduce_kernel(Ws w, Shape s) {
       for (int q = 0; q < NS; ++q) v[q] += p[q];
     }
 #pragma unroll
-    for (int q = 0; q < NS; ++q)
-      for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_down(v[q], o, 64);
+    for (int q = 0; q < NS; ++q) v[q] = wave_sum(v[q]);
     if (t == 0)
 #pragma unroll
       for (int q = 0; q < NS; ++q) w.tot[(int64_t)b * NPART + q] = v[q];
@@ -653,8 +581,6 @@ __global__ __launch_bounds__(TPB) void ml_align_kernel(const float* __restrict__
   }
 }
 
-bool ok() { return hipGetLastError() == hipSuccess; }
-
 bool shape_of(int32_t B, int32_t H, int32_t W, int32_t terms, int32_t scales, Layout& lo, Shape& s) {
   if (!layout(B, H, W, scales, lo) || (terms & ~ALL_TERMS)) return false;
   s = Shape{B, H, W, scales, terms, (int)lo.nblk, (uint32_t)((int64_t)H * W), (uint32_t)lo.per_block};
@@ -664,7 +590,7 @@ bool shape_of(int32_t B, int32_t H, int32_t W, int32_t terms, int32_t scales, La
 // stages a..c on the workspace
 bool run_stats(const float* pred, const float* targ, const uint8_t* mask, const Shape& s, const Layout& lo, const Ws& w,
                int image_based, float* stats, hipStream_t st) {
-  const int gy = s.B < MAX_GRID_Y ? s.B : MAX_GRID_Y;
+  const int gy = grid_y(s.B);
   if (hipMemsetAsync((char*)w.gcnt, 0, (size_t)lo.zero_bytes, st) != hipSuccess) return false;
   const dim3 grid((unsigned)s.nblk, (unsigned)gy);
   hipLaunchKernelGGL(ml_pass_kernel, grid, dim3(TPB), 0, st, pred, targ, mask, w, s, 0);
@@ -699,13 +625,13 @@ int dptx_midas_loss(const float* pred, const float* target, const uint8_t* mask,
   hipStream_t st = (hipStream_t)stream;
   const Ws w = ws_view(ws, lo);
   if (!run_stats(pred, target, mask, s, lo, w, image_based, nullptr, st)) return DPTX_E_HIP;
-  const int gy = B < MAX_GRID_Y ? B : MAX_GRID_Y;
+  const int gy = grid_y(B);
   const dim3 grid((unsigned)s.nblk, (unsigned)gy);
   if (record) hipLaunchKernelGGL(ml_loss_kernel<true>, grid, dim3(TPB), 0, st, pred, target, mask, w, s);
   else hipLaunchKernelGGL(ml_loss_kernel<false>, grid, dim3(TPB), 0, st, pred, target, mask, w, s);
   hipLaunchKernelGGL(ml_reduce_kernel, dim3((unsigned)gy), dim3(64), 0, st, w, s);
   hipLaunchKernelGGL(ml_finalize_kernel, dim3(1), dim3(TPB), 0, st, w, s, image_based, alpha, record ? 1 : 0, losses, record);
-  return ok() ? DPTX_OK : DPTX_E_HIP;
+  return launch_ok() ? DPTX_OK : DPTX_E_HIP;
 }
 
 int dptx_midas_loss_backward(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W,
@@ -718,10 +644,10 @@ int dptx_midas_loss_backward(const float* pred, const float* target, const uint8
       !(terms & (DPTX_MIDAS_SSI | DPTX_MIDAS_GRAD)) ||
       ((terms & (DPTX_MIDAS_ALIGN | DPTX_MIDAS_INVERSE)) && !(terms & DPTX_MIDAS_GRAD)) || !(alpha > 0.0f))
     return DPTX_E_INVALID;
-  const int gy = B < MAX_GRID_Y ? B : MAX_GRID_Y;
+  const int gy = grid_y(B);
   hipLaunchKernelGGL(ml_backward_kernel, dim3((s.HW + TPB - 1) / TPB, (unsigned)gy), dim3(TPB), 0, (hipStream_t)stream, pred, target,
                      mask, s, alpha, record, grad_losses, grad_pred);
-  return ok() ? DPTX_OK : DPTX_E_HIP;
+  return launch_ok() ? DPTX_OK : DPTX_E_HIP;
 }
 
 int dptx_midas_stats(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W, int32_t terms,
@@ -736,11 +662,11 @@ int dptx_midas_stats(const float* pred, const float* target, const uint8_t* mask
   const Ws w = ws_view(ws, lo);
   if (!run_stats(pred, target, mask, s, lo, w, 1, stats, st)) return DPTX_E_HIP;
   if (pred_aligned || target_aligned) {
-    const int gy = B < MAX_GRID_Y ? B : MAX_GRID_Y;
+    const int gy = grid_y(B);
     hipLaunchKernelGGL(ml_align_kernel, dim3((s.HW + TPB - 1) / TPB, (unsigned)gy), dim3(TPB), 0, st, pred, target, w, s,
                        pred_aligned, target_aligned);
   }
-  return ok() ? DPTX_OK : DPTX_E_HIP;
+  return launch_ok() ? DPTX_OK : DPTX_E_HIP;
 }
 
 }  // extern "C"

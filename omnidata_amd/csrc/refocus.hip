@@ -2,7 +2,7 @@
 // depth-aware defocus blur of the Omnidata paper, as four stream-ordered stages on a caller-provided workspace (no
 // allocation, no host synchronisation, no host read of the radii: graph-capturable).
 //
-//  a. exact quantiles (:82-88): a multi-rank radix select over order-preserving uint32 keys of the fp32 depth, four 8-bit
+//  a. exact quantiles (:82-88): a multi-rank radix select over order-preserving uint32 keys (select.h) of the depth, four 8-bit
 //     digit passes, per-block LDS histograms merged with global atomics (integer counts only: deterministic), then ATen's
 //     quantile arithmetic (rank = fp32(q * (N-1)), floor / ceil, lerp) so that the values are those of CPU torch.quantile.
 //  b. tap tables per (image, level) (:31-57, :77-79, :104-114): radius, M, the normalised Gaussian weights for
@@ -21,18 +21,17 @@
 #include <cstdint>
 
 #include "../../include/dptx.h"
+#include "select.h"
 
 namespace {
+
+using namespace dptx;
 
 constexpr int QSLOTS = 64;                       // distinct key prefixes per select chunk (= ranks per chunk)
 constexpr int QBINS = 256;                       // 8-bit digits, 4 passes
 constexpr int64_t QHIST_BYTES = (int64_t)QSLOTS * QBINS * 4;  // per image
 constexpr int64_t QSLOT_BYTES = 512;             // per image: nslot + QSLOTS sorted prefixes
-constexpr int MAX_SIDE = 8192;
-constexpr int64_t MAX_HW = 1ll << 24;
-constexpr int MAX_GRID_Y = 65535;
-
-int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
+constexpr int64_t Q_PX_PER_BLOCK = 4096, Q_MAX_BLOCKS = 1024;  // pixels per block of a digit pass (at least), blocks (at most)
 
 struct Layout {
   int64_t q_bytes, t_bytes, h_bytes, total;
@@ -54,13 +53,6 @@ bool layout(int32_t B, int32_t C, int32_t H, int32_t W, int32_t n, Layout& lo) {
   lo.total = lo.q_bytes + lo.t_bytes + lo.h_bytes;
   return true;
 }
-
-// order-preserving keys; -0.0 and +0.0 are one key (that of +0.0)
-__device__ __forceinline__ uint32_t f2key(float f) {
-  uint32_t u = __float_as_uint(f == 0.0f ? 0.0f : f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 // fp32 steps rounded one by one, as the reference's CPU arithmetic rounds them.  Plain operators under `fp contract(off)`:
 // the IR carries no `contract` flag then, so no FMA can absorb them (the __f*_rn intrinsics do not prevent that -- hipcc
@@ -425,8 +417,6 @@ __global__ __launch_bounds__(256) void vpass_kernel(const float* __restrict__ rg
   }
 }
 
-bool ok() { return hipGetLastError() == hipSuccess; }
-
 }  // namespace
 
 extern "C" {
@@ -445,20 +435,20 @@ int dptx_refocus_quantiles(const float* depth, int32_t B, int32_t H, int32_t W, 
   hipStream_t st = (hipStream_t)stream;
   const uint32_t N = (uint32_t)H * (uint32_t)W;
   const int n = n_quantiles, R = 2 * (n + 1);
-  const int gy = B < MAX_GRID_Y ? B : MAX_GRID_Y;
-  const uint32_t nblk = std::min<uint32_t>((N + 4095) / 4096, 1024);
-  const uint32_t per_block = (N + nblk - 1) / nblk;
+  const int gy = grid_y(B);
+  int64_t nblk, per_block;
+  split(N, Q_PX_PER_BLOCK, Q_MAX_BLOCKS, nblk, per_block);
   for (int chunk0 = 0; chunk0 < R; chunk0 += QSLOTS) {
     const int m = std::min(QSLOTS, R - chunk0);
     hipLaunchKernelGGL(q_step_kernel, dim3(gy), dim3(64), 0, st, ws, B, N, n, R, chunk0, m, 0);
     for (int p = 0; p < 4; ++p) {
-      hipLaunchKernelGGL(q_hist_kernel, dim3(nblk, gy), dim3(256), 0, st, depth, ws, B, N, R, p, per_block);
+      hipLaunchKernelGGL(q_hist_kernel, dim3((unsigned)nblk, gy), dim3(256), 0, st, depth, ws, B, N, R, p, (uint32_t)per_block);
       hipLaunchKernelGGL(q_step_kernel, dim3(gy), dim3(64), 0, st, ws, B, N, n, R, chunk0, m, p + 1);
     }
   }
   const int64_t tot = (int64_t)B * (n + 1);
   hipLaunchKernelGGL(q_final_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, ws, B, N, n, R, 1e-4f, qvals);
-  return ok() ? DPTX_OK : DPTX_E_HIP;
+  return launch_ok() ? DPTX_OK : DPTX_E_HIP;
 }
 
 int dptx_refocus(const float* rgb, const float* depth, int32_t B, int32_t C, int32_t H, int32_t W, int32_t n_quantiles,
@@ -474,14 +464,14 @@ int dptx_refocus(const float* rgb, const float* depth, int32_t B, int32_t C, int
   float* hstack = (float*)((char*)ws + lo.q_bytes + lo.t_bytes);
   const int64_t bc = (int64_t)B * C;
   if (bc > 0x7fffffff) return DPTX_E_INVALID;
-  const int gb = B < MAX_GRID_Y ? B : MAX_GRID_Y;
+  const int gb = grid_y(B);
   const int gbc = bc < MAX_GRID_Y ? (int)bc : MAX_GRID_Y;
   hipLaunchKernelGGL(tables_kernel, dim3(n1, gb), dim3(256), 0, st, B, n1, lo.L, lo.TS, qvals, focus, aperture, tables);
   hipLaunchKernelGGL(hpass_kernel, dim3(H, gbc), dim3(256), (size_t)2 * W * sizeof(float), st, rgb, B, C, H, W, n1, lo.L, lo.TS,
                      tables, hstack);
   hipLaunchKernelGGL(vpass_kernel, dim3((W + 63) / 64, (H + 3) / 4, gb), dim3(64, 4), 0, st, rgb, depth, B, C, H, W, n, lo.L,
                      lo.TS, qvals, tables, hstack, out, segments);
-  return ok() ? DPTX_OK : DPTX_E_HIP;
+  return launch_ok() ? DPTX_OK : DPTX_E_HIP;
 }
 
 }  // extern "C"

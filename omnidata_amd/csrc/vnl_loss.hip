@@ -6,10 +6,9 @@
 //     argument (:95-128 with the constants of the call at :136-140), the z == 0 replacement on the SECOND (:144), both unit
 //     normals and the per-triple loss (:169-189), all in registers; writes keep [B][n] and loss [B][n]; counts K and
 //     histograms the first 8-bit digit of the loss bits (losses are >= 0: the fp32 bit pattern is an order-preserving key).
-//  b. cut (select only): passes 1..3 histogram the next digit under the prefix selected so far; every block derives that
-//     prefix itself from the previous pass's histogram (an inclusive LDS scan), block 0 records it.  The rank is
-//     int(K * 0.25) = K >> 2.  A tie pass counts, per block of the flat (image, triple) order, the kept triples whose loss
-//     equals the cut value.
+//  b. cut (select only): passes 1..3 histogram the next digit under the prefix selected so far: the radix select of
+//     select.h, over the whole batch.  The rank is int(K * 0.25) = K >> 2.  A tie pass counts, per block of the flat
+//     (image, triple) order, the kept triples whose loss equals the cut value.
 //  c. reduce: every block ranks its tied triples (exclusive sum of the tie counts of the blocks before it + a scan inside the
 //     block), so that among kept triples at the cut value the EARLIEST in (image, triple) order are dropped first (the
 //     stable sort's order); fp64 sum of the kept, not-dropped losses per block in a fixed order; finalize (one wave): the
@@ -24,23 +23,20 @@
 // image's per-triple outputs do not depend on the batch.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
 
 #include "../../include/dptx.h"
+#include "select.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int BINS = 256;  // 8-bit digits, 4 passes
-constexpr int NPASS = 4;
-constexpr int MAX_SIDE = 8192;
-constexpr int64_t MAX_HW = 1ll << 24;
+using namespace dptx;
+
 constexpr int64_t MAX_TRIPLES = (1ll << 31) - 1;  // B * n
 constexpr int MAX_N = 1 << 29;
-constexpr int MAX_GRID_Y = 65535;
 constexpr int TPB = 256;
 constexpr int64_t PER_BLOCK = 1024;     // triples per block of the flat passes (at least)
 constexpr int64_t MAX_BLOCKS = 1024;
@@ -49,8 +45,6 @@ constexpr int64_t SORT_MAX_BLOCKS = 512;
 constexpr int HDR = DPTX_VNL_RECORD_HEADER;
 constexpr float DELTA_COS = 0.867f, DELTA_DIFF = 0.005f;  // :136-140
 constexpr float ENERGY_EPS = 1e-8f, ZERO_FILL = 0.0001f, NORM_FILL = 0.01f;
-
-int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
 struct Layout {
   int64_t N, N3, nblk, per_block, snb, schunk;
@@ -66,10 +60,8 @@ bool layout(int32_t B, int32_t H, int32_t W, int32_t n, Layout& lo) {
   const int64_t HW = (int64_t)H * W;
   lo.N = (int64_t)B * n;
   lo.N3 = 3 * (int64_t)n;
-  lo.nblk = std::min<int64_t>((lo.N + PER_BLOCK - 1) / PER_BLOCK, MAX_BLOCKS);
-  lo.per_block = (lo.N + lo.nblk - 1) / lo.nblk;
-  lo.snb = std::min<int64_t>((lo.N3 + SORT_CHUNK - 1) / SORT_CHUNK, SORT_MAX_BLOCKS);
-  lo.schunk = (lo.N3 + lo.snb - 1) / lo.snb;
+  split(lo.N, PER_BLOCK, MAX_BLOCKS, lo.nblk, lo.per_block);
+  split(lo.N3, SORT_CHUNK, SORT_MAX_BLOCKS, lo.snb, lo.schunk);
   int bits = 0;  // keys are 0 .. HW (HW: an entry of a triple with an index out of range, sorted last)
   while ((HW >> bits) != 0) ++bits;
   lo.spass = (bits + 7) / 8;
@@ -277,52 +269,21 @@ __global__ __launch_bounds__(TPB) void vnl_triple_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------- b. radix select of rank K >> 2 among the kept losses
-// The digit of pass q of the rank-th key among the keys with the prefix selected before q: inclusive scan of the pass's
-// histogram.  pre / rank: in = state before pass q, out = state after it (prefix << 8 | digit, rank left).
-__device__ void resolve(const uint32_t* __restrict__ h /*[BINS]*/, uint32_t* sc /*LDS [BINS]*/, uint32_t* res /*LDS [2]*/, bool has,
-                        uint32_t& pre, uint32_t& rank) {
-  const int t = threadIdx.x;
-  const uint32_t h0 = h[t];
-  sc[t] = h0;
-  if (t == 0) {
-    res[0] = pre << 8;
-    res[1] = 0;
-  }
-  __syncthreads();
-  for (int off = 1; off < BINS; off <<= 1) {
-    const uint32_t v0 = t >= off ? sc[t - off] : 0u;
-    __syncthreads();
-    sc[t] += v0;
-    __syncthreads();
-  }
-  const uint32_t inc = sc[t], ex = inc - h0;
-  if (has && ex <= rank && rank < inc) {  // exactly one bin holds the rank
-    res[0] = (pre << 8) | (uint32_t)t;
-    res[1] = rank - ex;
-  }
-  __syncthreads();
-  pre = res[0];
-  rank = res[1];
-  __syncthreads();
-}
-
-// the select state before pass q (q >= 1: derived from pass q - 1's histogram; block 0 records it).  After the last pass:
-// pre = the bits of the cut value, rank = how many of the kept triples AT the cut value are dropped.
-__device__ void select_state(const Ws& w, int q, uint32_t* sc, uint32_t* res, uint32_t& pre, uint32_t& rank) {
+// the select state before pass q (select.h).  After the last pass: pre = the bits of the cut value, rank = how many of the
+// kept triples AT the cut value are dropped.
+__device__ __forceinline__ void select_state(const Ws& w, int q, uint32_t (*sc)[BINS], uint32_t* res, uint32_t& pre, uint32_t& rank) {
   const uint32_t K = w.cnt[0];
-  const bool has = K > 0;
-  pre = q == 1 ? 0u : w.state[(q - 1) * 2];
-  rank = q == 1 ? (K >> 2) : w.state[(q - 1) * 2 + 1];  // int(K * 0.25)
-  resolve(w.hist + (q - 1) * BINS, sc, res, has, pre, rank);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    w.state[q * 2] = pre;
-    w.state[q * 2 + 1] = rank;
-  }
+  const bool has[1] = {K > 0};
+  const uint32_t rank0[1] = {K >> 2};  // int(K * 0.25)
+  uint32_t p[1], r[1];
+  dptx::select_state<1>(w.hist, w.state, q, sc, res, has, rank0, p, r);
+  pre = p[0];
+  rank = r[0];
 }
 
 __global__ __launch_bounds__(TPB) void vnl_pass_kernel(Ws w, uint32_t N, uint32_t per_block, int pass) {
   __shared__ uint32_t lh[BINS];
-  __shared__ uint32_t sc[BINS];
+  __shared__ uint32_t sc[1][BINS];
   __shared__ uint32_t res[2];
   const int t = threadIdx.x;
   uint32_t pre, rank;
@@ -341,7 +302,7 @@ __global__ __launch_bounds__(TPB) void vnl_pass_kernel(Ws w, uint32_t N, uint32_
 }
 
 // the cut of this call: with select, the state after the last pass; without, nothing is dropped
-__device__ void final_state(const Ws& w, int select, uint32_t* sc, uint32_t* res, uint32_t& cut, uint32_t& tdrop) {
+__device__ void final_state(const Ws& w, int select, uint32_t (*sc)[BINS], uint32_t* res, uint32_t& cut, uint32_t& tdrop) {
   cut = 0;
   tdrop = 0;
   if (select) select_state(w, NPASS, sc, res, cut, tdrop);
@@ -349,7 +310,7 @@ __device__ void final_state(const Ws& w, int select, uint32_t* sc, uint32_t* res
 
 // kept triples of this block's range whose loss equals the cut value
 __global__ __launch_bounds__(TPB) void vnl_tie_kernel(Ws w, uint32_t N, uint32_t per_block, int select) {
-  __shared__ uint32_t sc[BINS];
+  __shared__ uint32_t sc[1][BINS];
   __shared__ uint32_t res[2];
   __shared__ uint32_t lt;
   const int t = threadIdx.x;
@@ -369,7 +330,7 @@ __global__ __launch_bounds__(TPB) void vnl_tie_kernel(Ws w, uint32_t N, uint32_t
 // ---------------------------------------------------------------- c. reduce
 __global__ __launch_bounds__(TPB) void vnl_reduce_kernel(Ws w, uint32_t N, uint32_t per_block, int select,
                                                          uint8_t* __restrict__ active /*nullable*/) {
-  __shared__ uint32_t sc[BINS];
+  __shared__ uint32_t sc[1][BINS];
   __shared__ uint32_t res[2];
   __shared__ uint32_t lbase;
   __shared__ uint32_t wsum[4];
@@ -385,7 +346,7 @@ __global__ __launch_bounds__(TPB) void vnl_reduce_kernel(Ws w, uint32_t N, uint3
   __syncthreads();
   uint32_t run = lbase;
   const uint32_t lo = blockIdx.x * per_block, hi = min(N, lo + per_block);
-  double v = 0.0;
+  double v[1] = {0.0};
   for (uint32_t tile = lo; tile < hi; tile += TPB) {  // uniform trip count: the block scans every tile together
     const uint32_t i = tile + t;
     const bool in = i < hi;
@@ -406,13 +367,10 @@ __global__ __launch_bounds__(TPB) void vnl_reduce_kernel(Ws w, uint32_t N, uint3
     const bool act = kept && (key > cut || (tie && run + before + wrank >= tdrop));
     run += all;
     __syncthreads();
-    if (act) v += (double)loss;
+    if (act) v[0] += (double)loss;
     if (active && in) active[i] = act ? 1 : 0;
   }
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  if (t == 0) w.part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  block_sum<1>(v, red, w.part + blockIdx.x);
 }
 
 __global__ __launch_bounds__(64) void vnl_finalize_kernel(Ws w, int nblk, int select, float* __restrict__ loss_out,
@@ -420,7 +378,7 @@ __global__ __launch_bounds__(64) void vnl_finalize_kernel(Ws w, int nblk, int se
   const int t = threadIdx.x;
   double v = 0.0;
   for (int j = t; j < nblk; j += 64) v += w.part[j];
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  v = wave_sum(v);
   if (t != 0) return;
   const uint32_t K = w.cnt[0];
   const uint32_t rank = select ? (K >> 2) : 0u;
@@ -470,20 +428,14 @@ __global__ __launch_bounds__(64) void vnl_sort_count_kernel(const uint32_t* __re
 
 // exclusive scan of bh in (digit, block) order, in place (one block; thread d owns digit d)
 __global__ __launch_bounds__(BINS) void vnl_sort_scan_kernel(uint32_t* __restrict__ bh, int snb) {
-  __shared__ uint32_t sc[BINS];
+  __shared__ uint32_t sc[1][BINS];
   const int t = threadIdx.x;
   uint32_t* row = bh + (int64_t)t * snb;
   uint32_t tot = 0;
   for (int j = 0; j < snb; ++j) tot += row[j];
-  sc[t] = tot;
-  __syncthreads();
-  for (int off = 1; off < BINS; off <<= 1) {
-    const uint32_t v0 = t >= off ? sc[t - off] : 0u;
-    __syncthreads();
-    sc[t] += v0;
-    __syncthreads();
-  }
-  uint32_t run = sc[t] - tot;
+  sc[0][t] = tot;
+  block_scan256<1>(sc);
+  uint32_t run = sc[0][t] - tot;
   for (int j = 0; j < snb; ++j) {
     const uint32_t c = row[j];
     row[j] = run;
@@ -652,8 +604,6 @@ __global__ __launch_bounds__(TPB) void vnl_backward_kernel(const float* __restri
   }
 }
 
-bool ok() { return hipGetLastError() == hipSuccess; }
-
 Geo geo(int32_t B, int32_t H, int32_t W, int32_t n, float fx, float fy, float delta_z) {
   return Geo{B, H, W, n, (uint32_t)((int64_t)H * W), fx, fy, delta_z};
 }
@@ -691,7 +641,7 @@ int dptx_vnl_prepare(const int32_t* p1, const int32_t* p2, const int32_t* p3, in
                        shift, w.bh, key[cur ^ 1], ent[cur ^ 1]);
   }
   hipLaunchKernelGGL(vnl_first_kernel, dim3((N3 + TPB - 1) / TPB), dim3(TPB), 0, st, key[1], N3, HW, first);
-  return ok() ? DPTX_OK : DPTX_E_HIP;
+  return launch_ok() ? DPTX_OK : DPTX_E_HIP;
 }
 
 int dptx_vnl_loss(const float* first, const float* second, int32_t B, int32_t H, int32_t W, float fx, float fy, float delta_z,
@@ -706,7 +656,7 @@ int dptx_vnl_loss(const float* first, const float* second, int32_t B, int32_t H,
   const uint32_t N = (uint32_t)lo.N, per = (uint32_t)lo.per_block;
   const int sel = select ? 1 : 0;
   if (hipMemsetAsync(w.cnt, 0, (size_t)lo.zero_bytes, st) != hipSuccess) return DPTX_E_HIP;
-  hipLaunchKernelGGL(vnl_triple_kernel, dim3((unsigned)((n + TPB - 1) / TPB), (unsigned)std::min(B, MAX_GRID_Y)), dim3(TPB), 0, st, first,
+  hipLaunchKernelGGL(vnl_triple_kernel, dim3((unsigned)((n + TPB - 1) / TPB), (unsigned)grid_y(B)), dim3(TPB), 0, st, first,
                      second, g, Idx{{p1, p2, p3}}, w.keep, w.loss, (float*)nullptr, w.cnt, w.hist);
   const dim3 grid((unsigned)lo.nblk);
   if (sel)
@@ -714,7 +664,7 @@ int dptx_vnl_loss(const float* first, const float* second, int32_t B, int32_t H,
   hipLaunchKernelGGL(vnl_tie_kernel, grid, dim3(TPB), 0, st, w, N, per, sel);
   hipLaunchKernelGGL(vnl_reduce_kernel, grid, dim3(TPB), 0, st, w, N, per, sel, record ? record + HDR : (uint8_t*)nullptr);
   hipLaunchKernelGGL(vnl_finalize_kernel, dim3(1), dim3(64), 0, st, w, (int)lo.nblk, sel, loss_out, record);
-  return ok() ? DPTX_OK : DPTX_E_HIP;
+  return launch_ok() ? DPTX_OK : DPTX_E_HIP;
 }
 
 int dptx_vnl_loss_backward(const float* first, const float* second, int32_t B, int32_t H, int32_t W, float fx, float fy,
@@ -725,9 +675,9 @@ int dptx_vnl_loss_backward(const float* first, const float* second, int32_t B, i
       !layout(B, H, W, n, lo))
     return DPTX_E_INVALID;
   const Geo g = geo(B, H, W, n, fx, fy, 0.0f);
-  hipLaunchKernelGGL(vnl_backward_kernel, dim3((g.HW + TPB - 1) / TPB, (unsigned)std::min(B, MAX_GRID_Y)), dim3(TPB), 0,
+  hipLaunchKernelGGL(vnl_backward_kernel, dim3((g.HW + TPB - 1) / TPB, (unsigned)grid_y(B)), dim3(TPB), 0,
                      (hipStream_t)stream, first, second, g, Idx{{p1, p2, p3}}, record, inverse, grad_out, grad_first, grad_second);
-  return ok() ? DPTX_OK : DPTX_E_HIP;
+  return launch_ok() ? DPTX_OK : DPTX_E_HIP;
 }
 
 int dptx_vnl_triples(const float* first, const float* second, int32_t B, int32_t H, int32_t W, float fx, float fy, float delta_z,
@@ -735,10 +685,10 @@ int dptx_vnl_triples(const float* first, const float* second, int32_t B, int32_t
                      void* stream) {
   Layout lo;
   if (!first || !second || !p1 || !p2 || !p3 || !keep || !loss || !layout(B, H, W, n, lo)) return DPTX_E_INVALID;
-  hipLaunchKernelGGL(vnl_triple_kernel, dim3((unsigned)((n + TPB - 1) / TPB), (unsigned)std::min(B, MAX_GRID_Y)), dim3(TPB), 0,
+  hipLaunchKernelGGL(vnl_triple_kernel, dim3((unsigned)((n + TPB - 1) / TPB), (unsigned)grid_y(B)), dim3(TPB), 0,
                      (hipStream_t)stream, first, second, geo(B, H, W, n, fx, fy, delta_z), Idx{{p1, p2, p3}}, keep, loss, normals,
                      (uint32_t*)nullptr, (uint32_t*)nullptr);
-  return ok() ? DPTX_OK : DPTX_E_HIP;
+  return launch_ok() ? DPTX_OK : DPTX_E_HIP;
 }
 
 }  // extern "C"

@@ -12,34 +12,21 @@ fp32 sums leave a tiny non-zero det there and an arbitrary scale.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 from torch.autograd.function import once_differentiable
 
-from .engine import load_library
+from ._native import call, check_cuda, workspace
+from .engine import _stream
 
 SSI, GRAD, ALIGN, INVERSE = 1, 2, 4, 8          # include/dptx.h DPTX_MIDAS_*
 RECORD_DOUBLES = 32                             # DPTX_MIDAS_RECORD_DOUBLES
 STATS = 8                                       # DPTX_MIDAS_STATS
-_ws_cache: dict = {}
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _workspace(B: int, H: int, W: int, scales: int, device) -> torch.Tensor:
-    nbytes = C.c_int64()
-    if load_library().dptx_midas_workspace_bytes(B, H, W, scales, C.byref(nbytes)) != 0:
-        raise ValueError(f"unsupported MiDaS loss shape B={B} H={H} W={W} scales={scales} "
-                         "(B >= 1, 1 <= H, W <= 8192, H*W <= 2^24, 1 <= scales <= 8)")
-    key = (str(device), B, H, W)
-    ws = _ws_cache.get(key)
-    if ws is None:
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-        _ws_cache[key] = ws
-    return ws
+    return workspace("dptx_midas_workspace_bytes", device, (B, H, W, scales),
+                     f"unsupported MiDaS loss shape B={B} H={H} W={W} scales={scales} "
+                     "(B >= 1, 1 <= H, W <= 8192, H*W <= 2^24, 1 <= scales <= 8)")
 
 
 def _inputs(prediction, target, mask, dim: int, differentiable: bool):
@@ -47,8 +34,7 @@ def _inputs(prediction, target, mask, dim: int, differentiable: bool):
     graph), fp32 target and uint8 mask, contiguous [B, H, W]."""
     shape = "[B,1,H,W]" if dim == 4 else "[B,H,W]"
     for name, t in (("prediction", prediction), ("target", target), ("mask", mask)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"{name} must be a CUDA tensor (omnidata_amd has no CPU path)")
+        check_cuda(name, t)
         if t.dim() != dim or (dim == 4 and t.shape[1] != 1):
             raise ValueError(f"{name} must be {shape}, got shape {tuple(t.shape)}")
     if prediction.shape != target.shape or mask.shape != prediction.shape:
@@ -80,11 +66,8 @@ class _MidasLossFn(torch.autograd.Function):
         # the coefficient record belongs to this call (ctx), not to the cached workspace: two losses summed before one
         # backward() each keep their own
         record = torch.empty(B, RECORD_DOUBLES, dtype=torch.float64, device=pred.device) if want else None
-        rc = load_library().dptx_midas_loss(pred.data_ptr(), target.data_ptr(), mask.data_ptr(), B, H, W, terms, scales,
-                                            int(image_based), float(alpha), losses.data_ptr(),
-                                            record.data_ptr() if want else None, ws.data_ptr(), ws.numel(), _stream(pred))
-        if rc != 0:
-            raise RuntimeError(f"dptx_midas_loss failed ({rc})")
+        call("dptx_midas_loss", pred.data_ptr(), target.data_ptr(), mask.data_ptr(), B, H, W, terms, scales, int(image_based),
+             float(alpha), losses.data_ptr(), record.data_ptr() if want else None, ws.data_ptr(), ws.numel(), _stream(pred.device))
         ctx.cfg = (terms, scales, int(image_based), float(alpha))
         if want:
             ctx.save_for_backward(pred, target, mask, record)
@@ -98,11 +81,8 @@ class _MidasLossFn(torch.autograd.Function):
         B, H, W = pred.shape
         g = grad_losses.float().contiguous()
         grad = torch.empty_like(pred)
-        rc = load_library().dptx_midas_loss_backward(pred.data_ptr(), target.data_ptr(), mask.data_ptr(), B, H, W, terms, scales,
-                                                     image_based, alpha, record.data_ptr(), g.data_ptr(), grad.data_ptr(),
-                                                     _stream(pred))
-        if rc != 0:
-            raise RuntimeError(f"dptx_midas_loss_backward failed ({rc})")
+        call("dptx_midas_loss_backward", pred.data_ptr(), target.data_ptr(), mask.data_ptr(), B, H, W, terms, scales, image_based,
+             alpha, record.data_ptr(), g.data_ptr(), grad.data_ptr(), _stream(pred.device))
         return grad, None, None, None, None, None, None
 
 
@@ -155,11 +135,8 @@ def _stats(prediction, target, mask, dim, terms, aligned=False):
     st = torch.empty(B, STATS, dtype=torch.float32, device=p.device)
     pa = torch.empty_like(p) if aligned else None
     ga = torch.empty_like(t) if aligned else None
-    rc = load_library().dptx_midas_stats(p.data_ptr(), t.data_ptr(), m.data_ptr(), B, H, W, terms, st.data_ptr(),
-                                         pa.data_ptr() if aligned else None, ga.data_ptr() if aligned else None, ws.data_ptr(),
-                                         ws.numel(), _stream(p))
-    if rc != 0:
-        raise RuntimeError(f"dptx_midas_stats failed ({rc})")
+    call("dptx_midas_stats", p.data_ptr(), t.data_ptr(), m.data_ptr(), B, H, W, terms, st.data_ptr(),
+         pa.data_ptr() if aligned else None, ga.data_ptr() if aligned else None, ws.data_ptr(), ws.numel(), _stream(p.device))
     return st, pa, ga
 
 

@@ -8,37 +8,23 @@ path, as everywhere in omnidata_amd.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from .engine import load_library
+from ._native import call, check_cuda, workspace
+from .engine import _stream
 
 EPS = 1e-4          # compute_quantiles' eps as the reference's only caller passes it (:188); the kernel applies it
 MAX_M = 1 << 24     # largest blur filter the kernels define results for
-_ws_cache: dict = {}
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _workspace(B: int, C_: int, H: int, W: int, n: int, device) -> torch.Tensor:
-    nbytes = C.c_int64()
-    if load_library().dptx_refocus_workspace_bytes(B, C_, H, W, n, C.byref(nbytes)) != 0:
-        raise ValueError(f"unsupported refocus shape B={B} C={C_} H={H} W={W} n_quantiles={n} "
-                         "(1 <= H, W <= 8192, H*W <= 2^24, B, C, n >= 1)")
-    key = (str(device), B, C_, H, W, n)
-    ws = _ws_cache.get(key)
-    if ws is None:
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-        _ws_cache[key] = ws
-    return ws
+    return workspace("dptx_refocus_workspace_bytes", device, (B, C_, H, W, n),
+                     f"unsupported refocus shape B={B} C={C_} H={H} W={W} n_quantiles={n} "
+                     "(1 <= H, W <= 8192, H*W <= 2^24, B, C, n >= 1)")
 
 
 def _check_cuda(name: str, t: torch.Tensor, dim: int) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise ValueError(f"{name} must be a CUDA tensor (omnidata_amd has no CPU path)")
+    check_cuda(name, t)
     if t.dim() != dim:
         raise ValueError(f"{name} must be {dim}-D, got shape {tuple(t.shape)}")
     return t.detach().float().contiguous()
@@ -54,9 +40,7 @@ def compute_quantiles(depth: torch.Tensor, n_quantiles: int, eps: float = EPS) -
     n = int(n_quantiles)
     ws = _workspace(B, 1, H, W, n, d.device)
     q = torch.empty(B, n + 1, dtype=torch.float32, device=d.device)
-    rc = load_library().dptx_refocus_quantiles(d.data_ptr(), B, H, W, n, q.data_ptr(), ws.data_ptr(), ws.numel(), _stream(d))
-    if rc != 0:
-        raise RuntimeError(f"dptx_refocus_quantiles failed ({rc})")
+    call("dptx_refocus_quantiles", d.data_ptr(), B, H, W, n, q.data_ptr(), ws.data_ptr(), ws.numel(), _stream(d.device))
     return q
 
 
@@ -103,11 +87,8 @@ def refocus_image(rgb: torch.Tensor, depth: torch.Tensor, focus_distance, apertu
     _check_domain(d, q, f, a)
     out = torch.empty_like(x)
     seg = torch.empty(B, 1, H, W, dtype=torch.int64, device=x.device) if return_segments else None
-    rc = load_library().dptx_refocus(x.data_ptr(), d.data_ptr(), B, C_, H, W, n, q.data_ptr(), f.data_ptr(), a.data_ptr(),
-                                     out.data_ptr(), seg.data_ptr() if seg is not None else None, ws.data_ptr(), ws.numel(),
-                                     _stream(x))
-    if rc != 0:
-        raise RuntimeError(f"dptx_refocus failed ({rc})")
+    call("dptx_refocus", x.data_ptr(), d.data_ptr(), B, C_, H, W, n, q.data_ptr(), f.data_ptr(), a.data_ptr(), out.data_ptr(),
+         seg.data_ptr() if seg is not None else None, ws.data_ptr(), ws.numel(), _stream(x.device))
     return (out, seg) if return_segments else out
 
 

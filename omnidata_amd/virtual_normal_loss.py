@@ -13,42 +13,28 @@ order are dropped first (the order of a stable sort).
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from .engine import load_library
+from ._native import call, check_cuda, workspace
+from .engine import _stream
 from .midas_loss import MidasLoss
 
 RECORD_HEADER = 64                              # include/dptx.h DPTX_VNL_RECORD_HEADER
-_ws_cache: dict = {}
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _workspace(B: int, H: int, W: int, n: int, device) -> torch.Tensor:
-    nbytes = C.c_int64()
-    if load_library().dptx_vnl_workspace_bytes(B, H, W, n, C.byref(nbytes)) != 0:
-        raise ValueError(f"unsupported virtual normal loss shape B={B} H={H} W={W} n={n} "
-                         "(B >= 1, 1 <= H, W <= 8192, H*W <= 2^24, 1 <= n <= 2^29, B*n < 2^31)")
-    key = (str(device), B, H, W, n)
-    ws = _ws_cache.get(key)
-    if ws is None:
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-        _ws_cache[key] = ws
-    return ws
+    return workspace("dptx_vnl_workspace_bytes", device, (B, H, W, n),
+                     f"unsupported virtual normal loss shape B={B} H={H} W={W} n={n} "
+                     "(B >= 1, 1 <= H, W <= 8192, H*W <= 2^24, 1 <= n <= 2^29, B*n < 2^31)")
 
 
 def _inputs(first, second, input_size):
     """Validates (ValueError where the reference fails or where there is no path) -> fp32 contiguous [B, H, W] tensors,
     still in the autograd graph."""
     for name, t in (("gt_depth", first), ("pred_depth", second)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"{name} must be a CUDA tensor (omnidata_amd has no CPU path)")
+        check_cuda(name, t)
         if t.dim() != 4 or t.shape[1] != 1:
             raise ValueError(f"{name} must be [B,1,H,W], got shape {tuple(t.shape)}")
         if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
@@ -83,7 +69,6 @@ class _VNLFn(torch.autograd.Function):
     def forward(ctx, first, second, p, fx, fy, delta_z, select):
         B, H, W = first.shape
         n = p.shape[1]
-        lib = load_library()
         ws = _workspace(B, H, W, n, first.device)
         loss = torch.empty((), dtype=torch.float32, device=first.device)
         want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
@@ -91,18 +76,13 @@ class _VNLFn(torch.autograd.Function):
         # backward() each keep their own record and inverse index
         record = torch.empty(RECORD_HEADER + B * n, dtype=torch.uint8, device=first.device) if want else None
         inverse = None
-        st = _stream(first)
+        st = _stream(first.device)
         if want:
             inverse = torch.empty(H * W + 6 * n, dtype=torch.int32, device=first.device)
-            rc = lib.dptx_vnl_prepare(p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(), n, H, W, inverse.data_ptr(), ws.data_ptr(),
-                                      ws.numel(), st)
-            if rc != 0:
-                raise RuntimeError(f"dptx_vnl_prepare failed ({rc})")
-        rc = lib.dptx_vnl_loss(first.data_ptr(), second.data_ptr(), B, H, W, fx, fy, delta_z, p[0].data_ptr(), p[1].data_ptr(),
-                               p[2].data_ptr(), n, int(select), loss.data_ptr(), record.data_ptr() if want else None, ws.data_ptr(),
-                               ws.numel(), st)
-        if rc != 0:
-            raise RuntimeError(f"dptx_vnl_loss failed ({rc})")
+            call("dptx_vnl_prepare", p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(), n, H, W, inverse.data_ptr(), ws.data_ptr(),
+                 ws.numel(), st)
+        call("dptx_vnl_loss", first.data_ptr(), second.data_ptr(), B, H, W, fx, fy, delta_z, p[0].data_ptr(), p[1].data_ptr(),
+             p[2].data_ptr(), n, int(select), loss.data_ptr(), record.data_ptr() if want else None, ws.data_ptr(), ws.numel(), st)
         ctx.cfg = (fx, fy)
         if want:
             ctx.save_for_backward(first, second, p, record, inverse)
@@ -118,12 +98,9 @@ class _VNLFn(torch.autograd.Function):
         g = grad_out.float().reshape(1).contiguous()
         g1 = torch.empty_like(first) if ctx.needs_input_grad[0] else None
         g2 = torch.empty_like(second) if ctx.needs_input_grad[1] else None
-        rc = load_library().dptx_vnl_loss_backward(first.data_ptr(), second.data_ptr(), B, H, W, fx, fy, p[0].data_ptr(),
-                                                   p[1].data_ptr(), p[2].data_ptr(), n, record.data_ptr(), inverse.data_ptr(),
-                                                   g.data_ptr(), g1.data_ptr() if g1 is not None else None,
-                                                   g2.data_ptr() if g2 is not None else None, _stream(first))
-        if rc != 0:
-            raise RuntimeError(f"dptx_vnl_loss_backward failed ({rc})")
+        call("dptx_vnl_loss_backward", first.data_ptr(), second.data_ptr(), B, H, W, fx, fy, p[0].data_ptr(), p[1].data_ptr(),
+             p[2].data_ptr(), n, record.data_ptr(), inverse.data_ptr(), g.data_ptr(), g1.data_ptr() if g1 is not None else None,
+             g2.data_ptr() if g2 is not None else None, _stream(first.device))
         return g1, g2, None, None, None, None, None
 
 
@@ -180,11 +157,8 @@ class VNL_Loss(torch.nn.Module):
         keep = torch.empty(B, n, dtype=torch.uint8, device=first.device)
         loss = torch.empty(B, n, dtype=torch.float32, device=first.device)
         normals = torch.empty(B, n, 2, 3, dtype=torch.float32, device=first.device)
-        rc = load_library().dptx_vnl_triples(first.data_ptr(), second.data_ptr(), B, H, W, self.fx, self.fy, float(self.delta_z),
-                                             p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(), n, keep.data_ptr(), loss.data_ptr(),
-                                             normals.data_ptr(), _stream(first))
-        if rc != 0:
-            raise RuntimeError(f"dptx_vnl_triples failed ({rc})")
+        call("dptx_vnl_triples", first.data_ptr(), second.data_ptr(), B, H, W, self.fx, self.fy, float(self.delta_z), p[0].data_ptr(),
+             p[1].data_ptr(), p[2].data_ptr(), n, keep.data_ptr(), loss.data_ptr(), normals.data_ptr(), _stream(first.device))
         return dict(keep=keep.bool(), loss=loss, normal_first=normals[:, :, 0], normal_second=normals[:, :, 1])
 
     def diagnostics(self, gt_depth, pred_depth, p123, select=True):
@@ -196,11 +170,9 @@ class VNL_Loss(torch.nn.Module):
         ws = _workspace(B, H, W, n, first.device)
         loss = torch.empty(1, dtype=torch.float32, device=first.device)
         record = torch.empty(RECORD_HEADER + B * n, dtype=torch.uint8, device=first.device)
-        rc = load_library().dptx_vnl_loss(first.data_ptr(), second.data_ptr(), B, H, W, self.fx, self.fy, float(self.delta_z),
-                                          p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(), n, int(bool(select)), loss.data_ptr(),
-                                          record.data_ptr(), ws.data_ptr(), ws.numel(), _stream(first))
-        if rc != 0:
-            raise RuntimeError(f"dptx_vnl_loss failed ({rc})")
+        call("dptx_vnl_loss", first.data_ptr(), second.data_ptr(), B, H, W, self.fx, self.fy, float(self.delta_z), p[0].data_ptr(),
+             p[1].data_ptr(), p[2].data_ptr(), n, int(bool(select)), loss.data_ptr(), record.data_ptr(), ws.data_ptr(), ws.numel(),
+             _stream(first.device))
         head = record[:16].cpu().numpy().view(np.uint32)
         return dict(loss=loss[0], K=int(head[0]), dropped=int(head[1]), cut=float(head[2:3].view(np.float32)[0]),
                     active=record[RECORD_HEADER:].view(B, n).bool())

@@ -1,4 +1,5 @@
 """Helpers for the -m gpu tests: call libdptx.so op entry points on torch CUDA tensors."""
+import numpy as np
 import torch
 
 from omnidata_amd.engine import load_library, DTYPES
@@ -20,6 +21,25 @@ def ptr(t):
 def rel_err(a, ref):
     a, ref = a.double(), ref.double()
     return float((a - ref).abs().max() / ref.abs().max().clamp_min(1e-12))
+
+
+def ulps(a, b):
+    """fp32 ulp distance elementwise (-0 = +0; NaN = NaN)"""
+    def ordered(x):
+        i = np.ascontiguousarray(torch.as_tensor(x).float().cpu().numpy()).view(np.int32).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+    a32, b32 = torch.as_tensor(a).float().cpu(), torch.as_tensor(b).float().cpu()
+    d = np.abs(ordered(a32) - ordered(b32))
+    both_nan = (torch.isnan(a32) & torch.isnan(b32)).numpy()
+    return np.where(both_nan, 0, d)
+
+
+def smooth(gen, B, H, W, lo, hi, k=5):
+    """[B, 1, H, W] fp32 (CPU): a k x k grid of uniform draws interpolated to H x W, stretched to [lo, hi] per image"""
+    g = torch.rand(B, 1, k, k, generator=gen)
+    f = torch.nn.functional.interpolate(g, size=(H, W), mode="bilinear", align_corners=True)
+    f = (f - f.amin((2, 3), keepdim=True)) / (f.amax((2, 3), keepdim=True) - f.amin((2, 3), keepdim=True)).clamp_min(1e-12)
+    return (lo + (hi - lo) * f).float().contiguous()
 
 
 def op_gemm(dtype, A, W, bias=None, R=None, act=0, c_fp32=False):

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import midas_restatement as rs
+from gpu_util import smooth, ulps
 from omnidata_amd import midas_loss as ml
 
 pytestmark = pytest.mark.gpu
@@ -15,13 +16,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "midas_*.npz")))
 LOSS_GOLDEN = [p for p in GOLDEN if not p.endswith("_parts.npz")]
 ULP2 = 2.0 ** -22   # 2 fp32 ulps, relative
-
-
-def smooth(gen, B, H, W, lo, hi, k=5):
-    g = torch.rand(B, 1, k, k, generator=gen)
-    f = torch.nn.functional.interpolate(g, size=(H, W), mode="bilinear", align_corners=True)[:, 0]
-    f = (f - f.amin((1, 2), keepdim=True)) / (f.amax((1, 2), keepdim=True) - f.amin((1, 2), keepdim=True)).clamp_min(1e-12)
-    return (lo + (hi - lo) * f).float().contiguous()
 
 
 def values(kind, B, H, W, gen):
@@ -35,7 +29,7 @@ def values(kind, B, H, W, gen):
         d.view(B, -1)[:, 3::11] = -0.0
         return d
     if kind == "plateau":  # 16-bit decoded depth, half of the image at the far value 65535
-        v = (smooth(gen, B, H, W, 200.0, 9000.0) / 32).round() * 32
+        v = (smooth(gen, B, H, W, 200.0, 9000.0)[:, 0] / 32).round() * 32
         v.view(B, -1)[:, : (H * W) // 2] = 65535.0
         return (v / 65535.0) / torch.tensor(8000.0 / 65535.0)
     raise ValueError(kind)
@@ -54,22 +48,11 @@ def case(B, H, W, seed, frac=0.8, kind="pair"):
     """pred, target [B,1,H,W] fp32 and mask (CPU): a target depth, a prediction that is an affine map of it plus a smooth
     field and noise"""
     gen = torch.Generator().manual_seed(seed)
-    t = smooth(gen, B, H, W, 0.5, 6.0)
-    p = 0.7 * t + 0.3 + 0.5 * smooth(gen, B, H, W, 0.0, 1.0) + 0.02 * torch.randn(B, H, W, generator=gen)
+    t = smooth(gen, B, H, W, 0.5, 6.0)[:, 0]
+    p = 0.7 * t + 0.3 + 0.5 * smooth(gen, B, H, W, 0.0, 1.0)[:, 0] + 0.02 * torch.randn(B, H, W, generator=gen)
     if kind == "ties":
         p, t = (p * 4).round() / 4, (t * 2).round() / 2
     return p[:, None].contiguous(), t[:, None].contiguous(), make_mask(frac, B, H, W, gen)[:, None]
-
-
-def ulps(a, b):
-    """fp32 ulp distance elementwise (-0 = +0; NaN = NaN)"""
-    def ordered(x):
-        i = np.ascontiguousarray(torch.as_tensor(x).float().cpu().numpy()).view(np.int32).astype(np.int64)
-        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
-    a32, b32 = torch.as_tensor(a).float().cpu(), torch.as_tensor(b).float().cpu()
-    d = np.abs(ordered(a32) - ordered(b32))
-    both_nan = (torch.isnan(a32) & torch.isnan(b32)).numpy()
-    return np.where(both_nan, 0, d)
 
 
 @pytest.mark.parametrize("shape", [(2, 384, 384), (3, 37, 53), (1, 1, 4097), (4, 512, 640)])

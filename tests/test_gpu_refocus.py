@@ -11,18 +11,12 @@ import torch
 from PIL import Image
 
 import refocus_restatement as rs
+from gpu_util import smooth
 from omnidata_amd import refocus as rf
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "refocus_*.npz")))
-
-
-def smooth(gen, B, H, W, lo, hi, k=5):
-    g = torch.rand(B, 1, k, k, generator=gen)
-    f = torch.nn.functional.interpolate(g, size=(H, W), mode="bilinear", align_corners=True)
-    f = (f - f.amin((2, 3), keepdim=True)) / (f.amax((2, 3), keepdim=True) - f.amin((2, 3), keepdim=True)).clamp_min(1e-12)
-    return (lo + (hi - lo) * f).float().contiguous()
 
 
 def depth_case(kind, B, H, W, seed):

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import vnl_restatement as rs
+from gpu_util import smooth, ulps
 from omnidata_amd import virtual_normal_loss as vl
 from omnidata_amd.midas_loss import MidasLoss
 
@@ -16,24 +17,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "vnl_*.npz")))
 IDS = [os.path.basename(p)[4:-4] for p in GOLDEN]
 P_KEYS = ("p1_x", "p1_y", "p2_x", "p2_y", "p3_x", "p3_y")
-
-
-def ulps(a, b):
-    """fp32 ulp distance elementwise (-0 = +0; NaN = NaN)"""
-    def ordered(x):
-        i = np.ascontiguousarray(torch.as_tensor(x).float().cpu().numpy()).view(np.int32).astype(np.int64)
-        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
-    a32, b32 = torch.as_tensor(a).float().cpu(), torch.as_tensor(b).float().cpu()
-    d = np.abs(ordered(a32) - ordered(b32))
-    both_nan = (torch.isnan(a32) & torch.isnan(b32)).numpy()
-    return np.where(both_nan, 0, d)
-
-
-def smooth(gen, B, H, W, lo, hi, k=5):
-    g = torch.rand(B, 1, k, k, generator=gen)
-    f = torch.nn.functional.interpolate(g, size=(H, W), mode="bilinear", align_corners=True)
-    f = (f - f.amin((2, 3), keepdim=True)) / (f.amax((2, 3), keepdim=True) - f.amin((2, 3), keepdim=True)).clamp_min(1e-12)
-    return (lo + (hi - lo) * f).float().contiguous()
 
 
 def depths(B, H, W, seed, lo=0.05, hi=1.0):

@@ -4,13 +4,13 @@ import ctypes
 import glob
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import midas_restatement as rs
+from test_build_quality import disasm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "midas_*.npz")))
@@ -144,48 +144,19 @@ def test_workspace_bytes_rejects(built_lib, shape):
     assert load_library().dptx_midas_workspace_bytes(1, 8, 8, 4, None) == -1
 
 
-_asm = {}
-
-
-def midas_asm(tmp_path):
-    if not _asm:
-        from omnidata_amd.build import SOURCE_FLAGS
-        out = tmp_path / "midas_loss.s"
-        r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17"] +
-                           SOURCE_FLAGS.get("midas_loss.hip", []) +
-                           ["-S", "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "omnidata_amd", "csrc", "midas_loss.hip")],
-                           stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-        assert r.returncode == 0, r.stderr.decode()[-2000:]
-        _asm["s"] = out.read_text()
-    return _asm["s"]
-
-
 def test_midas_unit_built_without_packed_fp32():
     from omnidata_amd.build import SOURCE_FLAGS, SOURCES
     assert "midas_loss.hip" in SOURCES
     assert "-packed-fp32-ops" in SOURCE_FLAGS["midas_loss.hip"]
 
 
-def test_midas_no_scratch_no_spills(tmp_path):
-    s = midas_asm(tmp_path)
-    names = re.findall(r"^\s+\.name:\s+(\S+)", s, flags=re.M)
-    priv = re.findall(r"^\s+\.private_segment_fixed_size:\s+(\d+)", s, flags=re.M)
-    spills = re.findall(r"^\s+\.vgpr_spill_count:\s+(\d+)", s, flags=re.M)
-    assert len(names) >= 8 and len(priv) == len(names)
-    assert all(int(p) == 0 for p in priv), dict(zip(names, priv))
-    assert spills and all(int(p) == 0 for p in spills)
-    assert "scratch_" not in s
-    bad = [ln.strip() for ln in s.splitlines() if re.search(r"\bv_pk_\w+_f32\b", ln) and re.search(r"op_sel:\[[01,]*1", ln)]
-    assert not bad, bad[:3]
-
-
 def test_midas_no_float_atomics(tmp_path):
-    s = midas_asm(tmp_path)
+    s = disasm("midas_loss.hip", tmp_path)
     assert not re.search(r"\b(global|flat|buffer|ds)_atomic_\w*(add|pk_add)_f(32|64)\b", s)
 
 
 def test_entry_points_do_not_allocate_or_synchronise():
-    src = open(os.path.join(ROOT, "omnidata_amd", "csrc", "midas_loss.hip")).read()
+    src = "".join(open(os.path.join(ROOT, "omnidata_amd", "csrc", f)).read() for f in ("midas_loss.hip", "select.h"))
     code = re.sub(r"//[^\n]*", "", src)
     for word in ("hipMalloc", "hipFree", "hipMemcpy", "Synchronize", "hipEventQuery", "hipStreamQuery"):
         assert word not in code, word
