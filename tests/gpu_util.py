@@ -105,6 +105,11 @@ class PlaneArena:
         n = hi_view.numel()
         return (self.buf[0, o:o + n].double() + self.buf[1, o:o + n].double()).view(hi_view.shape)
 
+    def lo(self, hi_view):
+        """the lo plane of a tensor handed out by put()/empty(), as a view of the same shape."""
+        o = (hi_view.data_ptr() - self.buf.data_ptr()) // 2
+        return self.buf[1, o:o + hi_view.numel()].view(hi_view.shape)
+
     def release(self):
         load_library().dptx_op_set_planes(0, 0)
 
@@ -179,3 +184,109 @@ def per_row_err(got, ref):
     """max |got - ref| / max |ref| of every row of [M, N] tensors -> [M] (fp64)."""
     d = (got.double() - ref.double()).abs().amax(-1)
     return d / ref.double().abs().amax(-1).clamp_min(1e-30)
+
+
+# ------------------------------------------------------------------ attention, judged row by row
+# One error number per tensor (rel_err) lets the rows that average many keys -- outputs 10-30x smaller than those of rows that
+# look at one spiked key -- be wrong by tens of percent.  The helpers below give inputs in which every key counts, an fp64
+# reference with the quantities a per-element bound needs, and that bound.  Pure torch, any device.
+
+ATT_MODES = ("bf16", "fp16", "bf16x3", "fp16x3")
+ATT_FAMILIES = ("flat", "peaked", "lastkeys")
+ATT_SHAPES = ((2, 577, 12), (1, 505, 16), (1, 321, 16), (3, 129, 16), (1, 128, 12), (1, 193, 12), (3, 65, 12), (2, 17, 16),
+              (1, 2, 12), (1, 1, 12))
+ATT_PLANES = {"bf16": (torch.bfloat16, 1), "fp16": (torch.float16, 1), "bf16x3": (torch.bfloat16, 2), "fp16x3": (torch.float16, 2)}
+ATT_U = {"bf16": 2.0 ** -8, "fp16": 2.0 ** -11, "bf16x3": 2.0 ** -8, "fp16x3": 2.0 ** -11}
+# fp32 floor of the plane modes: the largest |err| / A of tests/test_attention_host.py's model with P and the output left in fp32
+# (no 16-bit rounding anywhere behind the operands), against attention_ref64, over ATT_SHAPES x ATT_FAMILIES x the two plane
+# modes on a CPU.  It was measured against the reference, never against the kernel; test_fp32_floor_is_what_the_bound_uses
+# re-measures it.
+ATT_F32_FLOOR_MEASURED = 5.9e-6
+ATT_F32_FLOOR_FACTOR = 4.0   # v_exp_f32 and the MFMA's accumulation order differ from torch's on the CPU
+
+
+def attention_inputs(B, S, H, family, seed=0):
+    """qkv [B, S, 3, H, 64] fp32 (CPU), deterministic in `seed`; b, h, s = image, head and token index.
+
+    flat      Q x 2^-3: the softmax is near uniform, so every key carries about 1 / S of the output.
+              V = 0.25 N(0, 1) + sign (1 + 0.25 ((h + b) % 5)), sign = +1 for even h + b, else -1: one key too many or too few
+              moves every output by ~|v| / S, and neighbouring heads and images differ in sign and size.
+    peaked    Q x 2^(0.5 ((5 h + 3 b) % 5)); V x vs + ((s + h) % 3 - 1) vs with vs = 2^((7 s + 3 h + b) % 9 - 4): every
+              (image, head) has a temperature and every key a value scale of its own.
+    lastkeys  K x (1 + 3 s / S), V + (s % 7 - 3): the running max grows in every tile and the last keys win.
+    All values fit fp16 (asserted)."""
+    g = torch.Generator().manual_seed(1000 + seed)
+    x = torch.randn(B, S, 3, H, 64, generator=g)
+    b = torch.arange(B).view(B, 1, 1, 1)
+    s = torch.arange(S).view(1, S, 1, 1)
+    h = torch.arange(H).view(1, 1, H, 1)
+    if family == "flat":
+        x[:, :, 0] *= 2.0 ** -3
+        sign = torch.where((h + b) % 2 == 0, 1.0, -1.0)
+        x[:, :, 2] = 0.25 * x[:, :, 2] + sign * (1.0 + 0.25 * ((h + b) % 5))
+    elif family == "peaked":
+        x[:, :, 0] *= torch.exp2(0.5 * ((5 * h + 3 * b) % 5))
+        vs = torch.exp2(((7 * s + 3 * h + b) % 9 - 4).float())
+        x[:, :, 2] = x[:, :, 2] * vs + ((s + h) % 3 - 1) * vs
+    elif family == "lastkeys":
+        x[:, :, 1] *= 1.0 + 3.0 * s / S
+        x[:, :, 2] += (s % 7 - 3).float()
+    else:
+        raise ValueError(family)
+    assert float(x.abs().max()) < 60000.0
+    return x.contiguous()
+
+
+def attention_ref64(x):
+    """fp64 attention of qkv values x [B, S, 3, H, 64] (the ROUNDED operands: hi + lo for the plane modes, PlaneArena.value).
+    Returns o, A, l, Vsum, each broadcastable to the output layout [B, S, H, 64]:
+      o    = softmax(Q K^T / 8) V
+      A    = softmax(Q K^T / 8) |V|            the scale of every rounding that is relative to a term of the sum
+      l    = 1 / max_j softmax  [B, S, H, 1]   the softmax denominator in the kernel's units (largest p = 1)
+      Vsum = sum_j |v_j|        [B, 1, H, 64]
+    Asserts max |logit log2 e| <= 64, which attention_row_bound's exponent-argument term assumes."""
+    x = x.double()
+    q, k, v = [t.permute(0, 2, 1, 3) for t in x.unbind(2)]          # [B, H, S, 64]
+    logit = (q @ k.transpose(-1, -2)) * 0.125
+    assert float(logit.abs().max()) * 1.4426950408889634 <= 64.0
+    p = logit.softmax(-1)
+    o = (p @ v).permute(0, 2, 1, 3)
+    A = (p @ v.abs()).permute(0, 2, 1, 3)
+    l = (1.0 / p.amax(-1, keepdim=True)).permute(0, 2, 1, 3)
+    Vsum = v.abs().sum(2, keepdim=True).permute(0, 2, 1, 3)
+    return o, A, l, Vsum
+
+
+def attention_row_bound(mode, A, l, Vsum):
+    """Elementwise bar on |out - o| of the attention kernel, u = 2^-8 (bf16) / 2^-11 (fp16) the unit roundoff.
+
+    bf16, fp16:      (2 u + 2^-17) A  [+ 2^-25 Vsum / l for fp16]
+        u A       P is rounded to 16 bit before the PV product
+        u A       the output is rounded to 16 bit (u |o| <= u A)
+        2^-17 A   fp32: the rounding of the exponent's argument, ln 2 * 3 * Lmax * 2^-24 with Lmax <= 64 (attention_ref64
+                  asserts it), and the accumulation
+        2^-25 Vsum / l   an fp16 P below 2^-14 is subnormal: absolute error 2^-25 per key, in the running scale, which never
+                  exceeds the final one (l)
+    bf16x3, fp16x3:  (3 u^2 + f32) A  [+ 2^-25 Vsum / l for fp16x3]
+        3 u^2     the hi / lo split of P, the dropped lo * lo products, the hi / lo split of the output
+        f32       4 x 5.9e-6 = 2.36e-5 (ATT_F32_FLOOR_FACTOR x ATT_F32_FLOOR_MEASURED): the fp32 floor depends on exp2 and on
+                  the accumulation order and has no tight derivation; 5.9e-6 is the largest |err| / A (5.81e-6, fp16x3 lastkeys
+                  2x577x12, rounded up) of the CPU model with nothing rounded to 16 bit behind the operands, against
+                  attention_ref64, over the whole test matrix -- measured against the reference, not against the kernel; the
+                  factor 4 is there because the GPU's v_exp_f32 and the MFMA's accumulation order differ from torch's on a
+                  CPU (profiles/attention_rows.md)."""
+    u = ATT_U[mode]
+    if ATT_PLANES[mode][1] == 1:
+        bound = (2.0 * u + 2.0 ** -17) * A
+    else:
+        bound = (3.0 * u * u + ATT_F32_FLOOR_FACTOR * ATT_F32_FLOOR_MEASURED) * A
+    if ATT_PLANES[mode][0] == torch.float16:
+        bound = bound + 2.0 ** -25 * Vsum / l
+    return bound
+
+
+def attention_planes(x, mode):
+    """(hi, lo) 16-bit planes of fp32 values x as PlaneArena.put splits them; lo is None for the single-plane modes."""
+    dt, pl = ATT_PLANES[mode]
+    hi = x.float().to(dt)
+    return hi, ((x.float() - hi.float()).to(dt) if pl == 2 else None)
