@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdptx.so")
-SOURCES = ["gemm.hip", "gemm_fp16.hip", "gemm_fp16e.hip", "gemm_x3.hip", "gemm_x2.hip", "gemm_fp8.hip", "attention.hip", "norm.hip", "misc.hip", "stem.hip", "head.hip", "prepost.hip", "refocus.hip", "midas_loss.hip", "vnl_loss.hip", "engine.hip"]
+SOURCES = ["gemm.hip", "gemm_fp16.hip", "gemm_fp16e.hip", "gemm_x3.hip", "gemm_x2.hip", "gemm_fp8.hip", "attention.hip", "norm.hip", "misc.hip", "stem.hip", "head.hip", "prepost.hip", "refocus.hip", "midas_loss.hip", "vnl_loss.hip", "engine.hip", "ops.hip"]
 HEADERS = ["common.h", "kernels.h", "gemm_impl.h", "select.h", os.path.join("..", "..", "include", "dptx.h")]
 # Per-source compiler flags.  Every kernel source except attention / stem / head / prepost is built WITHOUT packed fp32 arithmetic
 # (refocus.hip, midas_loss.hip, vnl_loss.hip: fp32 VALU code, built the same way from the start).

@@ -1,12 +1,13 @@
-// engine.hip -- libdptx.so host side: the C ABI of include/dptx.h, weight folding/packing, the
-// activation arena and the fixed kernel schedule of one DPT-Hybrid-384 forward.
+// engine.hip -- libdptx.so host side: the handle-based C ABI of include/dptx.h, the weight spec and its folding / packing,
+// the activation arena plan and the fixed kernel schedule of one forward (DPT-Hybrid-384 or DPT-Large-384).  The op-level
+// entry points (dptx_op_*), which touch no handle, live in ops.hip.
 //
 // Reference being replaced (paths under omnidata_tools/torch/modules/midas/):
-//   dpt_depth.py:67-85  DPT.forward          -> Engine::forward
-//   vit.py:119-155      forward_flex         -> stem / stages / tokens / 12 blocks
-//   vit.py:61-99        forward_vit          -> readout + reassemble (act_postprocess3/4)
-//   blocks.py:263-341   RCU / FeatureFusion  -> fusion()
-//   dpt_depth.py:91-99  head                 -> head convs + head_out
+//   dpt_depth.py:67-85  DPT.forward          -> Run::forward
+//   vit.py:119-155      forward_flex         -> stem / stages / tokens / 12 (24) blocks
+//   vit.py:61-99        forward_vit          -> the `readout` lambda: readout + reassemble (act_postprocess1..4)
+//   blocks.py:263-341   RCU / FeatureFusion  -> Run::rcu and the fusion loop of the `decode` lambda
+//   dpt_depth.py:91-99  head                 -> head convs + head tail / head_out (end of `decode`)
 // timm 0.4.12 vit_base_resnet50_384 (vit.py:483) is restated per SURVEY.md A.2.
 #include <hip/hip_runtime.h>
 
@@ -114,6 +115,14 @@ inline float e4m3_to_f32(uint8_t v) {
   return (float)((v & 0x80) ? -a : a);
 }
 
+// Power-of-two scale that puts a weight channel's max |w| into (224, 448] (e4m3 tops out at 448; 1 for an
+// all-zero channel); *inv receives its inverse, which the GEMM epilogue multiplies the channel's accumulators with
+inline float e4m3_channel_scale(float amax, float* inv) {
+  const float sc = std::ldexp(1.0f, amax > 0.f ? (int)std::floor(std::log2(448.0 / (double)amax)) : 0);
+  *inv = 1.0f / sc;
+  return sc;
+}
+
 // --------------------------------------------------------------------------- weight spec
 // R_DECONV: ConvTranspose2d [Cin, Cout, k, k] with kernel == stride, packed as the GEMM operand [(dy*k+dx)*Cout + co][ci];
 // R_DECONV_BIAS: its bias, tiled k*k times so that the GEMM epilogue can add it per column
@@ -128,15 +137,25 @@ struct Spec {
 
 void add(std::vector<Spec>& v, const std::string& k, std::vector<int64_t> s, Role r) { v.push_back({k, std::move(s), r}); }
 
-// Mirrors omnidata_amd/weights.py:state_dict_spec (reference key names, SURVEY.md A.3).
-// `dual`: a second decoder (depth, 1 channel) under "depth.scratch.*" next to the normal one (3 channels) under
-// "scratch.*"; both read the one shared encoder "pretrained.*" (SURVEY.md 8d config 5).
-// backbone 0: vitb_rn50_384 (DPT-Hybrid); 1: vitl16_384 (DPT-Large, SURVEY.md 8f row 3; omnidata_amd/weights.py
-// vitl16_state_dict_spec)
-// fp8 dtype, DPTX_FLAG_FP8_VIT (round 6): per-output-channel inverse scales of the e4m3 copies of qkv / fc1 / fc2 of one block, and
-// the column sums of the DEQUANTISED folded e4m3 weights (the LayerNorm fold's mean term must cancel against what the MFMA
-// actually multiplies)
-void add_vit_fp8(std::vector<Spec>& v, const std::string& p, int D_VIT, int D_MLP) {
+// One timm Block under prefix p: its 12 state-dict entries, then the entries derived at pack time -- the LayerNorm fold's
+// column sums and, for the fp8 dtype (DPTX_FLAG_FP8_VIT, round 6), the per-output-channel inverse scales of the e4m3 copies of
+// qkv / fc1 / fc2 and the column sums of the DEQUANTISED folded e4m3 weights (the fold's mean term must cancel against what
+// the MFMA actually multiplies)
+void add_vit_block(std::vector<Spec>& v, const std::string& p, int D_VIT, int D_MLP) {
+  add(v, p + "norm1.weight", {D_VIT}, R_VEC);
+  add(v, p + "norm1.bias", {D_VIT}, R_VEC);
+  add(v, p + "attn.qkv.weight", {3 * D_VIT, D_VIT}, R_LINEAR);
+  add(v, p + "attn.qkv.bias", {3 * D_VIT}, R_VEC);
+  add(v, p + "attn.proj.weight", {D_VIT, D_VIT}, R_LINEAR);
+  add(v, p + "attn.proj.bias", {D_VIT}, R_VEC);
+  add(v, p + "norm2.weight", {D_VIT}, R_VEC);
+  add(v, p + "norm2.bias", {D_VIT}, R_VEC);
+  add(v, p + "mlp.fc1.weight", {D_MLP, D_VIT}, R_LINEAR);
+  add(v, p + "mlp.fc1.bias", {D_MLP}, R_VEC);
+  add(v, p + "mlp.fc2.weight", {D_VIT, D_MLP}, R_LINEAR);
+  add(v, p + "mlp.fc2.bias", {D_VIT}, R_VEC);
+  add(v, p + "attn.qkv.lnsum", {3 * D_VIT}, R_DERIVED);
+  add(v, p + "mlp.fc1.lnsum", {D_MLP}, R_DERIVED);
   add(v, p + "attn.qkv.f8scale", {3 * D_VIT}, R_DERIVED);
   add(v, p + "mlp.fc1.f8scale", {D_MLP}, R_DERIVED);
   add(v, p + "mlp.fc2.f8scale", {D_VIT}, R_DERIVED);
@@ -144,114 +163,76 @@ void add_vit_fp8(std::vector<Spec>& v, const std::string& p, int D_VIT, int D_ML
   add(v, p + "mlp.fc1.lnsum8", {D_MLP}, R_DERIVED);
 }
 
+// pretrained.act_postprocess<n>: ProjectReadout, the 1x1 conv to f channels and the resampling layer "4" -- a ConvTranspose2d
+// with kernel == stride == deconv_k, or (conv3) the 3x3 stride-2 convolution, or neither
+void add_readout(std::vector<Spec>& v, int n, int D_VIT, int f, int deconv_k, bool conv3) {
+  const std::string p = "pretrained.act_postprocess" + std::to_string(n) + ".";
+  add(v, p + "0.project.0.weight", {D_VIT, 2 * D_VIT}, R_LINEAR);
+  add(v, p + "0.project.0.bias", {D_VIT}, R_VEC);
+  add(v, p + "3.weight", {f, D_VIT, 1, 1}, R_CONV);
+  add(v, p + "3.bias", {f}, R_VEC);
+  if (deconv_k) { add(v, p + "4.weight", {f, f, deconv_k, deconv_k}, R_DECONV); add(v, p + "4.bias", {f}, R_DECONV_BIAS); }
+  if (conv3) { add(v, p + "4.weight", {f, f, 3, 3}, R_CONV); add(v, p + "4.bias", {f}, R_VEC); }
+}
+
+// Mirrors omnidata_amd/weights.py:state_dict_spec (reference key names, SURVEY.md A.3).
+// `dual`: a second decoder (depth, 1 channel) under "depth.scratch.*" next to the normal one (3 channels) under
+// "scratch.*"; both read the one shared encoder "pretrained.*" (SURVEY.md 8d config 5).
+// backbone 0: vitb_rn50_384 (DPT-Hybrid); 1: vitl16_384 (DPT-Large, SURVEY.md 8f row 3; omnidata_amd/weights.py
+// vitl16_state_dict_spec)
 std::vector<Spec> build_spec(int C, bool dual, int backbone) {
   std::vector<Spec> v;
   const std::string vp = "pretrained.model.";
   const int D_VIT = backbone == 1 ? 1024 : 768, D_MLP = 4 * D_VIT, depth = backbone == 1 ? 24 : 12;
-  if (backbone == 1) {
-    add(v, vp + "cls_token", {1, 1, D_VIT}, R_VEC);
-    add(v, vp + "pos_embed", {1, S_TOK, D_VIT}, R_VEC);
-    add(v, vp + "patch_embed.proj.weight", {D_VIT, 3, 16, 16}, R_LINEAR);  // flattened (c, ky, kx) = the patch matrix's k order
-    add(v, vp + "patch_embed.proj.bias", {D_VIT}, R_VEC);
-    for (int l = 0; l < depth; ++l) {
-      const std::string p = vp + "blocks." + std::to_string(l) + ".";
-      add(v, p + "norm1.weight", {D_VIT}, R_VEC);
-      add(v, p + "norm1.bias", {D_VIT}, R_VEC);
-      add(v, p + "attn.qkv.weight", {3 * D_VIT, D_VIT}, R_LINEAR);
-      add(v, p + "attn.qkv.bias", {3 * D_VIT}, R_VEC);
-      add(v, p + "attn.proj.weight", {D_VIT, D_VIT}, R_LINEAR);
-      add(v, p + "attn.proj.bias", {D_VIT}, R_VEC);
-      add(v, p + "norm2.weight", {D_VIT}, R_VEC);
-      add(v, p + "norm2.bias", {D_VIT}, R_VEC);
-      add(v, p + "mlp.fc1.weight", {D_MLP, D_VIT}, R_LINEAR);
-      add(v, p + "mlp.fc1.bias", {D_MLP}, R_VEC);
-      add(v, p + "mlp.fc2.weight", {D_VIT, D_MLP}, R_LINEAR);
-      add(v, p + "mlp.fc2.bias", {D_VIT}, R_VEC);
-      add(v, p + "attn.qkv.lnsum", {3 * D_VIT}, R_DERIVED);
-      add(v, p + "mlp.fc1.lnsum", {D_MLP}, R_DERIVED);
-      add_vit_fp8(v, p, D_VIT, D_MLP);
-    }
-    add(v, vp + "norm.weight", {D_VIT}, R_UNUSED);
-    add(v, vp + "norm.bias", {D_VIT}, R_UNUSED);
-    add(v, vp + "head.weight", {1000, D_VIT}, R_UNUSED);
-    add(v, vp + "head.bias", {1000}, R_UNUSED);
-    const int feats[4] = {256, 512, 1024, 1024};
-    for (int n = 1; n <= 4; ++n) {
-      const std::string p = "pretrained.act_postprocess" + std::to_string(n) + ".";
-      const int f = feats[n - 1];
-      add(v, p + "0.project.0.weight", {D_VIT, 2 * D_VIT}, R_LINEAR);
-      add(v, p + "0.project.0.bias", {D_VIT}, R_VEC);
-      add(v, p + "3.weight", {f, D_VIT, 1, 1}, R_CONV);
-      add(v, p + "3.bias", {f}, R_VEC);
-      if (n == 1) { add(v, p + "4.weight", {f, f, 4, 4}, R_DECONV); add(v, p + "4.bias", {f}, R_DECONV_BIAS); }
-      if (n == 2) { add(v, p + "4.weight", {f, f, 2, 2}, R_DECONV); add(v, p + "4.bias", {f}, R_DECONV_BIAS); }
-      if (n == 4) { add(v, p + "4.weight", {f, f, 3, 3}, R_CONV); add(v, p + "4.bias", {f}, R_VEC); }
-    }
-  } else {
   add(v, vp + "cls_token", {1, 1, D_VIT}, R_VEC);
   add(v, vp + "pos_embed", {1, S_TOK, D_VIT}, R_VEC);
-  const std::string bp = vp + "patch_embed.backbone.";
-  add(v, bp + "stem.conv.weight", {64, 3, 7, 7}, R_STDCONV);
-  add(v, bp + "stem.norm.weight", {64}, R_VEC);
-  add(v, bp + "stem.norm.bias", {64}, R_VEC);
-  int cin = 64;
-  for (int s = 0; s < 3; ++s) {
-    const int cout = STAGE_OUT[s], mid = cout / 4;
-    for (int b = 0; b < STAGE_DEPTH[s]; ++b) {
-      const std::string p = bp + "stages." + std::to_string(s) + ".blocks." + std::to_string(b) + ".";
-      if (b == 0) {
-        add(v, p + "downsample.conv.weight", {cout, cin, 1, 1}, R_STDCONV);
-        add(v, p + "downsample.norm.weight", {cout}, R_VEC);
-        add(v, p + "downsample.norm.bias", {cout}, R_VEC);
+  if (backbone == 1) {
+    add(v, vp + "patch_embed.proj.weight", {D_VIT, 3, 16, 16}, R_LINEAR);  // flattened (c, ky, kx) = the patch matrix's k order
+    add(v, vp + "patch_embed.proj.bias", {D_VIT}, R_VEC);
+  } else {
+    const std::string bp = vp + "patch_embed.backbone.";
+    add(v, bp + "stem.conv.weight", {64, 3, 7, 7}, R_STDCONV);
+    add(v, bp + "stem.norm.weight", {64}, R_VEC);
+    add(v, bp + "stem.norm.bias", {64}, R_VEC);
+    int cin = 64;
+    for (int s = 0; s < 3; ++s) {
+      const int cout = STAGE_OUT[s], mid = cout / 4;
+      for (int b = 0; b < STAGE_DEPTH[s]; ++b) {
+        const std::string p = bp + "stages." + std::to_string(s) + ".blocks." + std::to_string(b) + ".";
+        if (b == 0) {
+          add(v, p + "downsample.conv.weight", {cout, cin, 1, 1}, R_STDCONV);
+          add(v, p + "downsample.norm.weight", {cout}, R_VEC);
+          add(v, p + "downsample.norm.bias", {cout}, R_VEC);
+        }
+        add(v, p + "conv1.weight", {mid, cin, 1, 1}, R_STDCONV);
+        add(v, p + "norm1.weight", {mid}, R_VEC);
+        add(v, p + "norm1.bias", {mid}, R_VEC);
+        add(v, p + "conv2.weight", {mid, mid, 3, 3}, R_STDCONV);
+        add(v, p + "norm2.weight", {mid}, R_VEC);
+        add(v, p + "norm2.bias", {mid}, R_VEC);
+        add(v, p + "conv3.weight", {cout, mid, 1, 1}, R_STDCONV);
+        add(v, p + "norm3.weight", {cout}, R_VEC);
+        add(v, p + "norm3.bias", {cout}, R_VEC);
+        cin = cout;
       }
-      add(v, p + "conv1.weight", {mid, cin, 1, 1}, R_STDCONV);
-      add(v, p + "norm1.weight", {mid}, R_VEC);
-      add(v, p + "norm1.bias", {mid}, R_VEC);
-      add(v, p + "conv2.weight", {mid, mid, 3, 3}, R_STDCONV);
-      add(v, p + "norm2.weight", {mid}, R_VEC);
-      add(v, p + "norm2.bias", {mid}, R_VEC);
-      add(v, p + "conv3.weight", {cout, mid, 1, 1}, R_STDCONV);
-      add(v, p + "norm3.weight", {cout}, R_VEC);
-      add(v, p + "norm3.bias", {cout}, R_VEC);
-      cin = cout;
     }
+    add(v, vp + "patch_embed.proj.weight", {D_VIT, 1024, 1, 1}, R_CONV);
+    add(v, vp + "patch_embed.proj.bias", {D_VIT}, R_VEC);
   }
-  add(v, vp + "patch_embed.proj.weight", {D_VIT, 1024, 1, 1}, R_CONV);
-  add(v, vp + "patch_embed.proj.bias", {D_VIT}, R_VEC);
-  for (int l = 0; l < depth; ++l) {
-    const std::string p = vp + "blocks." + std::to_string(l) + ".";
-    add(v, p + "norm1.weight", {D_VIT}, R_VEC);
-    add(v, p + "norm1.bias", {D_VIT}, R_VEC);
-    add(v, p + "attn.qkv.weight", {3 * D_VIT, D_VIT}, R_LINEAR);
-    add(v, p + "attn.qkv.bias", {3 * D_VIT}, R_VEC);
-    add(v, p + "attn.proj.weight", {D_VIT, D_VIT}, R_LINEAR);
-    add(v, p + "attn.proj.bias", {D_VIT}, R_VEC);
-    add(v, p + "norm2.weight", {D_VIT}, R_VEC);
-    add(v, p + "norm2.bias", {D_VIT}, R_VEC);
-    add(v, p + "mlp.fc1.weight", {D_MLP, D_VIT}, R_LINEAR);
-    add(v, p + "mlp.fc1.bias", {D_MLP}, R_VEC);
-    add(v, p + "mlp.fc2.weight", {D_VIT, D_MLP}, R_LINEAR);
-    add(v, p + "mlp.fc2.bias", {D_VIT}, R_VEC);
-    add(v, p + "attn.qkv.lnsum", {3 * D_VIT}, R_DERIVED);
-    add(v, p + "mlp.fc1.lnsum", {D_MLP}, R_DERIVED);
-    add_vit_fp8(v, p, D_VIT, D_MLP);
-  }
+  for (int l = 0; l < depth; ++l) add_vit_block(v, vp + "blocks." + std::to_string(l) + ".", D_VIT, D_MLP);
   add(v, vp + "norm.weight", {D_VIT}, R_UNUSED);
   add(v, vp + "norm.bias", {D_VIT}, R_UNUSED);
   add(v, vp + "head.weight", {1000, D_VIT}, R_UNUSED);
   add(v, vp + "head.bias", {1000}, R_UNUSED);
-  for (int n = 3; n <= 4; ++n) {
-    const std::string p = "pretrained.act_postprocess" + std::to_string(n) + ".";
-    add(v, p + "0.project.0.weight", {D_VIT, 2 * D_VIT}, R_LINEAR);
-    add(v, p + "0.project.0.bias", {D_VIT}, R_VEC);
-    add(v, p + "3.weight", {D_VIT, D_VIT, 1, 1}, R_CONV);
-    add(v, p + "3.bias", {D_VIT}, R_VEC);
-    if (n == 4) {
-      add(v, p + "4.weight", {D_VIT, D_VIT, 3, 3}, R_CONV);
-      add(v, p + "4.bias", {D_VIT}, R_VEC);
-    }
+  if (backbone == 1) {
+    add_readout(v, 1, D_VIT, 256, 4, false);
+    add_readout(v, 2, D_VIT, 512, 2, false);
+    add_readout(v, 3, D_VIT, 1024, 0, false);
+    add_readout(v, 4, D_VIT, 1024, 0, true);
+  } else {
+    add_readout(v, 3, D_VIT, D_VIT, 0, false);
+    add_readout(v, 4, D_VIT, D_VIT, 0, true);
   }
-  }  // backbone
   // "<conv>.f8scale": per-output-channel inverse of the power-of-two scale the e4m3 copy of the weight was quantised with
   // (fp8 dtype; derived at pack time, zero otherwise)
   auto decoder = [&](const std::string& pre, int ch) {
@@ -327,6 +308,11 @@ struct Buf {  // arena slice: `off` in the whole-batch plan, `off2` in the half-
   size_t off = 0, bytes = 0, off2 = 0;
 };
 
+inline bool ends_with(const std::string& k, const char* suf) {
+  const size_t n = strlen(suf);
+  return k.size() >= n && k.compare(k.size() - n, n, suf) == 0;
+}
+
 struct TapInfo {
   const void* ptr;
   int64_t shape[4];
@@ -398,7 +384,7 @@ struct dptx_engine {
   // convolutions that CAN run on e4m3 operands in the fp8 dtype (their weights get an e4m3 copy at pack time): the decoder's
   // RCU convs, out_conv and the first head conv ...
   static bool fp8_weight(const std::string& key) {
-    return key.find("scratch.") != std::string::npos && key.size() > 7 && key.compare(key.size() - 7, 7, ".weight") == 0 &&
+    return key.find("scratch.") != std::string::npos && key.size() > 7 && ends_with(key, ".weight") &&
            (key.find("resConfUnit") != std::string::npos || key.find("out_conv") != std::string::npos ||
             key.find("output_conv.0.") != std::string::npos);
   }
@@ -414,9 +400,8 @@ struct dptx_engine {
   // convolutions cost -- not the "destroyed output" that rounds 3-5 assumed.
   bool fp8_vit = false;
   static bool fp8_vit_weight(const std::string& key) {
-    auto ends = [&](const char* suf) { const size_t n = strlen(suf); return key.size() >= n && key.compare(key.size() - n, n, suf) == 0; };
     return key.find("pretrained.model.blocks.") != std::string::npos &&
-           (ends("attn.qkv.weight") || ends("mlp.fc1.weight") || ends("mlp.fc2.weight"));
+           (ends_with(key, "attn.qkv.weight") || ends_with(key, "mlp.fc1.weight") || ends_with(key, "mlp.fc2.weight"));
   }
   bool fp8_use(const std::string& key) const {
     if (!fp8()) return false;
@@ -480,6 +465,9 @@ struct dptx_engine {
   Buf pos_alt;
   Buf sraw, stem, S[3], T1, T2, PA, PB, DS, part[4], X, Hn, QKV, AO, F1, R3, R4, L3, T4, L4, clsb, lrn[4], tA, tB,
       tC, P[4], H0, H0U, H1, lnst;
+  // every buffer of the plan with its name, in plan order (recorded by plan_arena_for: what it takes is what
+  // dptx_debug_arena_layout lists and dptx_debug_arena_checksums sums)
+  std::vector<std::pair<std::string, const Buf*>> arena_bufs;
 
   int fail(int code, const std::string& m) {
     err = m;
@@ -523,53 +511,56 @@ struct DeviceGuard {
   } while (0)
 
 // Bump-allocates every activation buffer for Bn images; half = false fills Buf::off (one run over the whole batch),
-// half = true fills Buf::off2 (layout of ONE of the two half-batch regions).  Returns the bytes used.
+// half = true fills Buf::off2 (layout of ONE of the two half-batch regions).  The whole-batch pass also records every buffer
+// it takes, by name, in dptx_engine::arena_bufs.  Returns the bytes used.
 size_t plan_arena_for(dptx_engine* e, size_t B, bool half) {
   // every buffer scales with the pixel count of the largest supported input (H, W multiples of 32); P = H*W
   const size_t P = (size_t)e->max_h * e->max_w;
   const size_t p2 = P / 4, p4 = P / 16, p8 = P / 64, p16 = P / 256, p32 = P / 1024, S = p16 + 1;
   const size_t DV = (size_t)e->dv;
   size_t off = 0;
-  auto take = [&](Buf& b, size_t elems, size_t esz) {
+  if (!half) e->arena_bufs.clear();
+  auto take = [&](const std::string& name, Buf& b, size_t elems, size_t esz) {
     const size_t bytes = align_up(elems * esz, 256);
-    if (half) b.off2 = off; else { b.off = off; b.bytes = bytes; }
+    if (half) b.off2 = off; else { b.off = off; b.bytes = bytes; e->arena_bufs.push_back({name, &b}); }
     off += bytes;
   };
-  take(e->sraw, B * p2 * 64, 2);
-  take(e->stem, B * p4 * 64, 2);
-  take(e->S[0], B * p4 * 256, 2);
-  take(e->S[1], B * p8 * 512, 2);
-  take(e->S[2], B * p16 * 1024, 2);
-  take(e->T1, B * p4 * 128, 2);  // largest conv1 output: stage1 block0 (128 ch @ 1/4 resolution)
-  take(e->T2, B * p4 * 64, 2);   // largest conv2 output: stage0 (64 ch @ 1/4 resolution)
-  take(e->PA, B * p4 * 256, 2);
-  take(e->PB, B * p4 * 256, 2);
-  take(e->DS, B * p4 * 256, 2);
+  auto idx = [](const char* name, int i) { return name + std::to_string(i); };
+  take("sraw", e->sraw, B * p2 * 64, 2);
+  take("stem", e->stem, B * p4 * 64, 2);
+  take("S0", e->S[0], B * p4 * 256, 2);
+  take("S1", e->S[1], B * p8 * 512, 2);
+  take("S2", e->S[2], B * p16 * 1024, 2);
+  take("T1", e->T1, B * p4 * 128, 2);  // largest conv1 output: stage1 block0 (128 ch @ 1/4 resolution)
+  take("T2", e->T2, B * p4 * 64, 2);   // largest conv2 output: stage0 (64 ch @ 1/4 resolution)
+  take("PA", e->PA, B * p4 * 256, 2);
+  take("PB", e->PB, B * p4 * 256, 2);
+  take("DS", e->DS, B * p4 * 256, 2);
   // GroupNorm partial records (32 groups x float2): p2/256 chunks for the stem, p4/32 MFMA row blocks for a stage conv
-  for (int i = 0; i < 4; ++i) take(e->part[i], B * (std::max(p2 / 256, p4 / 32) + 64) * 64, 4);
-  take(e->X, B * S * DV, 4);
-  take(e->lnst, B * S * 8 * 2, 4);  // LayerNorm fold: (sum, sum of squares) per token row and 128-column block (<= 8 blocks)
-  take(e->Hn, B * S * DV, 2);
-  take(e->QKV, B * S * 3 * DV, 2);
-  take(e->AO, B * S * DV, 2);
-  take(e->F1, B * S * (size_t)e->dm, 2);
-  take(e->R3, B * p16 * DV, 2);
-  take(e->R4, B * p16 * DV, 2);
-  take(e->L3, B * p16 * DV, 2);
-  take(e->T4, B * p16 * DV, 2);
-  take(e->L4, B * p32 * DV, 2);
-  take(e->clsb, B * DV, 4);
-  take(e->pos_alt, S * DV, 4);  // bilinearly resized pos_embed for inputs other than 384x384
+  for (int i = 0; i < 4; ++i) take(idx("part", i), e->part[i], B * (std::max(p2 / 256, p4 / 32) + 64) * 64, 4);
+  take("X", e->X, B * S * DV, 4);
+  take("lnst", e->lnst, B * S * 8 * 2, 4);  // LayerNorm fold: (sum, sum of squares) per token row and 128-column block (<= 8 blocks)
+  take("Hn", e->Hn, B * S * DV, 2);
+  take("QKV", e->QKV, B * S * 3 * DV, 2);
+  take("AO", e->AO, B * S * DV, 2);
+  take("F1", e->F1, B * S * (size_t)e->dm, 2);
+  take("R3", e->R3, B * p16 * DV, 2);
+  take("R4", e->R4, B * p16 * DV, 2);
+  take("L3", e->L3, B * p16 * DV, 2);
+  take("T4", e->T4, B * p16 * DV, 2);
+  take("L4", e->L4, B * p32 * DV, 2);
+  take("clsb", e->clsb, B * DV, 4);
+  take("pos_alt", e->pos_alt, S * DV, 4);  // bilinearly resized pos_embed for inputs other than 384x384
   const size_t rn_px[4] = {p4, p8, p16, p32};
-  for (int i = 0; i < 4; ++i) take(e->lrn[i], B * rn_px[i] * FEAT, 2);
-  take(e->tA, B * p4 * FEAT, 2);
-  take(e->tB, B * p4 * FEAT, 2);
-  take(e->tC, B * p4 * FEAT, 2);
+  for (int i = 0; i < 4; ++i) take(idx("lrn", i), e->lrn[i], B * rn_px[i] * FEAT, 2);
+  take("tA", e->tA, B * p4 * FEAT, 2);
+  take("tB", e->tB, B * p4 * FEAT, 2);
+  take("tC", e->tC, B * p4 * FEAT, 2);
   const size_t p_px[4] = {p2, p4, p8, p16};  // P[0]=path_1 (1/2 res) ... P[3]=path_4 (1/16 res)
-  for (int i = 0; i < 4; ++i) take(e->P[i], B * p_px[i] * FEAT, 2);
-  take(e->H0, B * p2 * 128, 2);
-  take(e->H0U, B * P * 128, 2);
-  take(e->H1, B * P * 32, 2);
+  for (int i = 0; i < 4; ++i) take(idx("P", i), e->P[i], B * p_px[i] * FEAT, 2);
+  take("H0", e->H0, B * p2 * 128, 2);
+  take("H0U", e->H0U, B * P * 128, 2);
+  take("H1", e->H1, B * P * 32, 2);
   return off;
 }
 
@@ -614,10 +605,6 @@ int pack_host(dptx_engine* e) {
   };
   // value the MFMA sees for a packed single-plane operand element
   auto r16 = [&](float x) { return bf ? bf16_to_f32(f32_to_bf16(x)) : fp16_to_f32(f32_to_fp16(x)); };
-  auto ends_with = [](const std::string& k, const char* suf) {
-    const size_t n = strlen(suf);
-    return k.size() >= n && k.compare(k.size() - n, n, suf) == 0;
-  };
   for (const auto& s : e->spec) {
     if (s.role == R_UNUSED || s.role == R_DERIVED) continue;
     const std::vector<float>& src = e->staged.at(s.key);
@@ -708,9 +695,8 @@ int pack_host(dptx_engine* e) {
   }
   if (e->fp8()) {
     // e4m3 copies of the fp8 layers' weights (same [O][kh][kw][I] order as the bf16 copy, one byte per element, second
-    // plane of the blob), quantised per OUTPUT CHANNEL after a power-of-two scale that puts the channel's max |w| into
-    // (224, 448] (e4m3 tops out at 448); the inverses go to the layer's "f8scale" vector, which the
-    // GEMM epilogue multiplies the accumulators with.
+    // plane of the blob), quantised per OUTPUT CHANNEL after e4m3_channel_scale; the inverses go to the layer's "f8scale"
+    // vector.
     for (size_t si = 0; si < e->spec.size(); ++si) {
       const Spec& sp = e->spec[si];
       if (sp.role != R_CONV || !dptx_engine::fp8_weight(sp.key)) continue;
@@ -723,13 +709,11 @@ int pack_host(dptx_engine* e) {
       for (int o = 0; o < O; ++o) {
         float mx = 0.f;
         for (size_t i = 0; i < per_o; ++i) mx = std::max(mx, std::fabs(src[(size_t)o * per_o + i]));
-        const int k = mx > 0.f ? (int)std::floor(std::log2(448.0 / (double)mx)) : 0;
-        const float sc = std::ldexp(1.0f, k);
+        const float sc = e4m3_channel_scale(mx, &inv[o]);
         for (int ky = 0; ky < KH; ++ky)
           for (int kx = 0; kx < KW; ++kx)
             for (int i = 0; i < I; ++i)
               d8[(size_t)o * per_o + ((size_t)ky * KW + kx) * I + i] = f32_to_e4m3(src[(((size_t)o * I + i) * KH + ky) * KW + kx] * sc);
-        inv[o] = 1.0f / sc;
       }
     }
   }
@@ -752,15 +736,13 @@ int pack_host(dptx_engine* e) {
       for (size_t n = 0; n < N; ++n) {
         float mx = 0.f;
         for (size_t k = 0; k < K; ++k) mx = std::max(mx, std::fabs(W[n * K + k] * (gamma ? (*gamma)[k] : 1.0f)));
-        const int sh = mx > 0.f ? (int)std::floor(std::log2(448.0 / (double)mx)) : 0;
-        const float sc = std::ldexp(1.0f, sh);
+        const float sc = e4m3_channel_scale(mx, &inv[n]);
         double acc = 0.0;
         for (size_t k = 0; k < K; ++k) {
           const uint8_t q = f32_to_e4m3(W[n * K + k] * (gamma ? (*gamma)[k] : 1.0f) * sc);
           d8[n * K + k] = q;
           acc += (double)e4m3_to_f32(q);
         }
-        inv[n] = 1.0f / sc;
         if (cs8) cs8[n] = (float)(acc / (double)sc);
       }
     }
@@ -770,6 +752,42 @@ int pack_host(dptx_engine* e) {
 }
 
 // ------------------------------------------------------------------------------ schedule
+// What one GEMM of the schedule does besides the plain product (Run::conv, Run::rcu and the `dense` lambda of Run::forward).
+// Every call names what it sets: GemmOpt().bias(b).act(1)
+enum { LN_NONE = 0, LN_CONSUMER = 1, LN_PRODUCER = 2 };
+struct GemmOpt {
+  const float* bias_ = nullptr;
+  int act_ = 0, a_relu_ = 0;                  // GemmParams::act / a_relu
+  const void *R1_ = nullptr, *R2_ = nullptr;  // residuals
+  // fp8 dtype: the epilogue also writes the e4m3 copy of the output, for a consumer that multiplies on e4m3 operands (one
+  // calibrated power-of-two scale per tensor); 2 (conv): ReLU'd, for consumers that pre-activate
+  int q_ = 0;
+  // conv: != nullptr: the epilogue also writes the GroupNorm(32) statistics of the output (per 32-row block records,
+  // kernels.h GemmParams::gn_part); the caller checked gn_fusable(Hout * Wout)
+  float* gn_part_ = nullptr;
+  // conv, MIXED dtype, decoder groups only (-1 elsewhere): 1 = some consumer multiplies this tensor with 3 MFMAs and needs
+  // its lo plane, 0 = nobody reads it.  The layer's own arithmetic follows dptx_engine::layer_x3.
+  int out_lo_ = -1;
+  int c_fp32_ = 0, r1_fp32_ = 0;  // dense: C / R1 is the fp32 token stream
+  // dense: the layer's part in the folded LayerNorm -- consumer (qkv, fc1: normalises in the epilogue, with the column sums
+  // `colsum` of its folded weight; only a consumer reads them) or producer (proj, fc2: 16-bit copy + row statistics of the
+  // stream it writes)
+  int ln_ = LN_NONE;
+  const float* colsum_ = nullptr;
+  GemmOpt& bias(const float* v) { bias_ = v; return *this; }
+  GemmOpt& act(int v) { act_ = v; return *this; }
+  GemmOpt& a_relu(int v) { a_relu_ = v; return *this; }
+  GemmOpt& R1(const void* v) { R1_ = v; return *this; }
+  GemmOpt& R2(const void* v) { R2_ = v; return *this; }
+  GemmOpt& q(int v) { q_ = v; return *this; }
+  GemmOpt& gn_part(float* v) { gn_part_ = v; return *this; }
+  GemmOpt& out_lo(int v) { out_lo_ = v; return *this; }
+  GemmOpt& c_fp32(int v) { c_fp32_ = v; return *this; }
+  GemmOpt& r1_fp32(int v) { r1_fp32_ = v; return *this; }
+  GemmOpt& ln(int v) { ln_ = v; return *this; }
+  GemmOpt& colsum(const float* v) { colsum_ = v; return *this; }
+};
+
 struct Run {
   dptx_engine* e;
   int B;
@@ -840,54 +858,43 @@ struct Run {
   void group(int g) { dt = e->mode_of(g); cur_group = g; }  // the launches that follow belong to layer group g
 
   // NHWC convolution as implicit GEMM
-  // gn_part != nullptr: the epilogue also writes the GroupNorm(32) statistics of the output (per 32-row block records,
-  // kernels.h GemmParams::gn_part); the caller checked gn_fusable(Hout * Wout)
-  // out_lo (MIXED dtype, decoder groups only; -1 elsewhere): 1 = some consumer multiplies this tensor with 3 MFMAs and needs
-  // its lo plane, 0 = nobody reads it.  The layer's own arithmetic follows dptx_engine::layer_x3.
   void conv(const void* in, int Hin, int Win, int Cin, const std::string& wkey, int ksz, int stride, int pad_t, int pad_l,
-            int Hout, int Wout, int Cout, void* out, const float* bias, int act, int a_relu, const void* R1 = nullptr,
-            const void* R2 = nullptr, float* gn_part = nullptr, int q = 0, int out_lo = -1) {
-    // fp8 dtype: q = 1 / 2 also writes the e4m3 copy of the output (2: ReLU'd, for consumers that pre-activate); a conv
-    // whose weight has an e4m3 copy runs on the fp8 MFMA, reading the e4m3 copy of `in` (ReLU'd by its producer)
+            int Hout, int Wout, int Cout, void* out, const GemmOpt& o = GemmOpt()) {
+    // fp8 dtype: a conv whose weight has an e4m3 copy runs on the fp8 MFMA, reading the e4m3 copy of `in` (ReLU'd by its
+    // producer)
     // (a calibration forward runs these convs on their bf16 operands: a saturated e4m3 copy upstream must not distort the
     // max |x| measured downstream)
     const bool f8 = e->fp8_use(wkey) && !e->calibrating;
-    GemmParams p{};
-    p.A = in; p.W = e->w(wkey); p.C = out; p.bias = bias; p.R1 = R1; p.R2 = R2;
+    GemmParams p;
+    gemm_params_conv(p, B, Hin, Win, Cin, Cout, ksz, stride, pad_t, pad_l, Hout, Wout, f8 ? 1 : 2);
+    p.A = in; p.W = e->w(wkey); p.C = out; p.bias = o.bias_; p.R1 = o.R1_; p.R2 = o.R2_;
     int slot = -1;
-    if (e->fp8() && q) {
+    if (e->fp8() && o.q_) {
       slot = q8_produce(out);
-      p.C8 = e->q8(out); p.q_relu = q == 2; p.q_scale = e->act_scale[slot];
+      p.C8 = e->q8(out); p.q_relu = o.q_ == 2; p.q_scale = e->act_scale[slot];
     }
-    p.M = B * Hout * Wout; p.N = Cout; p.K = ksz * ksz * Cin; p.ldw = p.K;
-    p.a_rpi = Hout * Wout; p.Wout = Wout; p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.a_pix_stride = Cin;
-    p.a_img_stride = (long long)Hin * Win * Cin; p.a_off = 0;
-    p.a_bytes = (long long)B * Hin * Win * Cin * 2;
-    p.ksz = ksz; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-    p.c_rpi = 0x7fffffff; p.c_img_rows = 0; p.c_row_off = 0; p.ldc = Cout;
-    p.act = act; p.a_relu = a_relu; p.planes = e->pl;
-    p.k_tap_fast = (ksz == 3 && Cin >= 512) ? 1 : 0;  // measured per layer: profiles/r01_experiments.md
-    if (gn_part) { p.gn_part = gn_part; p.gn_hw = Hout * Wout; p.gn_blocks = Hout * Wout / 32; p.gn_cpg = Cout / 32; }
+    p.act = o.act_; p.a_relu = o.a_relu_; p.planes = e->pl;
+    if (o.gn_part_) { p.gn_part = o.gn_part_; p.gn_hw = Hout * Wout; p.gn_blocks = Hout * Wout / 32; p.gn_cpg = Cout / 32; }
     if (f8) {
-      p.A = e->q8(in); p.W = e->w8(wkey); p.a_bytes /= 2; p.a_relu = 0;
+      p.A = e->q8(in); p.W = e->w8(wkey); p.a_relu = 0;
       p.out_scale = 1.0f / q8_scale_of(in); p.out_scale_v = e->wscale(wkey);
     }
     int mode = f8 ? MODE_FP8 : dt;
-    if (out_lo >= 0 && e->mixed()) {  // per-layer policy
+    if (o.out_lo_ >= 0 && e->mixed()) {  // per-layer policy
       const bool x3 = e->layer_x3(wkey, cur_group), a_lo = e->layer_reads_lo(wkey, cur_group);
       p.a_hi_only = x3 && !a_lo;
       if (a_lo && !has_lo(in)) {  // cannot happen with the schedule below: every producer honours its consumers' needs
         if (err == hipSuccess) { err = hipErrorInvalidValue; where = "precision policy: a 3-MFMA layer reads a tensor without lo plane"; }
         return;
       }
-      const bool r1lo = R1 != nullptr && has_lo(R1), r2lo = R2 != nullptr && has_lo(R2);
+      const bool r1lo = o.R1_ != nullptr && has_lo(o.R1_), r2lo = o.R2_ != nullptr && has_lo(o.R2_);
       mode = x3 ? MODE_FP16X3 : MODE_FP16;
-      p.r1_hi_only = !r1lo; p.r2_hi_only = !r2lo; p.c_hi_only = !out_lo;
-      p.epi2 = (!x3 && (out_lo || r1lo || r2lo)) ? 1 : 0;
-      mark_lo(out, out_lo != 0);
+      p.r1_hi_only = !r1lo; p.r2_hi_only = !r2lo; p.c_hi_only = !o.out_lo_;
+      p.epi2 = (!x3 && (o.out_lo_ || r1lo || r2lo)) ? 1 : 0;
+      mark_lo(out, o.out_lo_ != 0);
     }
     gemm(mode, p, wkey.c_str());
-    if (slot >= 0) q8_measure(out, (size_t)p.M * p.N, q == 2, slot);
+    if (slot >= 0) q8_measure(out, (size_t)p.M * p.N, o.q_ == 2, slot);
   }
 
   // GroupNorm statistics come out of the producing conv's epilogue when an image's rows are whole 32-row MFMA blocks
@@ -905,15 +912,16 @@ struct Run {
     chk(launch_gn_apply(dt, g, e->pl, st), nkey.c_str(), 2);
   }
 
-  // RCU (blocks.py:263-286): out = conv2(relu(conv1(relu(x)))) + x (+ extra)
-  // q_out (fp8 dtype): e4m3 copy of the unit's output -- 2 when its consumer pre-activates (another RCU), 1 otherwise
-  // out_lo: MIXED per-layer policy (conv()): does a consumer of the unit's output need its lo plane
-  void rcu(const std::string& p, const void* x, int H, int W, void* tmp, void* out, const void* extra, int q_out, int out_lo) {
+  // RCU (blocks.py:263-286): out = conv2(relu(conv1(relu(x)))) + x (+ o.R2)
+  // Of `o` the unit reads R2 (the extra summand), q (fp8 dtype: e4m3 copy of the unit's output -- 2 when its consumer
+  // pre-activates (another RCU), 1 otherwise) and out_lo (MIXED per-layer policy: does a consumer of the unit's output need
+  // its lo plane)
+  void rcu(const std::string& p, const void* x, int H, int W, void* tmp, void* out, const GemmOpt& o) {
     const int mid_lo = e->mixed() ? (int)e->layer_reads_lo(p + "conv2.weight", cur_group) : -1;
-    conv(x, H, W, FEAT, p + "conv1.weight", 3, 1, 1, 1, H, W, FEAT, tmp, e->f(p + "conv1.bias"), /*act*/ 1, /*a_relu*/ 1, nullptr,
-         nullptr, nullptr, e->fp8_use(p + "conv2.weight") ? 1 : 0, mid_lo);
-    conv(tmp, H, W, FEAT, p + "conv2.weight", 3, 1, 1, 1, H, W, FEAT, out, e->f(p + "conv2.bias"), 0, 0, x, extra, nullptr, q_out,
-         e->mixed() ? out_lo : -1);
+    conv(x, H, W, FEAT, p + "conv1.weight", 3, 1, 1, 1, H, W, FEAT, tmp,
+         GemmOpt().bias(e->f(p + "conv1.bias")).act(1).a_relu(1).q(e->fp8_use(p + "conv2.weight") ? 1 : 0).out_lo(mid_lo));
+    conv(tmp, H, W, FEAT, p + "conv2.weight", 3, 1, 1, 1, H, W, FEAT, out,
+         GemmOpt().bias(e->f(p + "conv2.bias")).R1(x).R2(o.R2_).q(o.q_).out_lo(e->mixed() ? o.out_lo_ : -1));
   }
 
   int forward(const void* x, void* y, void* y2);
@@ -973,21 +981,18 @@ int Run::forward(const void* x, void* y, void* y2) {
       void* out = (b == STAGE_DEPTH[s] - 1) ? (void*)A(E->S[s]) : (void*)((b & 1) ? A(E->PB) : A(E->PA));
       const bool f_in = gn_fusable(H * Wd), f_out = gn_fusable(Ho * Wo);  // statistics from the conv epilogues
       if (b == 0) {
-        conv(cur, H, Wd, cin, p + "downsample.conv.weight", 1, stride, 0, 0, Ho, Wo, cout, A(E->DS), nullptr, 0, 0, nullptr, nullptr,
-             f_out ? part3 : nullptr);
+        conv(cur, H, Wd, cin, p + "downsample.conv.weight", 1, stride, 0, 0, Ho, Wo, cout, A(E->DS), GemmOpt().gn_part(f_out ? part3 : nullptr));
         if (!f_out) gn_stats(A(E->DS), part3, Ho * Wo, cout);
       }
-      conv(cur, H, Wd, cin, p + "conv1.weight", 1, 1, 0, 0, H, Wd, mid, A(E->T1), nullptr, 0, 0, nullptr, nullptr, f_in ? part0 : nullptr);
+      conv(cur, H, Wd, cin, p + "conv1.weight", 1, 1, 0, 0, H, Wd, mid, A(E->T1), GemmOpt().gn_part(f_in ? part0 : nullptr));
       if (!f_in) gn_stats(A(E->T1), part0, H * Wd, mid);
       gn_apply(A(E->T1), p + "norm1", part0, H * Wd, mid, 1);
       // 3x3, stride on conv2 (V1.5); TF-SAME: s1 -> pad (1,1); s2 on even H -> pad (0,1)
       const int pad = (stride == 1) ? 1 : 0;
-      conv(A(E->T1), H, Wd, mid, p + "conv2.weight", 3, stride, pad, pad, Ho, Wo, mid, A(E->T2), nullptr, 0, 0, nullptr, nullptr,
-           f_out ? part1 : nullptr);
+      conv(A(E->T1), H, Wd, mid, p + "conv2.weight", 3, stride, pad, pad, Ho, Wo, mid, A(E->T2), GemmOpt().gn_part(f_out ? part1 : nullptr));
       if (!f_out) gn_stats(A(E->T2), part1, Ho * Wo, mid);
       gn_apply(A(E->T2), p + "norm2", part1, Ho * Wo, mid, 1);
-      conv(A(E->T2), Ho, Wo, mid, p + "conv3.weight", 1, 1, 0, 0, Ho, Wo, cout, out, nullptr, 0, 0, nullptr, nullptr,
-           f_out ? part2 : nullptr);
+      conv(A(E->T2), Ho, Wo, mid, p + "conv3.weight", 1, 1, 0, 0, Ho, Wo, cout, out, GemmOpt().gn_part(f_out ? part2 : nullptr));
       if (!f_out) gn_stats(out, part2, Ho * Wo, cout);
       if (b == 0)
         gn_apply(out, p + "norm3", part2, Ho * Wo, cout, 1, A(E->DS), p + "downsample.norm", part3);
@@ -1051,29 +1056,26 @@ int Run::forward(const void* x, void* y, void* y2) {
   };
   tok_tap(0, "tok0");
 
-  // ln: 0 plain; 1 consumer of the folded LayerNorm (qkv, fc1); 2 producer (proj, fc2: 16-bit copy + row statistics)
-  // q8_out (fp8 ViT): the consumer of C multiplies on e4m3 operands -- the epilogue also writes C's e4m3 copy (one calibrated
-  // power-of-two scale per tensor, like the decoder's: Run::conv)
-  auto dense = [&](const void* A, const std::string& wkey, int N, int K, void* C, int c_fp32, const float* bias,
-                   int act, const void* R1, int r1_fp32, int ln = 0, const float* ln_colsum = nullptr, bool q8_out = false) {
+  // One linear layer of a transformer block over the M token rows
+  auto dense = [&](const void* A, const std::string& wkey, int N, int K, void* C, const GemmOpt& o) {
     GemmParams p;
     gemm_params_dense(p, M, N, K);
-    p.A = A; p.W = E->w(wkey); p.C = C; p.c_fp32 = c_fp32; p.bias = bias; p.act = act;
-    p.R1 = R1; p.r1_fp32 = r1_fp32; p.planes = E->pl;
-    if (ln == 1) { p.ln_stats = lnst; p.ln_colsum = ln_colsum; p.ln_nblk = ln_nblk; p.ln_eps = 1e-6f; p.ln_inv_dim = 1.0f / (float)K; }
-    if (ln == 2) { p.C16 = this->A(E->Hn); p.row_stats = lnst; p.stats_nblk = 8; }
-    if (ln == 2 && s16) {  // in place on the 16-bit stream: every thread reads exactly the elements it then writes
+    p.A = A; p.W = E->w(wkey); p.C = C; p.c_fp32 = o.c_fp32_; p.bias = o.bias_; p.act = o.act_;
+    p.R1 = o.R1_; p.r1_fp32 = o.r1_fp32_; p.planes = E->pl;
+    if (o.ln_ == LN_CONSUMER) { p.ln_stats = lnst; p.ln_colsum = o.colsum_; p.ln_nblk = ln_nblk; p.ln_eps = 1e-6f; p.ln_inv_dim = 1.0f / (float)K; }
+    if (o.ln_ == LN_PRODUCER) { p.C16 = this->A(E->Hn); p.row_stats = lnst; p.stats_nblk = 8; }
+    if (o.ln_ == LN_PRODUCER && s16) {  // in place on the 16-bit stream: every thread reads exactly the elements it then writes
       p.C = this->A(E->Hn); p.c_fp32 = 0; p.R1 = this->A(E->Hn); p.r1_fp32 = 0; p.C16 = nullptr;
     }
     int mode = dt;
     if (E->fp8_use(wkey) && !E->calibrating) {  // e4m3 operands: the e4m3 copies of A and of the (folded) weight
       p.A = E->q8(A); p.W = E->w8(wkey); p.a_bytes /= 2;
       p.out_scale = 1.0f / q8_scale_of(A); p.out_scale_v = E->wscale(wkey);
-      if (ln == 1) p.ln_colsum = E->f(wkey.substr(0, wkey.size() - 6) + "lnsum8");
+      if (o.ln_ == LN_CONSUMER) p.ln_colsum = E->f(wkey.substr(0, wkey.size() - 6) + "lnsum8");
       mode = MODE_FP8;
     }
     int slot = -1;
-    if (q8_out) {
+    if (o.q_) {
       slot = q8_produce(p.C);
       p.C8 = E->q8(p.C); p.q_relu = 0; p.q_scale = E->act_scale[slot];
     }
@@ -1106,9 +1108,10 @@ int Run::forward(const void* x, void* y, void* y2) {
     p.c_rpi = NP; p.c_img_rows = NP; p.c_row_off = 0; p.ldc = D_VIT;
     p.bias = clsb; p.bias_per_img = 1; p.act = 2;
     gemm(dt, p, "readout");
+    const int f = n == 1 ? 256 : (n == 2 ? 512 : D_VIT);  // n <= 2: DPT-Large only
+    conv(R, gh, gw, D_VIT, pp + "3.weight", 1, 1, 0, 0, gh, gw, f, n == 3 ? A(E->L3) : A(E->T4), GemmOpt().bias(E->f(pp + "3.bias")));
     if (n <= 2) {
-      const int f = n == 1 ? 256 : 512, k = n == 1 ? 4 : 2;
-      conv(R, gh, gw, D_VIT, pp + "3.weight", 1, 1, 0, 0, gh, gw, f, A(E->T4), E->f(pp + "3.bias"), 0, 0);
+      const int k = n == 1 ? 4 : 2;
       GemmParams d;
       gemm_params_dense(d, B * NP, k * k * f, f);
       d.A = A(E->T4); d.W = E->w(pp + "4.weight"); d.C = A(E->F1); d.bias = E->f(pp + "4.bias"); d.planes = E->pl;
@@ -1116,11 +1119,9 @@ int Run::forward(const void* x, void* y, void* y2) {
       chk(launch_depth_to_space(dt, A(E->F1), A(E->S[n - 1]), B, gh, gw, k, f, E->pl, st), "reassemble.d2s");
       tap(n == 1 ? "l1" : "l2", A(E->S[n - 1]), gh * k, gw * k, f);
     } else if (n == 3) {
-      conv(R, gh, gw, D_VIT, pp + "3.weight", 1, 1, 0, 0, gh, gw, D_VIT, A(E->L3), E->f(pp + "3.bias"), 0, 0);
       tap("l3", A(E->L3), gh, gw, D_VIT);
     } else {
-      conv(R, gh, gw, D_VIT, pp + "3.weight", 1, 1, 0, 0, gh, gw, D_VIT, A(E->T4), E->f(pp + "3.bias"), 0, 0);
-      conv(A(E->T4), gh, gw, D_VIT, pp + "4.weight", 3, 2, 1, 1, h32, w32, D_VIT, A(E->L4), E->f(pp + "4.bias"), 0, 0);
+      conv(A(E->T4), gh, gw, D_VIT, pp + "4.weight", 3, 2, 1, 1, h32, w32, D_VIT, A(E->L4), GemmOpt().bias(E->f(pp + "4.bias")));
       tap("l4", A(E->L4), h32, w32, D_VIT);
     }
   };
@@ -1130,22 +1131,25 @@ int Run::forward(const void* x, void* y, void* y2) {
     group(DPTX_GROUP_VIT);
     const std::string p = vp + "blocks." + std::to_string(l) + ".";
     const bool lf = E->ln_fold;
+    const int ln_in = lf ? LN_CONSUMER : LN_NONE, ln_out = lf ? LN_PRODUCER : LN_NONE;  // qkv, fc1 / proj, fc2
     if (!lf) chk(launch_layernorm(dt, X, E->f(p + "norm1.weight"), E->f(p + "norm1.bias"), A(E->Hn), M, D_VIT, 1e-6f, E->pl, st), "ln1", 2);
     // fp8 ViT: the tensors that an e4m3 GEMM reads get their e4m3 copy from the epilogue that produces them -- the stream
     // after proj (fc1's operand), the GELU output (fc2's), the stream after fc2 (the next block's qkv)
     const std::string pn = vp + "blocks." + std::to_string(l + 1) + ".";
     const bool q_fc1 = E->fp8_use(p + "mlp.fc1.weight"), q_fc2 = E->fp8_use(p + "mlp.fc2.weight");
     const bool q_next = l + 1 < E->depth && E->fp8_use(pn + "attn.qkv.weight");
-    dense(A(E->Hn), p + "attn.qkv.weight", 3 * D_VIT, D_VIT, A(E->QKV), 0, E->f(p + "attn.qkv.bias"), 0, nullptr, 0, lf ? 1 : 0,
-          lf ? E->f(p + "attn.qkv.lnsum") : nullptr);
+    dense(A(E->Hn), p + "attn.qkv.weight", 3 * D_VIT, D_VIT, A(E->QKV),
+          GemmOpt().bias(E->f(p + "attn.qkv.bias")).ln(ln_in).colsum(E->f(p + "attn.qkv.lnsum")));
     chk(launch_attention(dt, A(E->QKV), A(E->AO), B, S, N_HEADS, E->pl, st), "attention", 1);
     exec_macs += 2.0 * N_HEADS * (double)S * S * 64;
     cat_macs[1] += 2.0 * N_HEADS * (double)S * S * 64;
-    dense(A(E->AO), p + "attn.proj.weight", D_VIT, D_VIT, X, 1, E->f(p + "attn.proj.bias"), 0, X, 1, lf ? 2 : 0, nullptr, q_fc1);
+    dense(A(E->AO), p + "attn.proj.weight", D_VIT, D_VIT, X,
+          GemmOpt().c_fp32(1).bias(E->f(p + "attn.proj.bias")).R1(X).r1_fp32(1).ln(ln_out).q(q_fc1));
     if (!lf) chk(launch_layernorm(dt, X, E->f(p + "norm2.weight"), E->f(p + "norm2.bias"), A(E->Hn), M, D_VIT, 1e-6f, E->pl, st), "ln2", 2);
-    dense(A(E->Hn), p + "mlp.fc1.weight", D_MLP, D_VIT, A(E->F1), 0, E->f(p + "mlp.fc1.bias"), 2, nullptr, 0, lf ? 1 : 0,
-          lf ? E->f(p + "mlp.fc1.lnsum") : nullptr, q_fc2);
-    dense(A(E->F1), p + "mlp.fc2.weight", D_VIT, D_MLP, X, 1, E->f(p + "mlp.fc2.bias"), 0, X, 1, lf ? 2 : 0, nullptr, q_next);
+    dense(A(E->Hn), p + "mlp.fc1.weight", D_MLP, D_VIT, A(E->F1),
+          GemmOpt().bias(E->f(p + "mlp.fc1.bias")).act(2).ln(ln_in).colsum(E->f(p + "mlp.fc1.lnsum")).q(q_fc2));
+    dense(A(E->F1), p + "mlp.fc2.weight", D_VIT, D_MLP, X,
+          GemmOpt().c_fp32(1).bias(E->f(p + "mlp.fc2.bias")).R1(X).r1_fp32(1).ln(ln_out).q(q_next));
     {
       char nm[16];
       snprintf(nm, sizeof nm, "blk%d", l);
@@ -1188,8 +1192,8 @@ int Run::forward(const void* x, void* y, void* y2) {
     // consumer of lrn[i] as a GEMM operand: refinenet4.resConfUnit2.conv1 (i = 3), refinenet{i+1}.resConfUnit1.conv1 (else)
     const std::string cons = pre + "scratch.refinenet" + std::to_string(i + 1) + (i == 3 ? ".resConfUnit2.conv1.weight" : ".resConfUnit1.conv1.weight");
     conv(rn_in[i], rn_h[i], rn_w[i], rn_c[i], pre + "scratch.layer" + std::to_string(i + 1) + "_rn.weight", 3, 1, 1, 1, rn_h[i],
-         rn_w[i], FEAT, A(E->lrn[i]), nullptr, 0, 0, nullptr, nullptr, nullptr, /*q: every consumer pre-activates*/ E->fp8_use(cons) ? 2 : 0,
-         lo_of(RLO(cons, DPTX_GROUP_FUSION)));
+         rn_w[i], FEAT, A(E->lrn[i]),
+         GemmOpt().q(/*every consumer pre-activates*/ E->fp8_use(cons) ? 2 : 0).out_lo(lo_of(RLO(cons, DPTX_GROUP_FUSION))));
     tap((pre + rn_names[i]).c_str(), A(E->lrn[i]), rn_h[i], rn_w[i], FEAT);
   }
 
@@ -1207,17 +1211,19 @@ int Run::forward(const void* x, void* y, void* y2) {
     if (i == 4) {
       sum = A(E->lrn[3]);
     } else {
-      rcu(p + "resConfUnit1.", A(E->lrn[i - 1]), h, w, A(E->tA), A(E->tB), path, E->fp8_use(p + "resConfUnit2.conv1.weight") ? 2 : 0,
-          lo_of(RLO(p + "resConfUnit2.conv1.weight", DPTX_GROUP_FUSION)));  // tB = path + RCU1(lrn)
+      rcu(p + "resConfUnit1.", A(E->lrn[i - 1]), h, w, A(E->tA), A(E->tB),  // tB = path + RCU1(lrn)
+          GemmOpt().R2(path).q(E->fp8_use(p + "resConfUnit2.conv1.weight") ? 2 : 0)
+              .out_lo(lo_of(RLO(p + "resConfUnit2.conv1.weight", DPTX_GROUP_FUSION))));
       sum = A(E->tB);
     }
-    rcu(p + "resConfUnit2.", sum, h, w, A(E->tA), A(E->tC), nullptr, E->fp8_use(p + "out_conv.weight") ? 1 : 0,
-        lo_of(RLO(p + "out_conv.weight", DPTX_GROUP_FUSION)));
+    rcu(p + "resConfUnit2.", sum, h, w, A(E->tA), A(E->tC),
+        GemmOpt().q(E->fp8_use(p + "out_conv.weight") ? 1 : 0).out_lo(lo_of(RLO(p + "out_conv.weight", DPTX_GROUP_FUSION))));
     // the path tensor keeps a lo plane when out_conv computed one (it is added to the next stage's sum in fp32) and when
     // the first head conv multiplies it with 3 MFMAs.  A 2-MFMA head conv reads the hi plane only: path_1 is then interpolated
     // from both planes of the low-resolution tensor and rounded ONCE, into the hi plane
-    conv(A(E->tC), h, w, FEAT, p + "out_conv.weight", 1, 1, 0, 0, h, w, FEAT, A(E->tA), E->f(p + "out_conv.bias"), 0, 0, nullptr,
-         nullptr, nullptr, 0, lo_of(X3(p + "out_conv.weight", DPTX_GROUP_FUSION) || (i == 1 && X3(oc + "0.weight", DPTX_GROUP_HEAD))));
+    conv(A(E->tC), h, w, FEAT, p + "out_conv.weight", 1, 1, 0, 0, h, w, FEAT, A(E->tA),
+         GemmOpt().bias(E->f(p + "out_conv.bias"))
+             .out_lo(lo_of(X3(p + "out_conv.weight", DPTX_GROUP_FUSION) || (i == 1 && X3(oc + "0.weight", DPTX_GROUP_HEAD)))));
     // path_1 feeds the first head conv: in the fp8 dtype the up-sampling also writes its e4m3 copy
     {
       const bool up8 = i == 1 && E->fp8_use(oc + "0.weight");
@@ -1236,8 +1242,7 @@ int Run::forward(const void* x, void* y, void* y2) {
   // ---- head (dpt_depth.py:91-99) ----------------------------------------------------------
   group(DPTX_GROUP_HEAD);
   const bool conv2_x3 = mx ? X3(oc + "2.weight", DPTX_GROUP_HEAD) : mode_is_x3(dt);
-  conv(path, h2, w2, FEAT, oc + "0.weight", 3, 1, 1, 1, h2, w2, 128, A(E->H0), E->f(oc + "0.bias"), 0, 0, nullptr, nullptr, nullptr, 0,
-       lo_of(conv2_x3));
+  conv(path, h2, w2, FEAT, oc + "0.weight", 3, 1, 1, 1, h2, w2, 128, A(E->H0), GemmOpt().bias(E->f(oc + "0.bias")).out_lo(lo_of(conv2_x3)));
   tap((pre + "h0").c_str(), A(E->H0), h2, w2, 128);
   // fp16-plane dtypes: did anything upstream leave the fp16 range?  (one pass over the hi plane of H0: every decoder path and,
   // through them, the ViT blocks reach it by residual adds; the ResNetV2 stages cannot overflow -- standardised weights and
@@ -1258,8 +1263,8 @@ int Run::forward(const void* x, void* y, void* y2) {
   } else {
     chk(launch_upsample2x(planes_mode(A(E->H0)), A(E->H0), A(E->H0U), B, h2, w2, 128, E->pl, st), "head.up");
     if (mx) mark_lo(A(E->H0U), has_lo(A(E->H0)));
-    conv(A(E->H0U), Hi, Wi, 128, oc + "2.weight", 3, 1, 1, 1, Hi, Wi, 32, A(E->H1), E->f(oc + "2.bias"), 1, 0, nullptr, nullptr,
-         nullptr, 0, lo_of(conv2_x3));
+    conv(A(E->H0U), Hi, Wi, 128, oc + "2.weight", 3, 1, 1, 1, Hi, Wi, 32, A(E->H1),
+         GemmOpt().bias(E->f(oc + "2.bias")).act(1).out_lo(lo_of(conv2_x3)));
     tap((pre + "h1").c_str(), A(E->H1), Hi, Wi, 32);
     chk(launch_head_out(planes_mode(A(E->H1)), A(E->H1), E->f(oc + "4.weight"), E->f(oc + "4.bias"), yout, io, B, Hi * Wi, ch,
                         E->cfg.non_negative, E->pl, st),
@@ -1662,37 +1667,38 @@ int dptx_forward(dptx_handle h, const void* x_dev, int32_t x_dtype, void* y_dev,
   return dptx_forward_hw(h, x_dev, x_dtype, y_dev, batch, IMG, IMG, stream);
 }
 
-int dptx_forward_hw(dptx_handle h, const void* x_dev, int32_t x_dtype, void* y_dev, int32_t batch, int32_t height,
-                    int32_t width, void* stream) {
-  if (!h || !x_dev || !y_dev) return DPTX_E_INVALID;
-  if (h->cfg.device_id < 0) return h->fail(DPTX_E_NODEVICE, "dptx_forward on a host-only handle");
-  if (!h->device_ready) return h->fail(DPTX_E_INVALID, "dptx_forward before weights were finalized/imported");
+// The argument checks of the two forward entry points; `fn` names the caller in the messages, `dual` says which kind of
+// handle it serves
+static int check_forward_args(dptx_handle h, const char* fn, bool dual, int32_t x_dtype, int32_t batch, int32_t height, int32_t width) {
+  if (h->cfg.device_id < 0) return h->fail(DPTX_E_NODEVICE, std::string(fn) + " on a host-only handle");
+  if (dual != (h->cfg.dual_task != 0))
+    return h->fail(DPTX_E_INVALID, dual ? "dptx_forward_dual needs a handle created with dual_task = 1" : "dual-task handle: call dptx_forward_dual");
+  if (!h->device_ready) return h->fail(DPTX_E_INVALID, std::string(fn) + " before weights were finalized/imported");
   if (batch < 1 || batch > h->cfg.max_batch) return h->fail(DPTX_E_INVALID, "batch out of range [1, max_batch]");
   if (x_dtype != DPTX_IO_FP32 && x_dtype != DPTX_IO_BF16 && x_dtype != DPTX_IO_FP16)
     return h->fail(DPTX_E_INVALID, "unsupported x_dtype (DPTX_IO_FP32 / DPTX_IO_BF16 / DPTX_IO_FP16)");
-  DeviceGuard guard(h->cfg.device_id);
-  HIPCHK(h, guard.err);
   if (height < 64 || width < 64 || height % 32 != 0 || width % 32 != 0)
     return h->fail(DPTX_E_INVALID, "input height/width must be multiples of 32, >= 64");
   if ((long long)height * width > (long long)h->max_h * h->max_w)
     return h->fail(DPTX_E_INVALID, "input larger than the engine was planned for (dptx_config.max_height/max_width)");
-  if (h->cfg.dual_task) return h->fail(DPTX_E_INVALID, "dual-task handle: call dptx_forward_dual");
+  return DPTX_OK;
+}
+
+int dptx_forward_hw(dptx_handle h, const void* x_dev, int32_t x_dtype, void* y_dev, int32_t batch, int32_t height,
+                    int32_t width, void* stream) {
+  if (!h || !x_dev || !y_dev) return DPTX_E_INVALID;
+  const int rc = check_forward_args(h, "dptx_forward", false, x_dtype, batch, height, width);
+  if (rc != DPTX_OK) return rc;
+  DeviceGuard guard(h->cfg.device_id);
+  HIPCHK(h, guard.err);
   return run_forward(h, x_dev, x_dtype, y_dev, nullptr, batch, height, width, (hipStream_t)stream);
 }
 
 int dptx_forward_dual(dptx_handle h, const void* x_dev, int32_t x_dtype, void* y_normal_dev, void* y_depth_dev, int32_t batch,
                       int32_t height, int32_t width, void* stream) {
   if (!h || !x_dev || !y_normal_dev || !y_depth_dev) return DPTX_E_INVALID;
-  if (h->cfg.device_id < 0) return h->fail(DPTX_E_NODEVICE, "dptx_forward_dual on a host-only handle");
-  if (!h->cfg.dual_task) return h->fail(DPTX_E_INVALID, "dptx_forward_dual needs a handle created with dual_task = 1");
-  if (!h->device_ready) return h->fail(DPTX_E_INVALID, "dptx_forward_dual before weights were finalized/imported");
-  if (batch < 1 || batch > h->cfg.max_batch) return h->fail(DPTX_E_INVALID, "batch out of range [1, max_batch]");
-  if (x_dtype != DPTX_IO_FP32 && x_dtype != DPTX_IO_BF16 && x_dtype != DPTX_IO_FP16)
-    return h->fail(DPTX_E_INVALID, "unsupported x_dtype (DPTX_IO_FP32 / DPTX_IO_BF16 / DPTX_IO_FP16)");
-  if (height < 64 || width < 64 || height % 32 != 0 || width % 32 != 0)
-    return h->fail(DPTX_E_INVALID, "input height/width must be multiples of 32, >= 64");
-  if ((long long)height * width > (long long)h->max_h * h->max_w)
-    return h->fail(DPTX_E_INVALID, "input larger than the engine was planned for (dptx_config.max_height/max_width)");
+  const int rc = check_forward_args(h, "dptx_forward_dual", true, x_dtype, batch, height, width);
+  if (rc != DPTX_OK) return rc;
   DeviceGuard guard(h->cfg.device_id);
   HIPCHK(h, guard.err);
   return run_forward(h, x_dev, x_dtype, y_normal_dev, y_depth_dev, batch, height, width, (hipStream_t)stream);
@@ -1937,138 +1943,6 @@ int dptx_profile_dump(dptx_handle h, const char* path) {
   return DPTX_OK;
 }
 
-// --------------------------------------------------------------------- op-level entry points
-static Planes g_op_planes{0, 0};
-int dptx_op_set_planes(int64_t act_plane_elems, int64_t w_plane_elems) {
-  g_op_planes.act = act_plane_elems;
-  g_op_planes.w = w_plane_elems;
-  return DPTX_OK;
-}
-
-int dptx_op_gemm(int32_t dtype, const void* A, const void* W, const float* bias, const void* R, void* C, int32_t M, int32_t N,
-                 int32_t K, int32_t act, int32_t a_fp32, int32_t c_fp32, int32_t r_fp32, void* stream) {
-  GemmParams p;
-  gemm_params_dense(p, M, N, K);
-  p.A = A; p.W = W; p.C = C; p.bias = bias; p.R1 = R; p.act = act; p.a_fp32 = a_fp32; p.c_fp32 = c_fp32; p.r1_fp32 = r_fp32;
-  p.planes = g_op_planes;
-  return launch_gemm(dtype, p, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-// dense GEMM with the LayerNorm fold's CONSUMER epilogue (tests/test_gpu_coresidency.py): C = act((A W^T - mu colsum) rstd + bias),
-// (mu, rstd) of row m from the (sum, sum of squares) records ln_stats[m][0 .. ln_nblk) (row stride 8 records)
-int dptx_op_gemm_ln(int32_t dtype, const void* A, const void* W, const float* bias, void* C, int32_t M, int32_t N, int32_t K,
-                    int32_t act, const float* ln_stats, const float* ln_colsum, int32_t ln_nblk, float ln_eps, void* stream) {
-  GemmParams p;
-  gemm_params_dense(p, M, N, K);
-  p.A = A; p.W = W; p.C = C; p.bias = bias; p.act = act; p.planes = g_op_planes;
-  p.ln_stats = ln_stats; p.ln_colsum = ln_colsum; p.ln_nblk = ln_nblk; p.ln_eps = ln_eps; p.ln_inv_dim = 1.0f / (float)K;
-  return launch_gemm(dtype, p, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-// dense GEMM with the LayerNorm fold's PRODUCER epilogue on the 16-bit token stream (what the proj / fc2 launches run):
-// C <- C + A W^T + bias in place, and (sum, sum of squares) of every new row per 128-column block into row_stats[m][0 .. N / 128)
-int dptx_op_gemm_stream(int32_t dtype, const void* A, const void* W, const float* bias, void* C, float* row_stats, int32_t M,
-                        int32_t N, int32_t K, void* stream) {
-  GemmParams p;
-  gemm_params_dense(p, M, N, K);
-  p.A = A; p.W = W; p.C = C; p.R1 = C; p.bias = bias; p.planes = g_op_planes;
-  p.row_stats = row_stats; p.stats_nblk = 8;
-  return launch_gemm(dtype, p, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-// the same on the fp32 token stream of the parity mode: X (fp32) <- X + A W^T + bias in place, its 16-bit image into C16
-int dptx_op_gemm_stream32(int32_t dtype, const void* A, const void* W, const float* bias, float* X, void* C16, float* row_stats,
-                          int32_t M, int32_t N, int32_t K, void* stream) {
-  GemmParams p;
-  gemm_params_dense(p, M, N, K);
-  p.A = A; p.W = W; p.C = X; p.c_fp32 = 1; p.R1 = X; p.r1_fp32 = 1; p.C16 = C16; p.bias = bias; p.planes = g_op_planes;
-  p.row_stats = row_stats; p.stats_nblk = 8;
-  return launch_gemm(dtype, p, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-int dptx_op_head_tail(int32_t dtype, const void* H0, const void* W2, const float* b2, const float* w4, const float* b4, float* y,
-                      int32_t B, int32_t Hs, int32_t Ws, int32_t C, int32_t relu_out, void* stream) {
-  return launch_head_tail(dtype, H0, W2, b2, w4, b4, y, DPTX_IO_FP32, B, Hs, Ws, C, relu_out, (hipStream_t)stream, g_op_planes) == hipSuccess
-             ? DPTX_OK
-             : DPTX_E_HIP;
-}
-
-int dptx_op_conv(int32_t dtype, const void* X, const void* Wt, const float* bias, const void* R, void* Y, int32_t B, int32_t H,
-                 int32_t W, int32_t Cin, int32_t Cout, int32_t ksize, int32_t stride, int32_t pad_t, int32_t pad_l, int32_t Ho,
-                 int32_t Wo, int32_t a_relu, int32_t act, void* stream) {
-  GemmParams p{};
-  p.A = X; p.W = Wt; p.C = Y; p.bias = bias; p.R1 = R;
-  p.M = B * Ho * Wo; p.N = Cout; p.K = ksize * ksize * Cin; p.ldw = p.K;
-  p.a_rpi = Ho * Wo; p.Wout = Wo; p.Hin = H; p.Win = W; p.Cin = Cin; p.a_pix_stride = Cin;
-  p.a_img_stride = (long long)H * W * Cin;
-  p.a_bytes = (long long)B * H * W * Cin * 2;
-  p.ksz = ksize; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-  p.c_rpi = 0x7fffffff; p.ldc = Cout; p.act = act; p.a_relu = a_relu; p.planes = g_op_planes;
-  p.k_tap_fast = (ksize == 3 && Cin >= 512) ? 1 : 0;
-  return launch_gemm(dtype, p, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-int dptx_op_conv_planes(int32_t dtype, const void* X, const void* Wt, const float* bias, const void* R, void* Y, int32_t B, int32_t H,
-                        int32_t W, int32_t Cin, int32_t Cout, int32_t ksize, int32_t stride, int32_t pad_t, int32_t pad_l, int32_t Ho,
-                        int32_t Wo, int32_t a_relu, int32_t act, int32_t epi2, int32_t c_hi_only, int32_t r1_hi_only, void* stream) {
-  GemmParams p{};
-  p.A = X; p.W = Wt; p.C = Y; p.bias = bias; p.R1 = R;
-  p.M = B * Ho * Wo; p.N = Cout; p.K = ksize * ksize * Cin; p.ldw = p.K;
-  p.a_rpi = Ho * Wo; p.Wout = Wo; p.Hin = H; p.Win = W; p.Cin = Cin; p.a_pix_stride = Cin;
-  p.a_img_stride = (long long)H * W * Cin;
-  p.a_bytes = (long long)B * H * W * Cin * 2;
-  p.ksz = ksize; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-  p.c_rpi = 0x7fffffff; p.ldc = Cout; p.act = act; p.a_relu = a_relu; p.planes = g_op_planes;
-  p.k_tap_fast = (ksize == 3 && Cin >= 512) ? 1 : 0;
-  p.epi2 = epi2 & 1; p.a_hi_only = (epi2 >> 1) & 1; p.c_hi_only = c_hi_only; p.r1_hi_only = r1_hi_only;
-  return launch_gemm(dtype, p, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-int dptx_op_stem_conv(int32_t dtype, const float* x, const void* Wt, void* y, int32_t B, int32_t H, int32_t W, void* stream) {
-  return launch_stem_conv(dtype, x, DPTX_IO_FP32, Wt, y, B, H, W, g_op_planes, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-int dptx_op_attention(int32_t dtype, const void* qkv, void* out, int32_t B, int32_t S, int32_t heads, void* stream) {
-  return launch_attention(dtype, qkv, out, B, S, heads, g_op_planes, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-int dptx_op_layernorm(int32_t dtype, const float* x, const float* gamma, const float* beta, void* y, int32_t M, int32_t C,
-                      float eps, void* stream) {
-  return launch_layernorm(dtype, x, gamma, beta, y, M, C, eps, g_op_planes, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-int dptx_op_groupnorm(int32_t dtype, const void* X, const float* gamma, const float* beta, const void* R, void* Y, int32_t B,
-                      int32_t HW, int32_t C, int32_t relu, float eps, void* scratch_f32, void* stream) {
-  if (scratch_f32 == nullptr) return DPTX_E_INVALID;
-  hipError_t r = launch_gn_stats(dtype, X, (float*)scratch_f32, B, HW, C, g_op_planes, (hipStream_t)stream);
-  if (r != hipSuccess) return DPTX_E_HIP;
-  GnParams g{};
-  g.X = X; g.Y = Y; g.gamma = gamma; g.beta = beta; g.partial = (float*)scratch_f32; g.R = R;
-  g.B = B; g.HW = HW; g.C = C; g.relu = relu; g.eps = eps;
-  return launch_gn_apply(dtype, g, g_op_planes, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-// the stem's GroupNorm + ReLU + MaxPool2dSame(3, 2): the stats pass, then the fused apply / pool.  Odd H / W are refused by
-// launch_gn_relu_maxpool itself -- the guard the forward relies on -- and deliberately not here, so that the op-level test
-// reaches it (the stats pass before it is harmless at any size).
-int dptx_op_gn_relu_maxpool(int32_t dtype, const void* X, const float* gamma, const float* beta, void* Y, int32_t B, int32_t H,
-                            int32_t W, int32_t C, float eps, void* scratch_f32, void* stream) {
-  if (scratch_f32 == nullptr) return DPTX_E_INVALID;
-  hipError_t r = launch_gn_stats(dtype, X, (float*)scratch_f32, B, H * W, C, g_op_planes, (hipStream_t)stream);
-  if (r != hipSuccess) return DPTX_E_HIP;
-  return launch_gn_relu_maxpool(dtype, X, Y, gamma, beta, (const float*)scratch_f32, B, H, W, C, eps, g_op_planes,
-                                (hipStream_t)stream) == hipSuccess
-             ? DPTX_OK
-             : DPTX_E_HIP;
-}
-
-int dptx_op_cls_rows(int32_t dtype, const float* cls, const float* pos, float* X, int32_t B, int32_t S, int32_t C, void* X16,
-                     float* row_stats, void* X8, float q_scale, void* stream) {
-  if (row_stats != nullptr && C > 8 * 128) return DPTX_E_INVALID;  // records have a row stride of 8: C <= 1024
-  return launch_cls_rows(dtype, cls, pos, X, B, S, C, X16, row_stats, (hipStream_t)stream, X8, q_scale) == hipSuccess ? DPTX_OK
-                                                                                                                      : DPTX_E_HIP;
-}
-
 // ---- arena debugging (tests/test_gpu_poison.py): a forward must not read an arena byte it did not write itself
 int dptx_debug_arena_fill(dptx_handle h, int32_t byte_value) {
   if (!h) return DPTX_E_INVALID;
@@ -2093,16 +1967,6 @@ int dptx_debug_arena_read(dptx_handle h, void* dst_host, size_t offset, size_t b
   return DPTX_OK;
 }
 
-static std::vector<std::pair<const char*, const Buf*>> arena_buf_list(dptx_handle h) {
-  return {{"sraw", &h->sraw}, {"stem", &h->stem}, {"S0", &h->S[0]}, {"S1", &h->S[1]}, {"S2", &h->S[2]}, {"T1", &h->T1}, {"T2", &h->T2},
-          {"PA", &h->PA}, {"PB", &h->PB}, {"DS", &h->DS}, {"part0", &h->part[0]}, {"part1", &h->part[1]}, {"part2", &h->part[2]},
-          {"part3", &h->part[3]}, {"X", &h->X}, {"lnst", &h->lnst}, {"Hn", &h->Hn}, {"QKV", &h->QKV}, {"AO", &h->AO}, {"F1", &h->F1},
-          {"R3", &h->R3}, {"R4", &h->R4}, {"L3", &h->L3}, {"T4", &h->T4}, {"L4", &h->L4}, {"clsb", &h->clsb}, {"pos_alt", &h->pos_alt},
-          {"lrn0", &h->lrn[0]}, {"lrn1", &h->lrn[1]}, {"lrn2", &h->lrn[2]}, {"lrn3", &h->lrn[3]}, {"tA", &h->tA}, {"tB", &h->tB},
-          {"tC", &h->tC}, {"P0", &h->P[0]}, {"P1", &h->P[1]}, {"P2", &h->P[2]}, {"P3", &h->P[3]}, {"H0", &h->H0}, {"H0U", &h->H0U},
-          {"H1", &h->H1}};
-}
-
 int dptx_debug_arena_layout(dptx_handle h, char* dst, size_t capacity) {
   if (!h) return DPTX_E_INVALID;
   std::string s;
@@ -2110,8 +1974,8 @@ int dptx_debug_arena_layout(dptx_handle h, char* dst, size_t capacity) {
   snprintf(line, sizeof line, "arena_bytes %zu\narena_single %zu\nhalf_region %zu\nhalf_batch %d\nmax_batch %d\nn_streams %d\nplanes %d\n",
            h->arena_bytes, h->arena_single, h->half_region, h->half_batch, h->cfg.max_batch, h->n_streams, h->two_planes() ? 2 : 1);
   s += line;
-  for (const auto& nb : arena_buf_list(h)) {
-    snprintf(line, sizeof line, "buf %s %zu %zu %zu\n", nb.first, nb.second->off, nb.second->bytes, nb.second->off2);
+  for (const auto& nb : h->arena_bufs) {
+    snprintf(line, sizeof line, "buf %s %zu %zu %zu\n", nb.first.c_str(), nb.second->off, nb.second->bytes, nb.second->off2);
     s += line;
   }
   if (dst && capacity > 0) {
@@ -2128,7 +1992,7 @@ int dptx_debug_arena_layout(dptx_handle h, char* dst, size_t capacity) {
 // the same input names the first tensor that differs (round 4's hunt, profiles/history.md section 10).
 int dptx_debug_arena_checksums(dptx_handle h, void* out_dev, int32_t capacity, void* stream) {
   if (!h) return DPTX_E_INVALID;
-  const auto bufs = arena_buf_list(h);
+  const auto& bufs = h->arena_bufs;
   const int nbuf = (int)bufs.size();
   const int regions = h->last_regions > 1 ? h->last_regions : 1;
   const int planes = h->two_planes() ? 2 : 1;
@@ -2154,57 +2018,6 @@ int dptx_debug_arena_checksums(dptx_handle h, void* out_dev, int32_t capacity, v
         HIPCHK(h, launch_checksum(base, end - off, (unsigned long long*)out_dev + ((size_t)pl * regions + r) * nbuf + order[k].second, st));
       }
   return total;
-}
-
-int dptx_debug_set_trace(void* dev_buf) {
-  gemm_set_trace((long long*)dev_buf);
-  return DPTX_OK;
-}
-
-int dptx_debug_set_gemm_flags(int32_t flags) {
-  gemm_set_debug_flags(flags);
-  return DPTX_OK;
-}
-
-int dptx_op_conv_fp8(const void* X8, const void* Wt8, const float* bias, const void* R, void* Y, void* Y8, int32_t B, int32_t H,
-                     int32_t W, int32_t Cin, int32_t Cout, int32_t ksize, int32_t stride, int32_t pad_t, int32_t pad_l, int32_t Ho,
-                     int32_t Wo, int32_t act, int32_t q_relu, float out_scale, void* stream) {
-  GemmParams p{};
-  p.A = X8; p.W = Wt8; p.C = Y; p.bias = bias; p.R1 = R; p.C8 = Y8; p.q_relu = q_relu; p.out_scale = out_scale;
-  p.M = B * Ho * Wo; p.N = Cout; p.K = ksize * ksize * Cin; p.ldw = p.K;
-  p.a_rpi = Ho * Wo; p.Wout = Wo; p.Hin = H; p.Win = W; p.Cin = Cin; p.a_pix_stride = Cin;
-  p.a_img_stride = (long long)H * W * Cin;
-  p.a_bytes = (long long)B * H * W * Cin;
-  p.ksz = ksize; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-  p.c_rpi = 0x7fffffff; p.ldc = Cout; p.act = act;
-  p.k_tap_fast = (ksize == 3 && Cin >= 512) ? 1 : 0;
-  return launch_gemm(MODE_FP8, p, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-int dptx_op_conv_groupnorm(int32_t dtype, const void* X, const void* Wt, void* Yraw, const float* gamma, const float* beta,
-                           const void* R, void* Y, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t ksize,
-                           int32_t stride, int32_t pad_t, int32_t pad_l, int32_t Ho, int32_t Wo, int32_t relu, float eps,
-                           void* scratch_f32, void* stream) {
-  if (scratch_f32 == nullptr || (Ho * Wo) % 32 != 0) return DPTX_E_INVALID;
-  GemmParams p{};
-  p.A = X; p.W = Wt; p.C = Yraw;
-  p.M = B * Ho * Wo; p.N = Cout; p.K = ksize * ksize * Cin; p.ldw = p.K;
-  p.a_rpi = Ho * Wo; p.Wout = Wo; p.Hin = H; p.Win = W; p.Cin = Cin; p.a_pix_stride = Cin;
-  p.a_img_stride = (long long)H * W * Cin;
-  p.a_bytes = (long long)B * H * W * Cin * 2;
-  p.ksz = ksize; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-  p.c_rpi = 0x7fffffff; p.ldc = Cout; p.planes = g_op_planes;
-  p.k_tap_fast = (ksize == 3 && Cin >= 512) ? 1 : 0;
-  p.gn_part = (float*)scratch_f32; p.gn_hw = Ho * Wo; p.gn_blocks = Ho * Wo / 32; p.gn_cpg = Cout / 32;
-  if (launch_gemm(dtype, p, (hipStream_t)stream) != hipSuccess) return DPTX_E_HIP;
-  GnParams g{};
-  g.X = Yraw; g.Y = Y; g.gamma = gamma; g.beta = beta; g.partial = (float*)scratch_f32; g.R = R;
-  g.B = B; g.HW = Ho * Wo; g.C = Cout; g.relu = relu; g.eps = eps; g.nrec = Ho * Wo / 32;
-  return launch_gn_apply(dtype, g, g_op_planes, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
-}
-
-int dptx_op_upsample2x(int32_t dtype, const void* X, void* Y, int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
-  return launch_upsample2x(dtype, X, Y, B, H, W, C, g_op_planes, (hipStream_t)stream) == hipSuccess ? DPTX_OK : DPTX_E_HIP;
 }
 
 }  // extern "C"

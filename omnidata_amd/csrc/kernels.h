@@ -88,6 +88,10 @@ struct GemmParams {
 
 // Fills the "plain dense row-major" defaults for A [M,K] (lda = K) and C [M,N].
 void gemm_params_dense(GemmParams& p, int M, int N, int K);
+// Fills the geometry of an NHWC convolution [B,Hin,Win,Cin] -> [B,Hout,Wout,Cout] (weights [Cout][ksz][ksz][Cin], C dense
+// [M,N]): M, N, K, ldw, the a_* and c_* fields, ldc and the tap order k_tap_fast.  a_elem_bytes: 2, or 1 for e4m3 operands.
+void gemm_params_conv(GemmParams& p, int B, int Hin, int Win, int Cin, int Cout, int ksz, int stride, int pad_t, int pad_l,
+                      int Hout, int Wout, int a_elem_bytes);
 // dtype 0 bf16 / 1 fp16.  Picks the tile configuration from (M, N).  Returns hipError_t.
 hipError_t launch_gemm(int dtype, const GemmParams& p, hipStream_t stream);
 // debug: every following GEMM launch stamps s_memtime per k-tile phase for the 8 waves of block 0 into dev_buf

@@ -28,54 +28,50 @@ FEATURES = 256
 BACKBONES = ("vitb_rn50_384", "vitl16_384")
 
 
-def vitl16_state_dict_spec(num_channels: int = 1, include_unused: bool = True) -> "OrderedDict[str, Tuple[int, ...]]":
-    """Ordered {key: shape} of ``DPTDepthModel(backbone='vitl16_384', num_channels=C)`` (DPT-Large: blocks.py:12-18,
-    vit.py:299-309 hooks [5,11,17,23], reassemble vit.py:176-260): timm ``vit_large_patch16_384`` under ``pretrained.model.``
-    (16x16 patch conv, 24 blocks of width 1024, 16 heads), four ProjectReadouts, ConvTranspose2d up-sampling in
-    act_postprocess1/2, and the same scratch / RefineNet / head modules with layerN_rn inputs [256, 512, 1024, 1024]."""
-    D, depth, mlp = 1024, 24, 4096
-    sp: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+def _vit_block_entries(sp, p: str, D: int, mlp: int) -> None:
+    """One timm ``Block`` under prefix ``p``, in state-dict order."""
+    sp[p + "norm1.weight"] = (D,)
+    sp[p + "norm1.bias"] = (D,)
+    sp[p + "attn.qkv.weight"] = (3 * D, D)
+    sp[p + "attn.qkv.bias"] = (3 * D,)
+    sp[p + "attn.proj.weight"] = (D, D)
+    sp[p + "attn.proj.bias"] = (D,)
+    sp[p + "norm2.weight"] = (D,)
+    sp[p + "norm2.bias"] = (D,)
+    sp[p + "mlp.fc1.weight"] = (mlp, D)
+    sp[p + "mlp.fc1.bias"] = (mlp,)
+    sp[p + "mlp.fc2.weight"] = (D, mlp)
+    sp[p + "mlp.fc2.bias"] = (D,)
+
+
+def _vit_entries(sp, D: int, mlp: int, depth: int, include_unused: bool) -> None:
+    """The transformer blocks and, with ``include_unused``, timm's final ``norm`` + 1000-class ``head``."""
     vp = "pretrained.model."
-    sp[vp + "cls_token"] = (1, 1, D)
-    sp[vp + "pos_embed"] = (1, 577, D)
-    sp[vp + "patch_embed.proj.weight"] = (D, 3, 16, 16)
-    sp[vp + "patch_embed.proj.bias"] = (D,)
     for l in range(depth):
-        p = f"{vp}blocks.{l}."
-        sp[p + "norm1.weight"] = (D,)
-        sp[p + "norm1.bias"] = (D,)
-        sp[p + "attn.qkv.weight"] = (3 * D, D)
-        sp[p + "attn.qkv.bias"] = (3 * D,)
-        sp[p + "attn.proj.weight"] = (D, D)
-        sp[p + "attn.proj.bias"] = (D,)
-        sp[p + "norm2.weight"] = (D,)
-        sp[p + "norm2.bias"] = (D,)
-        sp[p + "mlp.fc1.weight"] = (mlp, D)
-        sp[p + "mlp.fc1.bias"] = (mlp,)
-        sp[p + "mlp.fc2.weight"] = (D, mlp)
-        sp[p + "mlp.fc2.bias"] = (D,)
+        _vit_block_entries(sp, f"{vp}blocks.{l}.", D, mlp)
     if include_unused:
         sp[vp + "norm.weight"] = (D,)
         sp[vp + "norm.bias"] = (D,)
         sp[vp + "head.weight"] = (1000, D)
         sp[vp + "head.bias"] = (1000,)
-    feats = (256, 512, 1024, 1024)
-    for n, f in enumerate(feats, start=1):
-        p = f"pretrained.act_postprocess{n}."
-        sp[p + "0.project.0.weight"] = (D, 2 * D)
-        sp[p + "0.project.0.bias"] = (D,)
-        sp[p + "3.weight"] = (f, D, 1, 1)
-        sp[p + "3.bias"] = (f,)
-        if n == 1:
-            sp[p + "4.weight"] = (f, f, 4, 4)   # ConvTranspose2d(k=4, s=4): [Cin, Cout, kh, kw]
-            sp[p + "4.bias"] = (f,)
-        elif n == 2:
-            sp[p + "4.weight"] = (f, f, 2, 2)   # ConvTranspose2d(k=2, s=2)
-            sp[p + "4.bias"] = (f,)
-        elif n == 4:
-            sp[p + "4.weight"] = (f, f, 3, 3)   # Conv2d(k=3, s=2, p=1)
-            sp[p + "4.bias"] = (f,)
-    for i, c in enumerate(feats, start=1):
+
+
+def _readout_entries(sp, n: int, D: int, f: int, resample_k: int) -> None:
+    """``pretrained.act_postprocess<n>``: ProjectReadout, the 1x1 conv to ``f`` channels and, unless ``resample_k`` is 0,
+    the resampling layer with that kernel size (vit.py:176-260)."""
+    p = f"pretrained.act_postprocess{n}."
+    sp[p + "0.project.0.weight"] = (D, 2 * D)
+    sp[p + "0.project.0.bias"] = (D,)
+    sp[p + "3.weight"] = (f, D, 1, 1)
+    sp[p + "3.bias"] = (f,)
+    if resample_k:   # ConvTranspose2d(k, s=k): [Cin, Cout, k, k]; Conv2d(k=3, s=2, p=1): [Cout, Cin, k, k]; both f -> f
+        sp[p + "4.weight"] = (f, f, resample_k, resample_k)
+        sp[p + "4.bias"] = (f,)
+
+
+def _decoder_entries(sp, rn_in, num_channels: int, include_unused: bool) -> None:
+    """``scratch.*``: layerN_rn (input widths ``rn_in``), the four RefineNet blocks and the head (blocks.py, dpt_depth.py:91-99)."""
+    for i, c in enumerate(rn_in, start=1):
         sp[f"scratch.layer{i}_rn.weight"] = (FEATURES, c, 3, 3)
     for i in (1, 2, 3, 4):
         p = f"scratch.refinenet{i}."
@@ -94,6 +90,26 @@ def vitl16_state_dict_spec(num_channels: int = 1, include_unused: bool = True) -
     sp[oc + "2.bias"] = (32,)
     sp[oc + "4.weight"] = (num_channels, 32, 1, 1)
     sp[oc + "4.bias"] = (num_channels,)
+
+
+def vitl16_state_dict_spec(num_channels: int = 1, include_unused: bool = True) -> "OrderedDict[str, Tuple[int, ...]]":
+    """Ordered {key: shape} of ``DPTDepthModel(backbone='vitl16_384', num_channels=C)`` (DPT-Large: blocks.py:12-18,
+    vit.py:299-309 hooks [5,11,17,23], reassemble vit.py:176-260): timm ``vit_large_patch16_384`` under ``pretrained.model.``
+    (16x16 patch conv, 24 blocks of width 1024, 16 heads), four ProjectReadouts, ConvTranspose2d up-sampling in
+    act_postprocess1/2, and the same scratch / RefineNet / head modules with layerN_rn inputs [256, 512, 1024, 1024]."""
+    D, depth, mlp = 1024, 24, 4096
+    sp: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    vp = "pretrained.model."
+    sp[vp + "cls_token"] = (1, 1, D)
+    sp[vp + "pos_embed"] = (1, 577, D)
+    sp[vp + "patch_embed.proj.weight"] = (D, 3, 16, 16)
+    sp[vp + "patch_embed.proj.bias"] = (D,)
+    _vit_entries(sp, D, mlp, depth, include_unused)
+    feats = (256, 512, 1024, 1024)
+    # ConvTranspose2d(k=4, s=4), ConvTranspose2d(k=2, s=2), nothing, Conv2d(k=3, s=2, p=1)
+    for n, (f, k) in enumerate(zip(feats, (4, 2, 0, 3)), start=1):
+        _readout_entries(sp, n, D, f, k)
+    _decoder_entries(sp, feats, num_channels, include_unused)
     return sp
 
 
@@ -138,53 +154,10 @@ def state_dict_spec(num_channels: int = 3, include_unused: bool = True,
             cin = cout
     sp[vp + "patch_embed.proj.weight"] = (VIT_DIM, 1024, 1, 1)
     sp[vp + "patch_embed.proj.bias"] = (VIT_DIM,)
-    for l in range(VIT_DEPTH):
-        p = f"{vp}blocks.{l}."
-        sp[p + "norm1.weight"] = (VIT_DIM,)
-        sp[p + "norm1.bias"] = (VIT_DIM,)
-        sp[p + "attn.qkv.weight"] = (3 * VIT_DIM, VIT_DIM)
-        sp[p + "attn.qkv.bias"] = (3 * VIT_DIM,)
-        sp[p + "attn.proj.weight"] = (VIT_DIM, VIT_DIM)
-        sp[p + "attn.proj.bias"] = (VIT_DIM,)
-        sp[p + "norm2.weight"] = (VIT_DIM,)
-        sp[p + "norm2.bias"] = (VIT_DIM,)
-        sp[p + "mlp.fc1.weight"] = (VIT_MLP, VIT_DIM)
-        sp[p + "mlp.fc1.bias"] = (VIT_MLP,)
-        sp[p + "mlp.fc2.weight"] = (VIT_DIM, VIT_MLP)
-        sp[p + "mlp.fc2.bias"] = (VIT_DIM,)
-    if include_unused:
-        sp[vp + "norm.weight"] = (VIT_DIM,)
-        sp[vp + "norm.bias"] = (VIT_DIM,)
-        sp[vp + "head.weight"] = (1000, VIT_DIM)
-        sp[vp + "head.bias"] = (1000,)
-    for n in (3, 4):
-        p = f"pretrained.act_postprocess{n}."
-        sp[p + "0.project.0.weight"] = (VIT_DIM, 2 * VIT_DIM)
-        sp[p + "0.project.0.bias"] = (VIT_DIM,)
-        sp[p + "3.weight"] = (VIT_DIM, VIT_DIM, 1, 1)
-        sp[p + "3.bias"] = (VIT_DIM,)
-        if n == 4:
-            sp[p + "4.weight"] = (VIT_DIM, VIT_DIM, 3, 3)
-            sp[p + "4.bias"] = (VIT_DIM,)
-    for i, c in enumerate((256, 512, 768, 768), start=1):
-        sp[f"scratch.layer{i}_rn.weight"] = (FEATURES, c, 3, 3)
-    for i in (1, 2, 3, 4):
-        p = f"scratch.refinenet{i}."
-        sp[p + "out_conv.weight"] = (FEATURES, FEATURES, 1, 1)
-        sp[p + "out_conv.bias"] = (FEATURES,)
-        for u in (1, 2):
-            if u == 1 and i == 4 and not include_unused:
-                continue
-            for c in (1, 2):
-                sp[f"{p}resConfUnit{u}.conv{c}.weight"] = (FEATURES, FEATURES, 3, 3)
-                sp[f"{p}resConfUnit{u}.conv{c}.bias"] = (FEATURES,)
-    oc = "scratch.output_conv."
-    sp[oc + "0.weight"] = (FEATURES // 2, FEATURES, 3, 3)
-    sp[oc + "0.bias"] = (FEATURES // 2,)
-    sp[oc + "2.weight"] = (32, FEATURES // 2, 3, 3)
-    sp[oc + "2.bias"] = (32,)
-    sp[oc + "4.weight"] = (num_channels, 32, 1, 1)
-    sp[oc + "4.bias"] = (num_channels,)
+    _vit_entries(sp, VIT_DIM, VIT_MLP, VIT_DEPTH, include_unused)
+    _readout_entries(sp, 3, VIT_DIM, VIT_DIM, 0)
+    _readout_entries(sp, 4, VIT_DIM, VIT_DIM, 3)   # Conv2d(k=3, s=2, p=1)
+    _decoder_entries(sp, (256, 512, VIT_DIM, VIT_DIM), num_channels, include_unused)
     return sp
 
 

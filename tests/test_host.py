@@ -218,6 +218,35 @@ def test_config_validation_and_arena_scaling():
         assert e.workspace_bytes <= one.workspace_bytes * 1.35
 
 
+def test_arena_layout_lists_every_planned_buffer():
+    """dptx_debug_arena_layout (and with it the per-buffer checksums) lists exactly what the arena plan takes: the listed
+    buffers tile the whole-batch plan from offset 0 without a gap -- a buffer that was planned but not listed would leave
+    one -- and they appear in the same order, strictly ascending, inside a sub-batch region (host-only handles)."""
+    import ctypes
+    from omnidata_amd.engine import Engine
+    for cfg in (dict(streams=1), dict(streams=4), dict(max_hw=(512, 640))):
+        e = Engine(num_channels=3, max_batch=7, device_id=None, **cfg)
+        n = e.lib.dptx_debug_arena_layout(e.h, None, 0)
+        text = ctypes.create_string_buffer(n)
+        e.lib.dptx_debug_arena_layout(e.h, text, n)
+        e.close()
+        lines = [ln.split() for ln in text.value.decode().splitlines()]
+        head = {f[0]: int(f[1]) for f in lines if f[0] != "buf"}
+        bufs = [(f[1], int(f[2]), int(f[3]), int(f[4])) for f in lines if f[0] == "buf"]   # name, off, bytes, off2
+        names = [b[0] for b in bufs]
+        assert len(bufs) > 0 and len(set(names)) == len(names), cfg
+        by_off = sorted(bufs, key=lambda b: b[1])
+        assert by_off[0][1] == 0, cfg
+        for cur, nxt in zip(by_off, by_off[1:]):
+            assert cur[1] + cur[2] == nxt[1], (cfg, cur, nxt)
+        assert by_off[-1][1] + by_off[-1][2] <= head["arena_single"], cfg
+        by_off2 = sorted(bufs, key=lambda b: b[3])
+        assert [b[0] for b in by_off2] == [b[0] for b in by_off], cfg
+        for cur, nxt in zip(by_off2, by_off2[1:]):
+            assert cur[3] < nxt[3], (cfg, cur, nxt)
+        assert by_off2[-1][3] < head["half_region"], cfg
+
+
 class _FakeCudaTensor(torch.Tensor):
     """A CPU tensor that claims to live on the GPU: lets the host-side control flow of DPTDepthModel.forward run here."""
     @property
