@@ -92,8 +92,7 @@ def build_replicated_engine(state_dict_fn, num_channels: int, max_batch: int, dt
         got = broadcast_blob(blob, eng.packed_bytes, device, src)
         torch.cuda.synchronize(device)
         ms = 1e3 * (time.perf_counter() - t0)
-        rx = Engine(num_channels=num_channels, max_batch=1, dtype=dtype, device_id=device_index, dual=dual, x3_groups=x3_groups,
-                    backbone=backbone)
+        rx = Engine(**{**eng.config_kwargs(), "max_batch": 1})
         rx.import_packed(got)
         same = bool(torch.equal(rx.export_packed(), blob))
         rx.close()

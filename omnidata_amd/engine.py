@@ -12,9 +12,15 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DPTX_LIB") or os.path.join(_HERE, "libdptx.so")  # $DPTX_LIB: an experiment build (build.py)
 
+# The tables below mirror the enums of include/dptx.h (tests/test_host.py compares them with the header).
 DTYPES = {"bf16": 0, "fp16": 1, "bf16x3": 2, "fp16x3": 3, "mixed": 4, "fp8": 5}
+TWO_PLANE_DTYPES = frozenset(("bf16x3", "fp16x3", "mixed", "fp8"))  # hi / lo (fp8: 16-bit / e4m3) planes of weights and arena
 # layer groups of dptx_config.x3_groups (include/dptx.h DPTX_GROUP_*)
-GROUPS = {"resnet": 1, "embed": 2, "vit": 4, "reassemble": 8, "rn": 16, "fusion": 32, "head": 64}
+GROUPS = {"resnet": 1, "embed": 2, "vit": 4, "reassemble": 8, "rn": 16, "fusion": 32, "head": 64, "all": 127}
+# dptx_config.flags (include/dptx.h DPTX_FLAG_*): no LayerNorm fold; group-level precision policy only; fp32 token stream in the
+# single-pass dtypes; no fp16 range scan; dtype fp8 with all 19 eligible convs on e4m3; dtype fp8 with qkv / fc1 / fc2 of the ViT
+# blocks on e4m3
+FLAGS = {"no_ln_fold": 1, "group_policy": 2, "fp32_stream": 4, "no_range_check": 8, "fp8_all": 16, "fp8_vit": 32}
 
 
 def groups_mask(names) -> int:
@@ -23,7 +29,12 @@ def groups_mask(names) -> int:
         return names
     if isinstance(names, str):
         names = [n for n in names.replace(",", "+").split("+") if n]
-    return sum(GROUPS[n] for n in set(names))
+    mask = 0
+    for n in names:
+        mask |= GROUPS[n]
+    return mask
+
+
 # include/dptx.h DPTX_BACKBONE_*
 BACKBONE_IDS = {"vitb_rn50_384": 0, "vitl16_384": 1}
 ERRORS = {0: "ok", -1: "invalid argument / call order", -2: "state_dict key error", -3: "HIP error",
@@ -195,10 +206,9 @@ def probe_stream_overlap(stream_a, stream_b, device_index: int = 0, spin_us: int
     return float(r.value)
 
 
-def _check_out(out: torch.Tensor, shape, device, dtype=torch.float32):
-    if (out.dtype != dtype or not out.is_contiguous() or out.device != device or tuple(out.shape) != tuple(shape)):
-        raise ValueError(f"out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got "
-                         f"{out.dtype} {tuple(out.shape)} on {out.device} (contiguous={out.is_contiguous()})")
+def check_image_shape(x: torch.Tensor):
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
+        raise ValueError(f"expected [B,3,H,W] with H, W multiples of 32 (384x384 is the trained size), got {tuple(x.shape)}")
 
 
 class Engine:
@@ -219,13 +229,12 @@ class Engine:
         cfg.streams = int(streams)
         cfg.x3_groups = groups_mask(x3_groups)  # dtype "mixed": groups that run 3 MFMAs per product (0 = all but the ViT blocks)
         cfg.backbone = BACKBONE_IDS[backbone]
-        cfg.flags = int(flags)  # include/dptx.h DPTX_FLAG_* (1: no LayerNorm fold, 2: group-level precision policy only, 4: fp32 token stream in the single-pass dtypes, 8: no fp16 range scan, 16: dtype fp8 with all 19 eligible convs on e4m3, 32: dtype fp8 with qkv / fc1 / fc2 of the ViT blocks on e4m3)
+        cfg.flags = int(flags)  # an OR of FLAGS values
         self.cfg = cfg
         self.fp8_calibrated = False
         self.fp8_scales = None  # the scales installed last (calibrate_fp8 / set_fp8_calibration): what a rebuilt engine re-installs
         # per-layer precision overrides made through set_layer_precision, in call order: handle state that is NOT part of the
-        # packed weights, so every handle that is meant to compute what this one computes (ForwardPipeline.from_engine, an
-        # engine rebuilt for a larger input) replays them
+        # packed weights, so every handle that is meant to compute what this one computes replays them (follow)
         self.layer_precision: Dict[str, int] = {}
         # streams = 0 (the default): the intra-forward schedule is MEASURED at the first forward of at least AUTO_TUNE_MIN_BATCH
         # images (include/dptx.h dptx_tune_schedule; a few extra forwards and one host synchronisation, once per handle)
@@ -254,6 +263,23 @@ class Engine:
             self.close()
         except Exception:
             pass
+
+    def config_kwargs(self) -> dict:
+        """The constructor keywords that reproduce this handle's configuration: Engine(**e.config_kwargs()).cfg == e.cfg."""
+        c = self.cfg
+        return dict(num_channels=c.num_channels, max_batch=c.max_batch, dtype=self.dtype,
+                    device_id=None if c.device_id < 0 else c.device_id, non_negative=bool(c.non_negative), ws_form=c.ws_form,
+                    ws_eps=c.ws_eps, max_hw=(c.max_height, c.max_width), dual=bool(c.dual_task), streams=c.streams,
+                    x3_groups=c.x3_groups, backbone=self.backbone, flags=c.flags)
+
+    def follow(self, owner: "Engine"):
+        """Makes this handle (created from owner.config_kwargs(), possibly with another max_batch / streams) compute what
+        `owner` computes: its weights in place, its per-layer precision and its fp8 scales -- the handle state that is not
+        part of the configuration."""
+        self.share_weights_from(owner)
+        self.copy_layer_precision_from(owner)
+        if owner.fp8_scales is not None:
+            self.set_fp8_calibration(owner.fp8_scales)
 
     # ---- weights
     def load_state_dict(self, sd: Dict[str, torch.Tensor]):
@@ -322,9 +348,50 @@ class Engine:
     # ---- compute
     AUTO_TUNE_MIN_BATCH = 8
 
+    def _image(self, x: torch.Tensor) -> torch.Tensor:
+        """The input contract of every entry point that reads images: a [B,3,H,W] tensor on this handle's device, returned
+        contiguous in an element type the kernels read (fp32 -- the reference's convention --, bf16 and fp16 as they are)."""
+        if not x.is_cuda:
+            raise RuntimeError("dptx forward needs a CUDA(HIP) tensor; there is no CPU fallback")
+        check_image_shape(x)
+        if x.dtype not in IO_DTYPES:
+            x = x.float()
+        x = x.contiguous()
+        if x.device.index != self.cfg.device_id:
+            raise RuntimeError(f"input is on {x.device}, the engine was created for cuda:{self.cfg.device_id}")
+        return x
+
+    def _outputs(self, x: torch.Tensor, outs: tuple) -> tuple:
+        """One output per entry of `outs` -- (out,) of the primary head or (normals, depth) of a dual handle --, allocated in
+        the input's element type where the caller passed None and checked where it passed a tensor.  `x` comes from _image."""
+        B, _, H, W = x.shape
+        res = []
+        for c, out in zip((self.cfg.num_channels,) if len(outs) == 1 else (3, 1), outs):
+            if out is None:
+                out = torch.empty(B, c, H, W, dtype=x.dtype, device=x.device)
+            elif out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device or tuple(out.shape) != (B, c, H, W):
+                raise ValueError(f"out must be a contiguous {x.dtype} tensor of shape {(B, c, H, W)} on {x.device}, got "
+                                 f"{out.dtype} {tuple(out.shape)} on {out.device} (contiguous={out.is_contiguous()})")
+            res.append(out)
+        return tuple(res)
+
+    def _run(self, x: torch.Tensor, outs: tuple) -> tuple:
+        """Enqueues the forward of `x` (from _image) into `outs` (from _outputs) on the current stream."""
+        B, _, H, W = x.shape
+        if not self._schedule_tuned and B >= self.AUTO_TUNE_MIN_BATCH:
+            self.tune_schedule(x, *outs)
+        io, st = IO_DTYPES[x.dtype], _stream(x.device)
+        if len(outs) == 1:
+            self._check(self.lib.dptx_forward_hw(self.h, x.data_ptr(), io, outs[0].data_ptr(), B, H, W, st), "forward")
+        else:
+            self._check(self.lib.dptx_forward_dual(self.h, x.data_ptr(), io, outs[0].data_ptr(), outs[1].data_ptr(), B, H, W, st),
+                        "forward_dual")
+        return outs
+
     def tune_schedule(self, x: torch.Tensor, out: torch.Tensor, out_depth: Optional[torch.Tensor] = None, reps: int = 2) -> dict:
         """Times this batch's forward under both intra-forward schedules and keeps the faster one (include/dptx.h
         dptx_tune_schedule); blocks until done.  `out` (and `out_depth`) receive a valid result."""
+        x = self._image(x)
         B, _, H, W = x.shape
         self._check(self.lib.dptx_tune_schedule(self.h, x.data_ptr(), IO_DTYPES[x.dtype], out.data_ptr(), _ptr(out_depth), B, H, W,
                                                 int(reps), _stream(x.device)), "tune_schedule")
@@ -338,52 +405,14 @@ class Engine:
         return {"split": bool(sp.value), "tuned": bool(tu.value), "ms_single": round(a.value, 4), "ms_split": round(b.value, 4)}
 
     def forward(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if not x.is_cuda:
-            raise RuntimeError("dptx forward needs a CUDA(HIP) tensor; there is no CPU fallback")
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
-            raise ValueError(f"expected [B,3,H,W] with H, W multiples of 32 (384x384 is the trained size), got {tuple(x.shape)}")
-        if x.dtype not in IO_DTYPES:  # fp32 (the reference's convention), bf16 and fp16 images are read as they are
-            x = x.float()
-        x = x.contiguous()
-        B, _, H, W = x.shape
-        if x.device.index != self.cfg.device_id:
-            raise RuntimeError(f"input is on {x.device}, the engine was created for cuda:{self.cfg.device_id}")
-        if out is None:  # the result comes back in the input's element type
-            out = torch.empty(B, self.cfg.num_channels, H, W, dtype=x.dtype, device=x.device)
-        else:
-            _check_out(out, (B, self.cfg.num_channels, H, W), x.device, x.dtype)
-        if not self._schedule_tuned and B >= self.AUTO_TUNE_MIN_BATCH:
-            self.tune_schedule(x, out)
-        self._check(self.lib.dptx_forward_hw(self.h, x.data_ptr(), IO_DTYPES[x.dtype], out.data_ptr(), B, H, W,
-                                             _stream(x.device)), "forward")
-        return out
+        x = self._image(x)
+        return self._run(x, self._outputs(x, (out,)))[0]
 
     def forward_dual(self, x: torch.Tensor, out_normal: Optional[torch.Tensor] = None,
                      out_depth: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """One encoder pass, two decoders (handle created with dual=True): ([B,3,H,W] normals, [B,1,H,W] depth)."""
-        if not x.is_cuda:
-            raise RuntimeError("dptx forward needs a CUDA(HIP) tensor; there is no CPU fallback")
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
-            raise ValueError(f"expected [B,3,H,W] with H, W multiples of 32, got {tuple(x.shape)}")
-        if x.dtype not in IO_DTYPES:
-            x = x.float()
-        x = x.contiguous()
-        B, _, H, W = x.shape
-        if x.device.index != self.cfg.device_id:
-            raise RuntimeError(f"input is on {x.device}, the engine was created for cuda:{self.cfg.device_id}")
-        if out_normal is None:
-            out_normal = torch.empty(B, 3, H, W, dtype=x.dtype, device=x.device)
-        else:
-            _check_out(out_normal, (B, 3, H, W), x.device, x.dtype)
-        if out_depth is None:
-            out_depth = torch.empty(B, 1, H, W, dtype=x.dtype, device=x.device)
-        else:
-            _check_out(out_depth, (B, 1, H, W), x.device, x.dtype)
-        if not self._schedule_tuned and B >= self.AUTO_TUNE_MIN_BATCH:
-            self.tune_schedule(x, out_normal, out_depth)
-        self._check(self.lib.dptx_forward_dual(self.h, x.data_ptr(), IO_DTYPES[x.dtype], out_normal.data_ptr(), out_depth.data_ptr(), B, H, W,
-                                               _stream(x.device)), "forward_dual")
-        return out_normal, out_depth
+        x = self._image(x)
+        return self._run(x, self._outputs(x, (out_normal, out_depth)))
 
     def set_layer_precision(self, conv_weight_key: str, mfmas: int):
         """dtype 'mixed': run one decoder convolution with 1 or 3 MFMAs per product (include/dptx.h)."""
@@ -400,20 +429,15 @@ class Engine:
     def calibrate_fp8(self, x: torch.Tensor):
         """Measures max |x| of every tensor that gets an e4m3 copy on this batch (one forward with a bf16 decoder) and sets
         the tensors' power-of-two scales.  Returns that forward's result(s)."""
-        if not x.is_cuda:
-            raise RuntimeError("dptx needs a CUDA(HIP) tensor; there is no CPU fallback")
-        if x.dtype not in IO_DTYPES:
-            x = x.float()
-        x = x.contiguous()
+        x = self._image(x)
         B, _, H, W = x.shape
         dual = bool(self.cfg.dual_task)
-        y = torch.empty(B, 3 if dual else self.cfg.num_channels, H, W, dtype=x.dtype, device=x.device)
-        y2 = torch.empty(B, 1, H, W, dtype=x.dtype, device=x.device) if dual else None
-        self._check(self.lib.dptx_calibrate_fp8(self.h, x.data_ptr(), IO_DTYPES[x.dtype], y.data_ptr(), _ptr(y2), B, H, W,
-                                                _stream(x.device)), "calibrate_fp8")
+        ys = self._outputs(x, (None, None) if dual else (None,))
+        self._check(self.lib.dptx_calibrate_fp8(self.h, x.data_ptr(), IO_DTYPES[x.dtype], ys[0].data_ptr(), _ptr(ys[1] if dual else None),
+                                                B, H, W, _stream(x.device)), "calibrate_fp8")
         self.fp8_calibrated = True
         self.fp8_scales = self.fp8_calibration()[0]
-        return (y, y2) if dual else y
+        return ys if dual else ys[0]
 
     def fp8_calibration(self):
         """(scales, max |x|) of the e4m3 tensors of the last forward, in launch order."""
@@ -458,7 +482,7 @@ class Engine:
         if rc < 0:
             self._check(rc, "debug_arena_checksums")
         nbuf = len(self.arena_layout()["bufs"])
-        planes = 2 if self.dtype in ("bf16x3", "fp16x3", "mixed", "fp8") else 1
+        planes = 2 if self.dtype in TWO_PLANE_DTYPES else 1
         return out.view(planes, n // (planes * nbuf), nbuf)
 
     def arena_read(self, offset: int, nbytes: int) -> np.ndarray:

@@ -16,14 +16,14 @@ from typing import Dict, Optional
 import torch
 import torch.nn as nn
 
-from .engine import Engine
+from .engine import FLAGS, IO_DTYPES, Engine, check_image_shape
 from .weights import (compose_dual_state_dict, dual_state_dict_spec, random_dual_state_dict, random_state_dict,
                       read_checkpoint, state_dict_spec, BACKBONES)
 
 
 def _io_dtype(x: torch.Tensor) -> torch.dtype:
     """Result element type: the input's when the engine reads it directly (fp32 / bf16 / fp16), else fp32."""
-    return x.dtype if x.dtype in (torch.float32, torch.bfloat16, torch.float16) else torch.float32
+    return x.dtype if x.dtype in IO_DTYPES else torch.float32
 
 
 class _Node(nn.Module):
@@ -37,7 +37,7 @@ class BaseModel(nn.Module):
 
 
 class _EngineGuards:
-    """What DPTDepthModel and DPTDualTaskModel share around an engine call: the fp16 range guard and the fp8 calibration.
+    """What the models do around an engine call (_EngineCore.forward): the fp16 range guard and the fp8 calibration.
 
     Range guard (``overflow_fallback``, default on).  The fp16-plane modes ('mixed', 'fp16x3', 'fp16') cannot represent
     |x| > 65504 (two planes: ~1.3e5) and nothing inside the forward clamps; the parity claims are validated on synthetic
@@ -139,7 +139,117 @@ class _EngineGuards:
         return True
 
 
-class DPTDepthModel(_EngineGuards, BaseModel):
+class _EngineCore(_EngineGuards, nn.Module):
+    """What DPTDepthModel and DPTDualTaskModel share: parameters registered under the reference's key names, one Engine kept
+    in sync with them (rebuilt for new weights, ``.to()``, another dtype or a larger input), and the forward around it.  A
+    model class adds its constructor contract and four hooks: ``_out_channels`` (channels of each output, the primary head
+    first), ``_engine_kwargs`` (Engine keywords of its own), ``_run_chunk`` (the engine call) and ``_result``."""
+
+    def __init__(self, init: Dict[str, torch.Tensor], keys, dtype: str, max_batch: int, non_negative: bool, x3_groups,
+                 overflow_fallback: bool, fp8_all: bool, fp8_vit: bool):
+        super().__init__()
+        self.fp8_all = bool(fp8_all)   # dtype 'fp8': all 19 eligible decoder convs on e4m3 (lossy) instead of the six safe ones
+        self.fp8_vit = bool(fp8_vit)   # dtype 'fp8': qkv / fc1 / fc2 of the ViT blocks on e4m3 too (include/dptx.h DPTX_FLAG_FP8_VIT)
+        self.non_negative = bool(non_negative)
+        self.engine_dtype = dtype
+        self.x3_groups = x3_groups
+        self._init_guards(overflow_fallback)
+        self.max_batch = max(1, min(int(max_batch), 48))  # engine limit; larger batches are chunked in forward()
+        self.max_hw = (384, 384)  # arena is planned for this input size; grows on demand (forward_flex, vit.py:119)
+        self._register_from(init, keys)
+        self._engine: Optional[Engine] = None
+        self._engine_key = None
+        self._pipe, self._pipe_key = None, None   # forward_pipelined's cached ForwardPipeline
+        self._weights_version = 0
+
+    def _register_from(self, init: Dict[str, torch.Tensor], keys):
+        for key in keys:
+            *mods, leaf = key.split(".")
+            node = self
+            for m in mods:
+                if not hasattr(node, m):
+                    node.add_module(m, _Node())
+                node = getattr(node, m)
+            node.register_parameter(leaf, nn.Parameter(init[key], requires_grad=False))
+
+    # ---- keep the engine in sync with the parameters
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        r = super().load_state_dict(state_dict, strict=strict, **kw)
+        self._weights_version += 1
+        self._values_version += 1
+        return r
+
+    def _apply(self, fn, *a, **kw):
+        r = super()._apply(fn, *a, **kw)
+        self._weights_version += 1
+        return r
+
+    def _chunk(self) -> int:
+        """Images per engine call: every activation must stay below 2 GB (32-bit buffer offsets, include/dptx.h)."""
+        return max(1, min(self.max_batch, ((1 << 31) - 1) // (self.max_hw[0] * self.max_hw[1] * 256)))
+
+    @property
+    def engine(self) -> Optional[Engine]:
+        return self._engine
+
+    def _key(self, device_index: int):
+        return (device_index, self._weights_version, self.engine_dtype, self._chunk(), self.max_hw)
+
+    def _get_engine(self, device: torch.device) -> Engine:
+        key = self._key(device.index if device.index is not None else torch.cuda.current_device())
+        if self._engine is None or self._engine_key != key:
+            self._drop_pipeline()   # its handles read the old engine's weights and arena plan
+            if self._engine is not None:
+                self._engine.close()
+            eng = Engine(num_channels=self._out_channels()[0], max_batch=self._chunk(), dtype=self.engine_dtype, device_id=key[0],
+                         non_negative=self.non_negative, max_hw=self.max_hw, x3_groups=self.x3_groups,
+                         flags=sum(FLAGS[n] for n in ("fp8_all", "fp8_vit") if getattr(self, n)), **self._engine_kwargs())
+            eng.load_state_dict(super().state_dict())
+            self._engine, self._engine_key = eng, key
+        return self._engine
+
+    def adopt_engine(self, engine: Engine, device_index: int):
+        """Use an engine whose packed weights arrived by broadcast (multi-GPU start-up)."""
+        self._engine, self._engine_key = engine, self._key(device_index)
+
+    def _drop_pipeline(self):
+        if getattr(self, "_pipe", None) is not None:
+            self._pipe.synchronize()
+            self._pipe.close()
+        self._pipe, self._pipe_key = None, None
+
+    def _check_input(self, x: torch.Tensor):
+        """-> (B, H, W) of a [B,3,H,W] device tensor with H, W multiples of 32; anything else raises."""
+        if not x.is_cuda:
+            raise RuntimeError(f"omnidata_amd.{type(self).__name__} runs only on an AMD GPU (HIP); got a CPU tensor. "
+                               "There is no CPU fallback -- use the reference implementation on CPU.")
+        check_image_shape(x)
+        return x.shape[0], x.shape[2], x.shape[3]
+
+    def _alloc(self, x: torch.Tensor):
+        B, _, H, W = x.shape
+        return tuple(torch.empty(B, c, H, W, dtype=_io_dtype(x), device=x.device) for c in self._out_channels())
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor):
+        B, H, W = self._check_input(x)
+        if H * W > self.max_hw[0] * self.max_hw[1]:
+            self.max_hw = (H, W)  # re-plans the arena (and re-packs the weights) once for the larger size
+        eng = self._get_engine(x.device)
+        step = self._chunk()
+        self._ensure_fp8(eng, x[:step])
+        ys = self._alloc(x)
+
+        def run():
+            for i in range(0, B, step):
+                self._run_chunk(eng, x[i:i + step], *(y[i:i + step] for y in ys))
+        run()
+        if self._range_fallback_needed(eng, x, run):
+            return self.forward(x)  # on the bf16-plane engine
+        return self._result(*ys)
+
+
+class DPTDepthModel(_EngineCore, BaseModel):
     """Drop-in for ``DPTDepthModel(backbone={'vitb_rn50_384' | 'vitl16_384'}, num_channels={1,3})``
     (DPT-Hybrid, the published omnidata configuration, and DPT-Large, demo.py:81 / dpt_depth.py:41-45).
 
@@ -163,9 +273,6 @@ class DPTDepthModel(_EngineGuards, BaseModel):
                  channels_last: bool = False, use_bn: bool = False, dtype: str = "mixed",
                  max_batch: int = 32, init_seed: int = 0, x3_groups=0, overflow_fallback: bool = True, fp8_all: bool = False,
                  fp8_vit: bool = False):
-        super().__init__()
-        self.fp8_all = bool(fp8_all)   # dtype 'fp8': all 19 eligible decoder convs on e4m3 (lossy) instead of the six safe ones
-        self.fp8_vit = bool(fp8_vit)   # dtype 'fp8': qkv / fc1 / fc2 of the ViT blocks on e4m3 too (include/dptx.h DPTX_FLAG_FP8_VIT)
         if backbone not in BACKBONES:
             # blocks.py:42-44: unknown backbones print and assert
             print(f"Backbone '{backbone}' not implemented")
@@ -175,37 +282,25 @@ class DPTDepthModel(_EngineGuards, BaseModel):
                                       "omnidata DPT-Hybrid configuration) is supported")
         if num_channels not in (1, 3):
             raise ValueError("num_channels must be 1 (depth) or 3 (surface normals)")
+        super().__init__(random_state_dict(init_seed, num_channels, backbone=backbone), state_dict_spec(num_channels, backbone=backbone),
+                         dtype, max_batch, non_negative, x3_groups, overflow_fallback, fp8_all, fp8_vit)
         self.num_channels = num_channels
         self.backbone = backbone
-        self.non_negative = bool(non_negative)
         self.channels_last = channels_last  # accepted and, as in the reference (dpt_depth.py:68-69), a no-op
-        self.engine_dtype = dtype
-        self.x3_groups = x3_groups
-        self._init_guards(overflow_fallback)
-        self.max_batch = max(1, min(int(max_batch), 48))  # engine limit; larger batches are chunked in forward()
-        self.max_hw = (384, 384)  # arena is planned for this input size; grows on demand (forward_flex, vit.py:119)
-        init = random_state_dict(init_seed, num_channels, backbone=backbone)
-        for key, shape in state_dict_spec(num_channels, backbone=backbone).items():
-            *mods, leaf = key.split(".")
-            node = self
-            for m in mods:
-                if not hasattr(node, m):
-                    node.add_module(m, _Node())
-                node = getattr(node, m)
-            node.register_parameter(leaf, nn.Parameter(init[key], requires_grad=False))
-        self._engine: Optional[Engine] = None
-        self._engine_key = None
-        self._pipe, self._pipe_key = None, None   # forward_pipelined's cached ForwardPipeline
-        self._weights_version = 0
         if path is not None:
             self.load(path)
 
-    # ---- keep the engine in sync with the parameters
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._weights_version += 1
-        self._values_version += 1
-        return r
+    def _out_channels(self):
+        return (self.num_channels,)
+
+    def _engine_kwargs(self):
+        return dict(backbone=self.backbone)
+
+    def _run_chunk(self, eng, x, y):
+        eng.forward(x, out=y)
+
+    def _result(self, y):
+        return y.squeeze(dim=1)  # dpt_depth.py:106-107
 
     @torch.no_grad()
     def forward_pipelined(self, batches, depth: int = 2):
@@ -240,22 +335,18 @@ class DPTDepthModel(_EngineGuards, BaseModel):
                 del pending[:]
                 self._drop_pipeline()
                 return [self.forward(e[0]) for e in redo]   # on the bf16-plane engine (forward squeezes)
-            return [y.squeeze(dim=1)]
+            return [self._result(y)]
 
         try:
             for x in batches:
-                if not x.is_cuda:
-                    raise RuntimeError("omnidata_amd.DPTDepthModel runs only on an AMD GPU (HIP); there is no CPU fallback")
-                if x.dim() != 4 or x.shape[2] % 32 or x.shape[3] % 32:
-                    raise ValueError(f"expected [B,3,H,W] with H, W multiples of 32, got {tuple(x.shape)}")
-                B, _, H, W = x.shape
+                B, H, W = self._check_input(x)
                 if H * W > self.max_hw[0] * self.max_hw[1]:
                     for e in pending:     # the arena is re-planned: finish what runs on the old one first
                         finish(e)
                     self.max_hw = (H, W)
                 pipe = self._get_pipeline(x.device, depth, x)
                 step = self._chunk()
-                y = torch.empty(B, self.num_channels, H, W, dtype=_io_dtype(x), device=x.device)
+                y, = self._alloc(x)
                 pending.append((x, y, [pipe.submit(x[i:i + step], out=y[i:i + step]) for i in range(0, B, step)]))
                 if len(pending) >= depth:
                     for r in retire(pending.pop(0)):
@@ -281,70 +372,8 @@ class DPTDepthModel(_EngineGuards, BaseModel):
             self._pipe, self._pipe_key = ForwardPipeline.from_engine(eng, depth=depth), key
         return self._pipe
 
-    def _drop_pipeline(self):
-        if getattr(self, "_pipe", None) is not None:
-            self._pipe.synchronize()
-            self._pipe.close()
-        self._pipe, self._pipe_key = None, None
 
-    def _apply(self, fn, *a, **kw):
-        r = super()._apply(fn, *a, **kw)
-        self._weights_version += 1
-        return r
-
-    def _get_engine(self, device: torch.device) -> Engine:
-        key = (device.index if device.index is not None else torch.cuda.current_device(),
-               self._weights_version, self.engine_dtype, self._chunk(), self.max_hw)
-        if self._engine is None or self._engine_key != key:
-            self._drop_pipeline()   # its handles read the old engine's weights and arena plan
-            if self._engine is not None:
-                self._engine.close()
-            eng = Engine(num_channels=self.num_channels, max_batch=self._chunk(), dtype=self.engine_dtype,
-                         device_id=key[0], non_negative=self.non_negative, max_hw=self.max_hw,
-                         x3_groups=self.x3_groups, backbone=self.backbone,
-                         flags=(16 if self.fp8_all else 0) | (32 if self.fp8_vit else 0))
-            eng.load_state_dict(super().state_dict())
-            self._engine, self._engine_key = eng, key
-        return self._engine
-
-    def _chunk(self) -> int:
-        """Images per engine call: every activation must stay below 2 GB (32-bit buffer offsets, include/dptx.h)."""
-        return max(1, min(self.max_batch, ((1 << 31) - 1) // (self.max_hw[0] * self.max_hw[1] * 256)))
-
-    @property
-    def engine(self) -> Optional[Engine]:
-        return self._engine
-
-    def adopt_engine(self, engine: Engine, device_index: int):
-        """Use an engine whose packed weights arrived by broadcast (multi-GPU start-up)."""
-        self._engine = engine
-        self._engine_key = (device_index, self._weights_version, self.engine_dtype, self._chunk(), self.max_hw)
-
-    @torch.no_grad()
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if not x.is_cuda:
-            raise RuntimeError("omnidata_amd.DPTDepthModel runs only on an AMD GPU (HIP); got a CPU tensor. "
-                               "There is no CPU fallback -- use the reference implementation on CPU.")
-        if x.dim() != 4 or x.shape[2] % 32 or x.shape[3] % 32:
-            raise ValueError(f"expected [B,3,H,W] with H, W multiples of 32, got {tuple(x.shape)}")
-        B, _, H, W = x.shape
-        if H * W > self.max_hw[0] * self.max_hw[1]:
-            self.max_hw = (H, W)  # re-plans the arena (and re-packs the weights) once for the larger size
-        eng = self._get_engine(x.device)
-        step = self._chunk()
-        self._ensure_fp8(eng, x[:step])
-        y = torch.empty(B, self.num_channels, H, W, dtype=_io_dtype(x), device=x.device)
-
-        def run():
-            for i in range(0, B, step):
-                eng.forward(x[i:i + step], out=y[i:i + step])
-        run()
-        if self._range_fallback_needed(eng, x, run):
-            return self.forward(x)  # on the bf16-plane engine
-        return y.squeeze(dim=1)  # dpt_depth.py:106-107
-
-
-class DPTDualTaskModel(_EngineGuards, nn.Module):
+class DPTDualTaskModel(_EngineCore):
     """Surface normals AND depth from one encoder pass (BASELINE.json configs[4]).
 
     ``pretrained.*`` (ResNetV2-50 + ViT-B + read-outs) runs once; ``scratch.*`` (normal decoder, 3 channels) and
@@ -358,27 +387,8 @@ class DPTDualTaskModel(_EngineGuards, nn.Module):
 
     def __init__(self, dtype: str = "mixed", max_batch: int = 32, init_seed: int = 0, non_negative: bool = True,
                  x3_groups=0, overflow_fallback: bool = True, fp8_all: bool = False, fp8_vit: bool = False):
-        super().__init__()
-        self._init_guards(overflow_fallback)
-        self.fp8_all = bool(fp8_all)
-        self.fp8_vit = bool(fp8_vit)
-        self.engine_dtype = dtype
-        self.x3_groups = x3_groups
-        self.max_batch = max(1, min(int(max_batch), 48))
-        self.max_hw = (384, 384)
-        self.non_negative = bool(non_negative)
-        init = random_dual_state_dict(init_seed)
-        for key in dual_state_dict_spec():
-            *mods, leaf = key.split(".")
-            node = self
-            for m in mods:
-                if not hasattr(node, m):
-                    node.add_module(m, _Node())
-                node = getattr(node, m)
-            node.register_parameter(leaf, nn.Parameter(init[key], requires_grad=False))
-        self._engine: Optional[Engine] = None
-        self._engine_key = None
-        self._weights_version = 0
+        super().__init__(random_dual_state_dict(init_seed), dual_state_dict_spec(), dtype, max_batch, non_negative, x3_groups,
+                         overflow_fallback, fp8_all, fp8_vit)
 
     @classmethod
     def from_single_task(cls, normal_sd: Dict[str, torch.Tensor], depth_sd: Dict[str, torch.Tensor],
@@ -387,57 +397,16 @@ class DPTDualTaskModel(_EngineGuards, nn.Module):
         m.load_state_dict(compose_dual_state_dict(normal_sd, depth_sd, backbone))
         return m
 
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._weights_version += 1
-        self._values_version += 1
-        return r
+    def _out_channels(self):
+        return (3, 1)
 
-    def _apply(self, fn, *a, **kw):
-        r = super()._apply(fn, *a, **kw)
-        self._weights_version += 1
-        return r
+    def _engine_kwargs(self):
+        return dict(dual=True)
 
-    def _chunk(self) -> int:
-        return max(1, min(self.max_batch, ((1 << 31) - 1) // (self.max_hw[0] * self.max_hw[1] * 256)))
+    def _run_chunk(self, eng, x, yn, yd):
+        eng.forward_dual(x, out_normal=yn, out_depth=yd)
 
-    @property
-    def engine(self) -> Optional[Engine]:
-        return self._engine
-
-    def _get_engine(self, device: torch.device) -> Engine:
-        key = (device.index if device.index is not None else torch.cuda.current_device(),
-               self._weights_version, self.engine_dtype, self._chunk(), self.max_hw)
-        if self._engine is None or self._engine_key != key:
-            if self._engine is not None:
-                self._engine.close()
-            eng = Engine(num_channels=3, max_batch=self._chunk(), dtype=self.engine_dtype, device_id=key[0],
-                         non_negative=self.non_negative, max_hw=self.max_hw, dual=True, x3_groups=self.x3_groups,
-                         flags=(16 if self.fp8_all else 0) | (32 if self.fp8_vit else 0))
-            eng.load_state_dict(super().state_dict())
-            self._engine, self._engine_key = eng, key
-        return self._engine
-
-    @torch.no_grad()
-    def forward(self, x: torch.Tensor):
-        if not x.is_cuda:
-            raise RuntimeError("omnidata_amd.DPTDualTaskModel runs only on an AMD GPU (HIP); there is no CPU fallback")
-        if x.dim() != 4 or x.shape[2] % 32 or x.shape[3] % 32:
-            raise ValueError(f"expected [B,3,H,W] with H, W multiples of 32, got {tuple(x.shape)}")
-        B, _, H, W = x.shape
-        if H * W > self.max_hw[0] * self.max_hw[1]:
-            self.max_hw = (H, W)
-        eng = self._get_engine(x.device)
-        step = self._chunk()
-        self._ensure_fp8(eng, x[:step])
-        yn = torch.empty(B, 3, H, W, dtype=_io_dtype(x), device=x.device)
-        yd = torch.empty(B, 1, H, W, dtype=_io_dtype(x), device=x.device)
-        def run():
-            for i in range(0, B, step):
-                eng.forward_dual(x[i:i + step], out_normal=yn[i:i + step], out_depth=yd[i:i + step])
-        run()
-        if self._range_fallback_needed(eng, x, run):
-            return self.forward(x)  # on the bf16-plane engine
+    def _result(self, yn, yd):
         return yn, yd.squeeze(dim=1)
 
 

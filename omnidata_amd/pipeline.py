@@ -27,7 +27,7 @@ from typing import Iterable, Iterator, List, Optional
 
 import torch
 
-from .engine import IO_DTYPES, Engine, probe_stream_overlap
+from .engine import Engine, probe_stream_overlap
 
 
 class Ticket:
@@ -119,16 +119,10 @@ class ForwardPipeline:
     def from_engine(cls, owner: Engine, depth: int = 2, inner_streams: int = 1, max_batch: Optional[int] = None) -> "ForwardPipeline":
         """`depth` fresh handles with `owner`'s configuration that all read `owner`'s weights (which must be on the device);
         `owner` itself stays free for ordinary forwards and is kept alive by the pipeline."""
-        c = owner.cfg
-        self = cls(depth=depth, inner_streams=inner_streams, num_channels=c.num_channels, max_batch=max_batch or c.max_batch,
-                   dtype=owner.dtype, device_id=c.device_id, non_negative=bool(c.non_negative), ws_form=c.ws_form, ws_eps=c.ws_eps,
-                   max_hw=(c.max_height, c.max_width), dual=bool(c.dual_task), x3_groups=c.x3_groups, backbone=owner.backbone,
-                   flags=c.flags)
+        self = cls(depth=depth, inner_streams=inner_streams,
+                   **{**owner.config_kwargs(), "max_batch": max_batch or owner.cfg.max_batch})
         for e in self.engines:
-            e.share_weights_from(owner)
-            e.copy_layer_precision_from(owner)   # per-layer precision is handle state, not part of the shared blob (ADVICE r5)
-            if owner.fp8_scales is not None:
-                e.set_fp8_calibration(owner.fp8_scales)
+            e.follow(owner)
         self._external_owner = owner
         return self
 
@@ -169,33 +163,19 @@ class ForwardPipeline:
         self._next = (self._next + 1) % self.depth
         eng, st = self.engines[slot], self.streams[slot]
         cur = torch.cuda.current_stream(self.device)
-        # conversions and output allocations happen on the CALLER's stream (its allocator pool): only the forward itself runs
-        # on the slot's stream
-        if x.is_cuda and x.dim() == 4:
-            if x.dtype not in IO_DTYPES:
-                x = x.float()
-            x = x.contiguous()
-            B, _, H, W = x.shape
-            if self.dual:
-                if out is None:
-                    out = torch.empty(B, 3, H, W, dtype=x.dtype, device=x.device)
-                if out_depth is None:
-                    out_depth = torch.empty(B, 1, H, W, dtype=x.dtype, device=x.device)
-            elif out is None:
-                out = torch.empty(B, eng.cfg.num_channels, H, W, dtype=x.dtype, device=x.device)
+        # the input checks, conversions and output allocations happen on the CALLER's stream (its allocator pool): only the
+        # forward itself runs on the slot's stream
+        x = eng._image(x)
+        outs = eng._outputs(x, (out, out_depth) if self.dual else (out,))
         st.wait_stream(cur)
         with torch.cuda.stream(st):
-            if self.dual:
-                res = eng.forward_dual(x, out_normal=out, out_depth=out_depth)
-            else:
-                res = eng.forward(x, out=out)
+            eng._run(x, outs)
             ev = torch.cuda.Event()
             ev.record(st)
         # the caching allocator must not hand these blocks to another stream's tensor before the forward has run
-        x.record_stream(st)
-        for t in (res if isinstance(res, tuple) else (res,)):
+        for t in (x,) + outs:
             t.record_stream(st)
-        return Ticket(res, ev)
+        return Ticket(outs if self.dual else outs[0], ev)
 
     def forward(self, x: torch.Tensor, out=None):
         """Stream-ordered convenience (the semantics of Engine.forward): submit + wait.  No overlap between calls."""

@@ -13,10 +13,18 @@ from omnidata_amd.weights import random_state_dict, state_dict_spec, is_unused
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def declared_symbols():
+def header_text():
     text = open(os.path.join(ROOT, "include", "dptx.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(dptx_[a-z0-9_]+)\s*\(", text)))
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def declared_symbols():
+    return sorted(set(re.findall(r"\b(dptx_[a-z0-9_]+)\s*\(", header_text())))
+
+
+def declared_enum(prefix):
+    """{lower-case member: value} of the enumerators DPTX_<prefix>_* of include/dptx.h."""
+    return {n.lower(): int(v) for n, v in re.findall(rf"\bDPTX_{prefix}_(\w+)\s*=\s*(-?\d+)", header_text())}
 
 
 def test_library_exports_every_declared_symbol(built_lib):
@@ -31,6 +39,35 @@ def test_python_binding_covers_header(built_lib):
     from omnidata_amd.engine import ABI, load_library
     load_library()
     assert sorted(n for n, _, _ in ABI) == declared_symbols()
+
+
+def test_python_tables_match_header_enums_and_config_round_trips(built_lib):
+    """The tables of omnidata_amd/engine.py are the enums of include/dptx.h, member for member, and Engine.config_kwargs()
+    names every field of dptx_config: a handle built from it has the same configuration."""
+    from omnidata_amd import engine as eng_mod
+    from omnidata_amd.engine import DptxConfig, Engine, FLAGS
+    torch_names = {torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}
+    tables = {"DTYPE": eng_mod.DTYPES, "GROUP": eng_mod.GROUPS, "BACKBONE": eng_mod.BACKBONE_IDS, "FLAG": FLAGS,
+              "IO": {torch_names[k]: v for k, v in eng_mod.IO_DTYPES.items()}}
+    for prefix, table in tables.items():
+        want = declared_enum(prefix)
+        assert len(want) >= 2, prefix
+        assert table == want, prefix
+    assert eng_mod.TWO_PLANE_DTYPES <= set(eng_mod.DTYPES)
+    # every non-default setting at once is not a configuration dptx_create accepts (the dual-task model is the hybrid), so the
+    # DPT-Large backbone gets a handle of its own; between them the two handles leave no field of dptx_config at its default.
+    # 'resnet+head' is not a policy dtype 'mixed' accepts (HEAD needs FUSION and RN): a dtype that ignores the groups carries it
+    common = dict(max_batch=5, dtype="fp16x3", device_id=None, non_negative=False, ws_form=1, ws_eps=1e-6, max_hw=(256, 320),
+                  streams=2, x3_groups="resnet+head", flags=FLAGS["no_ln_fold"] | FLAGS["no_range_check"])
+    for own in (dict(num_channels=3, dual=True), dict(num_channels=1, backbone="vitl16_384")):
+        e = Engine(**common, **own)
+        twin = Engine(**e.config_kwargs())
+        for name, _ in DptxConfig._fields_:
+            assert getattr(twin.cfg, name) == getattr(e.cfg, name), (own, name)
+        assert (twin.dtype, twin.backbone) == (e.dtype, e.backbone)
+        assert e.cfg.x3_groups == 65 and e.cfg.flags == 9 and (e.cfg.max_height, e.cfg.max_width) == (256, 320) and e.cfg.ws_form == 1
+        twin.close()
+        e.close()
 
 
 def test_device_handle_fails_loudly_without_gpu(built_lib):
@@ -97,11 +134,11 @@ def _blob_offsets(spec_items, dtype_bytes=2):
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 def test_packed_weights_match_numpy_fold(built_lib, dtype):
-    from omnidata_amd.engine import Engine
+    from omnidata_amd.engine import FLAGS, Engine
     from oracle.dpt_oracle import standardize_weight
     C = 1
     sd = random_state_dict(3, C)
-    e = Engine(num_channels=C, max_batch=2, dtype=dtype, device_id=None, flags=1)  # DPTX_FLAG_NO_LN_FOLD: weights as loaded
+    e = Engine(num_channels=C, max_batch=2, dtype=dtype, device_id=None, flags=FLAGS["no_ln_fold"])  # weights as loaded
     e.load_state_dict(sd)
     blob = e.export_packed_host()
     offs, total = _blob_offsets(state_dict_spec(C).items())
@@ -184,9 +221,9 @@ def test_fp16_conversion_edge_cases(built_lib):
 
 def test_bf16x3_packing_has_hi_and_lo_planes(built_lib):
     """bf16x3 blob = [hi blob | lo blob]: hi is exactly the bf16 blob, lo = bf16(w - hi)."""
-    from omnidata_amd.engine import Engine
+    from omnidata_amd.engine import FLAGS, Engine
     sd = random_state_dict(4, 3)
-    e1 = Engine(num_channels=3, max_batch=1, dtype="bf16", device_id=None, flags=1)  # no LayerNorm fold: bf16x3 never folds
+    e1 = Engine(num_channels=3, max_batch=1, dtype="bf16", device_id=None, flags=FLAGS["no_ln_fold"])  # bf16x3 never folds
     e1.load_state_dict(sd)
     e3 = Engine(num_channels=3, max_batch=1, dtype="bf16x3", device_id=None)
     e3.load_state_dict(sd)
@@ -233,10 +270,10 @@ def test_fp8_vit_host_packing(built_lib):
     weights the bf16 GEMM multiplies -- qkv / fc1 folded with the LayerNorm's gamma --, quantised per output channel after a
     power-of-two scale into (224, 448], the inverse scales ('f8scale') and the column sums of the DEQUANTISED copy ('lnsum8':
     the fold's mean term has to cancel against what the e4m3 MFMA multiplies).  Checked against numpy on the host-only handle."""
-    from omnidata_amd.engine import Engine
+    from omnidata_amd.engine import FLAGS, Engine
     C = 3
     sd = random_state_dict(5, C)
-    e = Engine(num_channels=C, max_batch=1, dtype="fp8", device_id=None, flags=32)
+    e = Engine(num_channels=C, max_batch=1, dtype="fp8", device_id=None, flags=FLAGS["fp8_vit"])
     e.load_state_dict(sd)
     blob = e.export_packed_host()
     offs, single = _blob_offsets(state_dict_spec(C).items())

@@ -254,6 +254,63 @@ class _FakeCudaTensor(torch.Tensor):
         return True
 
 
+class _FakeCuda0Tensor(_FakeCudaTensor):
+    """... and that says which GPU: cuda:0."""
+    @property
+    def device(self):
+        return torch.device("cuda", 0)
+
+
+def test_engine_entry_points_share_one_input_contract(built_lib):
+    """Engine.forward, Engine.forward_dual and Engine.calibrate_fp8 reject the same inputs with the same exception, in Python:
+    the library is never called with a pointer that was not checked (calibrate_fp8 used to hand a wrong-rank or wrong-device
+    tensor to dptx_calibrate_fp8).  Host-only handles: the control flow needs no GPU."""
+    from omnidata_amd.engine import Engine
+
+    class NoCalls:
+        def __getattr__(self, name):
+            raise AssertionError(f"library call {name} before the input was checked")
+
+    single = Engine(num_channels=3, max_batch=1, dtype="bf16", device_id=None)
+    dual = Engine(num_channels=3, max_batch=1, dtype="bf16", device_id=None, dual=True)
+    libs = [(e, e.lib) for e in (single, dual)]
+    entries = [single.forward, dual.forward_dual, single.calibrate_fp8, dual.calibrate_fp8]
+    fake = lambda *shape, **kw: torch.zeros(*shape, **kw).as_subclass(_FakeCuda0Tensor)
+    bad_inputs = [(torch.zeros(1, 3, 64, 64), RuntimeError, "no CPU fallback"),                  # a CPU tensor
+                  (fake(3, 64, 64), ValueError, r"expected \[B,3,H,W\]"),                         # 3-D
+                  (fake(1, 3, 48, 64), ValueError, r"expected \[B,3,H,W\]"),                      # H % 32 != 0
+                  (fake(1, 4, 64, 64), ValueError, r"expected \[B,3,H,W\]"),                      # 4 channels
+                  (fake(1, 3, 64, 64), RuntimeError, r"input is on cuda:0, the engine was created for cuda:-1"),
+                  (torch.zeros(1, 3, 64, 64).as_subclass(_FakeCudaTensor), RuntimeError, "the engine was created for")]
+    try:
+        for e, _ in libs:
+            e.lib = NoCalls()
+        for x, exc, stem in bad_inputs:
+            messages = set()
+            for entry in entries:
+                with pytest.raises(exc, match=stem) as info:
+                    entry(x)
+                messages.add(str(info.value))
+            assert len(messages) == 1, messages      # the same text from every entry point
+        # a wrong `out`: for the input to pass, the handles have to believe that they live on the fake tensor's device
+        x = fake(1, 3, 64, 64)
+        for e, _ in libs:
+            e.cfg.device_id = 0
+        for out in (fake(1, 3, 64, 32), fake(1, 3, 64, 64, dtype=torch.bfloat16), torch.zeros(1, 3, 64, 64),
+                    fake(1, 3, 64, 128)[..., ::2]):   # shape, dtype, device, not contiguous
+            with pytest.raises(ValueError, match="out must be a contiguous"):
+                single.forward(x, out=out)
+            with pytest.raises(ValueError, match="out must be a contiguous"):
+                dual.forward_dual(x, out_normal=out, out_depth=fake(1, 1, 64, 64))
+        for out_depth in (fake(1, 3, 64, 64), fake(1, 1, 64, 64, dtype=torch.float16)):
+            with pytest.raises(ValueError, match="out must be a contiguous"):
+                dual.forward_dual(x, out_normal=fake(1, 3, 64, 64), out_depth=out_depth)
+    finally:
+        for e, lib in libs:
+            e.lib = lib
+            e.close()
+
+
 class _StubEngine:
     """Stands in for omnidata_amd.engine.Engine: records calls; its range flag is set by every forward in the fp16-plane
     dtypes when `overflow` is on (sticky until read with reset, like dptx_range_status)."""

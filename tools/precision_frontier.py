@@ -16,7 +16,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from omnidata_amd.engine import Engine  # noqa: E402
+from omnidata_amd.engine import FLAGS, Engine  # noqa: E402
 from omnidata_amd.weights import random_state_dict, synthetic_input  # noqa: E402
 from oracle.dpt_oracle import dpt_forward, mean_angular_error_deg, oracle_threads  # noqa: E402
 
@@ -25,7 +25,7 @@ HEAD0 = "scratch.output_conv.0.weight"
 MODES = [("bf16", 0, 0, {}), ("fp16", 0, 0, {}), ("mixed", "resnet", 0, {}), ("mixed", "resnet+embed+reassemble+rn+fusion", 0, {}),
          ("mixed", 0, 0, {HEAD0: 1}),   # default per-layer table with the first head conv single-pass too ("policy C")
          ("mixed", 0, 0, {}),           # default: per-layer table of the decoder ("policy A")
-         ("mixed", 0, 2, {}),           # DPTX_FLAG_GROUP_POLICY: round 2's default (every group but the ViT blocks)
+         ("mixed", 0, FLAGS["group_policy"], {}),   # round 2's default (every group but the ViT blocks)
          ("fp16x3", 0, 0, {}), ("bf16x3", 0, 0, {})]
 
 
