@@ -427,6 +427,70 @@ int dptx_vnl_triples(const float* first, const float* second, int32_t B, int32_t
                      const int32_t* p1, const int32_t* p2, const int32_t* p3, int32_t n, uint8_t* keep, float* loss,
                      float* normals /*nullable*/, void* stream);
 
+/* ---- surface-normal loss (omnidata_tools/torch/train_normal.py:205-265, losses/masked_losses.py; no handle; DEVICE pointers) ----
+ * The normal objective of the reference: normal_loss = cos_loss + 10 * l1_loss on the prediction clamped to [0, 1], with
+ * its gradient with respect to the prediction; the flat masked losses; make_valid_mask.  Stream-ordered on `stream`, on
+ * the caller's workspace only: no allocation, no host synchronisation, no host read of any count (graph-capturable).  No
+ * atomics: every sum is fp64 in a fixed order that depends on the shape alone (not on the alignment of the pointers), so
+ * results are bitwise reproducible.  pred, target [B][3][H][W] fp32 and mask [B][H][W] uint8 (0 / non-zero) contiguous;
+ * shapes B >= 1, 1 <= H, W <= 8192, H*W <= 2^24; all indexing in 64 bits.  Anything else -> DPTX_E_INVALID.
+ * Per valid pixel, in fp32 with every step rounded on its own as the reference's fp32 tensors (p = clamp(pred, 0, 1) first
+ * with DPTX_NORMAL_CLAMP_PRED):
+ *   x = clamp(2 p - 1, -1, 1), y the same of the target; xh = x / max(|x|, 1e-12) (F.normalize); cos term -(xh . yh);
+ *   l1 terms |p_c - t_c|, c = 0, 1, 2.
+ * N = the number of valid pixels; cos = sum of the cos terms / N, l1 = sum of the l1 terms / (3 N), sums in fp64, each
+ * rounded to fp32 once; total = cos + l1_weight * l1 from the fp64 values, rounded once.  flags selects the terms
+ * (DPTX_NORMAL_L1, DPTX_NORMAL_COS, at least one): an absent term is 0 and total is the present one.  N == 0 gives NaN for
+ * every present term and for total, and an all-zero gradient.
+ * Host-only (no GPU needed): the workspace, with A(x) = x rounded up to a multiple of 256, units = ceil(B H W / 4) and
+ * nblk = min(ceil(units / 1024), 1024):
+ *   *bytes = A(24 nblk). */
+#define DPTX_NORMAL_L1 1
+#define DPTX_NORMAL_COS 2
+#define DPTX_NORMAL_CLAMP_PRED 4 /* pred -> clamp(pred, 0, 1) first (train_normal.py:251) */
+#define DPTX_NORMAL_RECORD_DOUBLES 1
+int dptx_normal_workspace_bytes(int32_t B, int32_t H, int32_t W, int64_t* bytes);
+/* losses [3] fp32 = (total, l1, cos).  record (nullable; needed by the backward): [DPTX_NORMAL_RECORD_DOUBLES] fp64 owned
+ * by the caller until the matching dptx_normal_loss_backward: N, the count alone. */
+int dptx_normal_loss(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W, int32_t flags,
+                     float l1_weight, float* losses, double* record /*nullable*/, void* ws, int64_t ws_bytes, void* stream);
+/* grad_pred [B][3][H][W] = d(g0 total + g1 l1 + g2 cos) / d pred for grad_losses = (g0, g1, g2) [3] fp32 on the device, from
+ * the record of the forward on the same inputs and arguments; the inputs are read again.  Evaluated in fp64 from the fp32
+ * inputs and rounded once; the clamp, sign and eps decisions are the forward's fp32 ones.  d|x| / dx = sign(x) with
+ * sign(0) = 0; a clamp passes its gradient where lo <= v <= hi, ends included (torch's rule), and nothing outside; through
+ * max(|x|, eps) the gradient goes to |x| where |x| >= eps, (yh - (xh . yh) xh) / |x|, and the denominator is the constant
+ * eps otherwise: a pixel whose scaled prediction is the zero vector has gradient -2 yh / (eps N) per component, the
+ * reference's value.  Pixels outside the mask get 0.  No workspace. */
+int dptx_normal_loss_backward(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W,
+                              int32_t flags, float l1_weight, const double* record, const float* grad_losses, float* grad_pred,
+                              void* stream);
+/* Per-pixel terms for tests and debugging: cos [B][H][W] fp32 the cos term, l1 [B][H][W] fp32 the fp64 sum of the three l1
+ * terms rounded once; 0 outside the mask.  Either may be null, not both.  flags: DPTX_NORMAL_CLAMP_PRED or 0.  No workspace. */
+int dptx_normal_pixels(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W, int32_t flags,
+                       float* cos /*nullable*/, float* l1 /*nullable*/, void* stream);
+/* The flat per-element form: masked_l1_loss, masked_mse_loss and masked_loss of losses/masked_losses.py on n elements,
+ * 1 <= n <= 2^40, with a mask per element: the fp64 sum of |p - t| (DPTX_MASKED_L1), of (p - t)^2 (DPTX_MASKED_MSE; the
+ * difference and the square each rounded to fp32) or of p (DPTX_MASKED_VALUE: `pred` holds the element-wise loss, target is
+ * NULL) over the mask, divided by its count N.  N == 0 gives NaN, or 0 with DPTX_MASKED_EMPTY_ZERO (masked_loss :28-29),
+ * decided on the device.  record (nullable; needed by the backward): [1] fp64, N.  The gradient is sign(p - t) / N,
+ * 2 (p - t) / N or 1 / N on the mask, times grad_loss[0], and 0 elsewhere and where N == 0.
+ * Host-only: the workspace, with units = ceil(n / 4) and nblk = min(ceil(units / 1024), 1024): *bytes = A(24 nblk). */
+#define DPTX_MASKED_L1 0
+#define DPTX_MASKED_MSE 1
+#define DPTX_MASKED_VALUE 2
+#define DPTX_MASKED_EMPTY_ZERO 4 /* OR-ed into kind */
+int dptx_masked_workspace_bytes(int64_t n, int64_t* bytes);
+int dptx_masked_loss(const float* pred, const float* target /*NULL for VALUE*/, const uint8_t* mask, int64_t n, int32_t kind,
+                     float* loss, double* record /*nullable*/, void* ws, int64_t ws_bytes, void* stream);
+int dptx_masked_loss_backward(const float* pred, const float* target, const uint8_t* mask, int64_t n, int32_t kind,
+                              const double* record, const float* grad_loss, float* grad_pred, void* stream);
+/* make_valid_mask (train_normal.py:205-232): valid [B][H][W] uint8 = 1 where the maximum of 1 - mask_float over the pixel's
+ * pool x pool window is exactly 0 (a NaN in the window: 0).  With Hp = H / pool, Wp = W / pool (integer division), the window
+ * of pixel (i, j) is row min(floor(i * (float(Hp) / float(H))), Hp - 1) and the like column of the pooled grid (max_pool2d,
+ * then F.interpolate(mode='nearest') back to H x W): rows and columns beyond pool * Hp are never pooled and take their nearest
+ * pooled window.  Requires H, W >= pool >= 1.  No workspace. */
+int dptx_valid_mask(const float* mask_float, int32_t B, int32_t H, int32_t W, int32_t pool, uint8_t* valid, void* stream);
+
 /* ---- op-level entry points (unit tests + micro-benchmarks of the individual kernels) ----
  * dtype: DPTX_DTYPE_*.  All pointers are device pointers; row-major / NHWC. */
 

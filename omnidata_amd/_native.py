@@ -1,4 +1,4 @@
-"""What the wrappers of libdptx's feature entry points (refocus.py, midas_loss.py, virtual_normal_loss.py) share: the
+"""What the wrappers of libdptx's feature entry points (refocus.py, midas_loss.py, virtual_normal_loss.py, normal_loss.py) share: the
 CUDA-tensor check, the cached workspace and the checked call (the current stream is engine._stream)."""
 from __future__ import annotations
 

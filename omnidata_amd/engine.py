@@ -101,6 +101,14 @@ ABI = [
                                          _vp, _vp]),
     ("dptx_vnl_triples", C.c_int, [_vp, _vp, _i32, _i32, _i32, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                    _vp]),
+    ("dptx_normal_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i64p]),
+    ("dptx_normal_loss", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_normal_loss_backward", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp]),
+    ("dptx_normal_pixels", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    ("dptx_masked_workspace_bytes", C.c_int, [C.c_int64, _i64p]),
+    ("dptx_masked_loss", C.c_int, [_vp, _vp, _vp, C.c_int64, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_masked_loss_backward", C.c_int, [_vp, _vp, _vp, C.c_int64, _i32, _vp, _vp, _vp, _vp]),
+    ("dptx_valid_mask", C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     ("dptx_op_set_planes", C.c_int, [C.c_int64, C.c_int64]),
     ("dptx_op_gemm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_op_conv", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp] + [_i32] * 13 + [_vp]),
