@@ -491,6 +491,52 @@ int dptx_masked_loss_backward(const float* pred, const float* target, const uint
  * pooled window.  Requires H, W >= pool >= 1.  No workspace. */
 int dptx_valid_mask(const float* mask_float, int32_t B, int32_t H, int32_t W, int32_t pool, uint8_t* valid, void* stream);
 
+/* ---- evaluation metrics (paper_code/evaluation_metrics.py:13-106, get_metrics for task='normal' and 'depth_zbuffer'; no
+ * handle; DEVICE pointers) ----
+ * Forward only.  Stream-ordered on `stream`, on the caller's workspace only: no allocation, no host synchronisation, no
+ * host read of the mask count.  pred, target [B][C][H][W] fp32 (C = 3 normal, 1 depth) and mask [B][H][W] uint8
+ * (0 / non-zero) contiguous; B >= 1, 1 <= H, W <= 8192, H*W <= 2^24 and B*H*W < 2^32.  A null pointer, an unknown flag, a
+ * workspace that is too small or another shape -> DPTX_E_INVALID, before anything is launched.
+ * Rows: one for the whole batch (the reference's call), or with DPTX_EVAL_PER_IMAGE one per image, each what the
+ * reference returns for that image alone (paper_code/test_normal.py:377-389 calls it per image).  A per-image row does not
+ * depend on B or on the image's place in the batch, and equals the batch row of a B = 1 call bit for bit.
+ * Every per-pixel term is evaluated in fp64 on the fp32 inputs (:18-19 .double()), each operation rounded on its own, for
+ * EVERY pixel, and multiplied by the 0 / 1 mask as the reference does: a non-finite term outside the mask poisons its sum
+ * exactly as there (a masked-out pixel with target == 0 makes rel_error NaN).  Sums are fp64 in an order fixed by (H, W)
+ * alone; there are no float atomics, so results are bitwise reproducible.  With n = the number of valid pixels of the row
+ * and numel = all its pixels:
+ *   normal (:33-59)  cos = (p . t) / max(|p| |t|, 1e-8) clamped to [-1, 1], ang = acos(cos) * (180 / pi);
+ *     out row [DPTX_EVAL_NORMAL_FIELDS] = n, ang_error_mean = sum(ang m) / n, ang_error_median, ang_error_without_masking =
+ *     sum(ang) / numel, the fractions of the valid pixels with ang <= 11.25, 22.5, 30 (a NaN compares false), eval_L1 and
+ *     eval_mse = 100 (numel / n) mean over pixels and channels of d and of d^2, d = |p / (|p| + 2e-2) - t / (|t| + 2e-2)| m.
+ *     ang_error_median is the exact np.median (:50) of the valid pixels' angles -- the value of rank floor((n - 1) / 2) for
+ *     odd n, (a + b) * 0.5 of ranks n / 2 - 1 and n / 2 for even n --, found by a radix select on 64-bit order-preserving
+ *     keys (8 passes of 8 bits, integer histograms); NaN if any valid pixel's angle is NaN, as np.median answers.
+ *   depth (:61-79)  d = |p - t| m, dlog = |(log(1 + 64 p) - log(1 + 64 t)) m|;
+ *     out row [DPTX_EVAL_DEPTH_FIELDS] = n, eval_L1 and eval_mse = 100 (numel / n) mean of d and of d^2, log10_diff =
+ *     (numel / n) mean(log(1 + 64 d) m), log10 = (numel / n) mean(dlog), si_log = sum(dlog^2) / n - sum(dlog)^2 / n^2,
+ *     rel_error = (numel / n) mean((d / t) m), irmse = (numel / n) mean((1 / (1 + 64 p) - 1 / (1 + 64 t))^2 m).
+ * A row with an empty mask gets n = 0 and NaN in every other field, decided on the device (:30-31 returns None).
+ * Host-only (no GPU needed): the workspace, with A(x) = x rounded up to a multiple of 256, units = ceil(H W / 4) and
+ * nblk = min(ceil(units / 256), 1024):
+ *   *bytes = A(8 B H W) + A(72 B nblk) + 16384 B + A(192 B)
+ * (the keys, the partial sums, and per possible row the histograms and the select states).  The call clears what it needs in stream order, so
+ * one workspace serves any sequence of calls of its shape ON ONE STREAM AT A TIME: two calls in flight on two streams need
+ * two workspaces.  The size is one per shape for both tasks: dptx_eval_depth asks for it too but never touches the key
+ * region, the histograms or the states (at B = 32, 384 x 384 about 38 MB of the 40 MB); a caller that evaluates depth only
+ * pays that for the single size function. */
+#define DPTX_EVAL_PER_IMAGE 1     /* rows = B (one per image); otherwise rows = 1 (the whole batch) */
+#define DPTX_EVAL_NORMAL_FIELDS 9 /* count, ang_error_mean, ang_error_median, ang_error_without_masking, within_11.25,
+                                     within_22.5, within_30, eval_L1, eval_mse */
+#define DPTX_EVAL_DEPTH_FIELDS 8  /* count, eval_L1, eval_mse, log10_diff, log10, si_log, rel_error, irmse */
+int dptx_eval_workspace_bytes(int32_t B, int32_t H, int32_t W, int64_t* bytes);
+int dptx_eval_normal(const float* pred, const float* target /*[B,3,H,W]*/, const uint8_t* mask /*[B,H,W]*/, int32_t B, int32_t H,
+                     int32_t W, int32_t flags, double* out /*[rows][9]*/, void* ws, int64_t ws_bytes, void* stream);
+int dptx_eval_depth(const float* pred, const float* target /*[B,1,H,W]*/, const uint8_t* mask /*[B,H,W]*/, int32_t B, int32_t H,
+                    int32_t W, int32_t flags, double* out /*[rows][8]*/, void* ws, int64_t ws_bytes, void* stream);
+/* Per-pixel angles for tests and debugging (:43): ang [B][H][W] fp64, degrees, the mask not applied.  No workspace. */
+int dptx_eval_normal_pixels(const float* pred, const float* target, int32_t B, int32_t H, int32_t W, double* ang, void* stream);
+
 /* ---- op-level entry points (unit tests + micro-benchmarks of the individual kernels) ----
  * dtype: DPTX_DTYPE_*.  All pointers are device pointers; row-major / NHWC. */
 

@@ -2,7 +2,7 @@
 """Real-checkpoint harness: everything that can be said about a checkpoint in ONE run.
 
     python tools/eval_checkpoint.py --task normal --ckpt pretrained_models/omnidata_dpt_normal_v2.ckpt --images DIR [--gt DIR]
-                                    [--dtypes mixed,bf16x3] [--batch 8] [--out report.json]
+                                    [--dtypes mixed,bf16x3] [--batch 8] [--device-metrics] [--out report.json]
 
 What the reference does with a checkpoint is `demo.py:62-72` (load, strip the Lightning prefix, strict load_state_dict) and
 `paper_code/evaluation_metrics.py:14-106` (the metrics of docs/pretrained.html:96-104).  This tool loads the same file through
@@ -16,7 +16,7 @@ every requested dtype reports
   * the output's range and its agreement with the first dtype of the list (max / rms difference; `bf16x3` and `fp16x3` are
     reference-grade, 1e-4 / 1e-5 from the fp32 forward on the synthetic families, so `mixed` vs `bf16x3` is the parity
     check that needs no CPU reference),
-  * with --gt: `omnidata_amd.metrics.get_metrics` (angular error / within-t degrees for normals; L1, log10, rel, irmse, si_log
+  * with --gt: `omnidata_amd.metrics.get_metrics`, or with --device-metrics `omnidata_amd.gpu_metrics.get_metrics` (angular error / within-t degrees for normals; L1, log10, rel, irmse, si_log
     for depth) against ground truth.  Ground-truth files: <gt>/<stem>.npy or <stem>.png for every image <stem>.*; normals as
     [H,W,3] in [0,1] (the reference's (n+1)/2 convention; an .npy in [-1,1] is mapped), depth as [H,W] in [0,1]; optional
     validity mask <stem>_mask.png (non-zero = valid).  They are resized / centre-cropped like the input.
@@ -78,9 +78,12 @@ def load_gt(gt_dir: str, stem: str, task: str):
 
 
 def evaluate(task: str, ckpt: str, images, gt_dir=None, dtypes=("mixed", "bf16x3"), batch: int = 8, backbone: str = "vitb_rn50_384",
-             device: str = "cuda:0") -> dict:
+             device: str = "cuda:0", device_metrics: bool = False) -> dict:
     from omnidata_amd import preprocess as pp
-    from omnidata_amd.metrics import get_metrics
+    if device_metrics:   # the same numbers from libdptx's eval kernels: one device-to-host copy instead of about ten reads
+        from omnidata_amd.gpu_metrics import get_metrics
+    else:
+        from omnidata_amd.metrics import get_metrics
     from omnidata_amd.model import build_model
     from omnidata_amd.weights import read_checkpoint
     if not torch.cuda.is_available():
@@ -149,6 +152,8 @@ def main(argv=None):
     ap.add_argument("--dtypes", default="bf16x3,mixed", help="first one is the reference the others are compared with")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--backbone", default="vitb_rn50_384", choices=["vitb_rn50_384", "vitl16_384"])
+    ap.add_argument("--device-metrics", action="store_true",
+                    help="compute the --gt metrics with omnidata_amd.gpu_metrics (HIP kernels) instead of omnidata_amd.metrics (torch ops)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if os.path.isdir(args.images):
@@ -158,7 +163,8 @@ def main(argv=None):
     if not images or not all(os.path.isfile(p) for p in images):
         print("invalid file path!")   # demo.py:161-163
         sys.exit(1)
-    rep = evaluate(args.task, args.ckpt, images, args.gt, tuple(d for d in args.dtypes.split(",") if d), args.batch, args.backbone)
+    rep = evaluate(args.task, args.ckpt, images, args.gt, tuple(d for d in args.dtypes.split(",") if d), args.batch, args.backbone,
+                   device_metrics=args.device_metrics)
     txt = json.dumps(rep, indent=1)
     if args.out:
         with open(args.out, "w") as f:
