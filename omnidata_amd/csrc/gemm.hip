@@ -58,6 +58,10 @@ hipError_t launch_gemm(int mode, const GemmParams& p0, hipStream_t stream) {
     return launch_gemm_fp8(p, stream);
   }
   if (p.K % BK != 0 || p.Cin % BK != 0 || p.M <= 0 || p.N % 32 != 0 || p.ldw < p.K || p.ldw % 8 != 0) return hipErrorInvalidValue;
+  // the small-K 1x1 convolutions stream through a kernel of their own (conv1x1.hip) in the classes where it measured faster;
+  // debug flag 8: never, flag 16: wherever it can run
+  if (!(p.debug_flags & 8) && conv1x1_stream_eligible(mode, p) && ((p.debug_flags & 16) || conv1x1_stream_adopted(p)))
+    return launch_conv1x1_stream(mode, p, stream);
   if (mode == MODE_BF16) return p.epi2 ? hipErrorInvalidValue : launch_gemm_16(DT_BF16, p, stream);
   if (mode == MODE_FP16) return p.epi2 ? launch_gemm_fp16e(p, stream) : launch_gemm_16(DT_FP16, p, stream);
   if (mode == MODE_BF16X3) return launch_gemm_x3(DT_BF16, p, stream);

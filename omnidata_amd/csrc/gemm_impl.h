@@ -203,6 +203,39 @@ __device__ __forceinline__ void mma_tile(const char* sa, const char* sb, int a_l
   }
 }
 
+// GroupNorm records of a wave's TM x TN accumulator blocks (lane = output column, registers = rows): the one definition of
+// the reduction order, shared by epilogue() below and the streaming 1x1 kernel (conv1x1.hip), so that a record has the same
+// bits whichever kernel wrote it.  m0 / n0: first row / column of the block tile, (wm, wn): the wave's place in it.
+template <int TM, int TN>
+__device__ __forceinline__ void gn_records(const GemmParams& p, int m0, int n0, int wm, int wn, int lr, int lh,
+                                           f32x16_t (&acc)[TM][TN]) {
+  const int cpg = p.gn_cpg;  // channels per group: 2..32, a power of two
+  const int cpg_sh = __builtin_ctz(cpg);
+  int gn_hw = p.gn_hw;
+  asm volatile("" : "+s"(gn_hw));  // opaque, like c_rpi in epilogue(): no hoisted divider constants in a tile loop
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    // first GEMM row of this wave's i-th 32-row block
+    const int mb = m0 + (wm * TM + i) * 32;
+    const int img = mb / gn_hw;
+    const int blk = (mb - img * gn_hw) >> 5;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      float sm = 0.f, sq = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { const float v = acc[i][j][r]; sm += v; sq = fmaf(v, v, sq); }
+      sm += __shfl_xor(sm, 32, 64);
+      sq += __shfl_xor(sq, 32, 64);
+      for (int o = 1; o < cpg; o <<= 1) { sm += __shfl_xor(sm, o, 64); sq += __shfl_xor(sq, o, 64); }
+      if (lh == 0 && (lr & (cpg - 1)) == 0 && mb < p.M) {
+        const int g = (n0 + (wn * TN + j) * 32 + lr) >> cpg_sh;
+        float2* dst = (float2*)p.gn_part + ((long long)img * p.gn_blocks + blk) * 32 + g;
+        *dst = make_float2(sm, sq);
+      }
+    }
+  }
+}
+
 // SLABS == 1: the whole BM x BN tile goes through LDS at once.  SLABS == TM (256x256 block: the fp32 tile would be
 // 266 KB): TM passes, pass s carries the s-th 32-row MFMA tile of every wave -- LDS row q = (wave row)*32 + r is tile
 // row (q/32)*(TM*32) + s*32 + q%32.
@@ -259,33 +292,7 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, char* smem, int m0
   const int rr = WP ? (tid & 63) >> 3 : tid / NCH;
   const int n = n0 + (WP ? wn * (TN * 32) : 0) + cn * 8;
 
-  if (p.gn_part != nullptr) {
-    const int cpg = p.gn_cpg;  // channels per group: 2..32, a power of two
-    const int cpg_sh = __builtin_ctz(cpg);
-    int gn_hw = p.gn_hw;
-    asm volatile("" : "+s"(gn_hw));  // opaque, like c_rpi below: no hoisted divider constants in a tile loop
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      // first GEMM row of this wave's i-th 32-row block
-      const int mb = m0 + (wm * TM + i) * 32;
-      const int img = mb / gn_hw;
-      const int blk = (mb - img * gn_hw) >> 5;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        float sm = 0.f, sq = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { const float v = acc[i][j][r]; sm += v; sq = fmaf(v, v, sq); }
-        sm += __shfl_xor(sm, 32, 64);
-        sq += __shfl_xor(sq, 32, 64);
-        for (int o = 1; o < cpg; o <<= 1) { sm += __shfl_xor(sm, o, 64); sq += __shfl_xor(sq, o, 64); }
-        if (lh == 0 && (lr & (cpg - 1)) == 0 && mb < p.M) {
-          const int g = (n0 + (wn * TN + j) * 32 + lr) >> cpg_sh;
-          float2* dst = (float2*)p.gn_part + ((long long)img * p.gn_blocks + blk) * 32 + g;
-          *dst = make_float2(sm, sq);
-        }
-      }
-    }
-  }
+  if (p.gn_part != nullptr) gn_records<TM, TN>(p, m0, n0, wm, wn, lr, lh, acc);
 
   float bias_c[8];
 #pragma unroll

@@ -82,7 +82,8 @@ struct GemmParams {
   int ln_nblk;
   float ln_eps, ln_inv_dim;
   long long* trace;  // debug: s_memtime stamps of block 0 (dptx_debug_set_trace); null in production
-  int debug_flags;   // debug (dptx_debug_set_gemm_flags): 1 = staged epilogue everywhere, 2 = one block per tile, 4 = lockstep two-plane 128x128 kernel
+  int debug_flags;   // debug (dptx_debug_set_gemm_flags): 1 = staged epilogue everywhere, 2 = one block per tile, 4 = lockstep two-plane 128x128 kernel,
+                     // 8 = never take the streaming 1x1 kernel, 16 = take it wherever it can run (not only in the adopted classes)
   float a_rpi_rcp, wout_rcp;  // 1 / a_rpi, 1 / Wout (filled in by launch_gemm: row -> (image, y, x) without integer division)
 };
 
@@ -97,9 +98,18 @@ hipError_t launch_gemm(int dtype, const GemmParams& p, hipStream_t stream);
 // debug: every following GEMM launch stamps s_memtime per k-tile phase for the 8 waves of block 0 into dev_buf
 // ([wave][64 k-tiles][4] int64; null switches it off)
 void gemm_set_trace(long long* dev_buf);
-// debug / tests: 1 = no register-direct epilogue, 2 = no persistent launch, 4 = no two-plane ping-pong kernel (same results
-// either way)
+// debug / tests: 1 = no register-direct epilogue, 2 = no persistent launch, 4 = no two-plane ping-pong kernel, 8 = never take
+// the streaming 1x1 kernel, 16 = take it for every launch it can serve, also outside the classes it was adopted for (same
+// results either way)
 void gemm_set_debug_flags(int flags);
+// conv1x1.hip: the streaming kernel for dense / strided 1x1 convolutions with K = Cin in {64, 128, 256}, N % 64 == 0, one 16-bit
+// plane, optional per-column bias, ReLU and GroupNorm records (bf16 / fp16 modes): conv1x1_stream_eligible().  launch_gemm
+// sends there what is eligible AND belongs to a (K, N, stride) class in which the kernel measured faster
+// (conv1x1_stream_adopted(); debug flag 16 drops that second condition, flag 8 switches the kernel off); the bits are those
+// of the tiled kernels.
+bool conv1x1_stream_eligible(int mode, const GemmParams& p);
+bool conv1x1_stream_adopted(const GemmParams& p);
+hipError_t launch_conv1x1_stream(int mode, const GemmParams& p, hipStream_t stream);
 // tile selection: the following launches share the chip with (1 / share - 1) concurrent streams of the same forward
 void gemm_set_cu_share(float share);
 

@@ -1,5 +1,6 @@
 """Per-shape micro-benchmark of the implicit-GEMM kernel on the DPT-Hybrid layer shapes (B=32).
-Usage (GPU box): python tools/gemm_bench.py [--dtype bf16]"""
+Usage (GPU box): python tools/gemm_bench.py [--dtype bf16]
+                 python tools/gemm_bench.py --ab-flags 0,8 --gn --reps 5 --only s0.c3,s1.c3   (A/B of two launch forms)"""
 import argparse
 import os
 import sys
@@ -7,7 +8,6 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from omnidata_amd.build import build  # noqa: E402
 from omnidata_amd.engine import DTYPES, load_library  # noqa: E402
 
 B = 32
@@ -22,7 +22,10 @@ CONV = [("rcu@96", 96, 256, 256, 3, 1, 1, 96), ("rcu@48", 48, 256, 256, 3, 1, 1,
         ("s0.c1", 96, 256, 64, 1, 1, 0, 96), ("s0.c2", 96, 64, 64, 3, 1, 1, 96), ("s0.c3", 96, 64, 256, 1, 1, 0, 96),
         ("s1.c1", 48, 512, 128, 1, 1, 0, 48), ("s1.c2", 48, 128, 128, 3, 1, 1, 48), ("s1.c3", 48, 128, 512, 1, 1, 0, 48),
         ("s2.c1", 24, 1024, 256, 1, 1, 0, 24), ("s2.c2", 24, 256, 256, 3, 1, 1, 24), ("s2.c3", 24, 256, 1024, 1, 1, 0, 24),
-        ("s1.b0.c2(s2)", 96, 128, 128, 3, 2, 0, 48), ("pp4.conv2", 24, 768, 768, 3, 2, 1, 12)]
+        ("s1.b0.c2(s2)", 96, 128, 128, 3, 2, 0, 48), ("pp4.conv2", 24, 768, 768, 3, 2, 1, 12),
+        # the remaining small-K 1x1 launches of the stages and the decoder (s0.ds has s0.c3's shape)
+        ("s0.c1a", 96, 64, 64, 1, 1, 0, 96), ("s1.b0.c1", 96, 256, 128, 1, 1, 0, 96), ("s1.ds", 96, 256, 512, 1, 2, 0, 48),
+        ("out_conv@48", 48, 256, 256, 1, 1, 0, 48), ("out_conv@24", 24, 256, 256, 1, 1, 0, 24), ("out_conv@12", 12, 256, 256, 1, 1, 0, 12)]
 
 
 ITERS = [10]
@@ -46,22 +49,64 @@ def _timeit(fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
+def ab_conv(lib, dt, tdt, st, args, only):
+    """Alternating A/B of two dptx_debug_set_gemm_flags values on the 16-bit conv shapes: --reps repetitions of --iters launches
+    per side, interleaved; prints every repetition, the medians and each side's spread (max - min).  --gn: the stage convs
+    run as the forward runs them, with the GroupNorm records written by the epilogue -- dptx_op_conv_groupnorm, i.e. the conv
+    plus the apply pass, which is the same on both sides (out_conv has a bias instead and is timed alone)."""
+    fa, fb = [int(v) for v in args.ab_flags.split(",")]
+    print(f"# flags {fa} vs {fb}, {args.reps} x {args.iters} launches, B = {B}, records {'on' if args.gn else 'off'}; us per launch")
+    for name, H, Cin, Cout, k, s, pad, Ho in CONV:
+        if only and name not in only:
+            continue
+        X = torch.randn(B, H, H, Cin, device="cuda").to(tdt)
+        Wt = (torch.randn(Cout, k, k, Cin, device="cuda") * (k * k * Cin) ** -0.5).to(tdt)
+        Y, Y2 = torch.empty(B, Ho, Ho, Cout, device="cuda", dtype=tdt), torch.empty(B, Ho, Ho, Cout, device="cuda", dtype=tdt)
+        bias, g = torch.randn(Cout, device="cuda"), torch.randn(Cout, device="cuda")
+        gn = args.gn and not name.startswith("out_conv") and (Ho * Ho) % 32 == 0 and Cout % 64 == 0
+        rec = torch.zeros(B * (Ho * Ho // 32 + 1) * 64, device="cuda")
+        if gn:
+            fn = lambda: lib.dptx_op_conv_groupnorm(dt, X.data_ptr(), Wt.data_ptr(), Y.data_ptr(), g.data_ptr(), bias.data_ptr(), None,
+                                                    Y2.data_ptr(), B, H, H, Cin, Cout, k, s, pad, pad, Ho, Ho, 1, 1e-5, rec.data_ptr(), st)
+        else:
+            fn = lambda: lib.dptx_op_conv(dt, X.data_ptr(), Wt.data_ptr(), bias.data_ptr(), None, Y.data_ptr(), B, H, H, Cin, Cout,
+                                          k, s, pad, pad, Ho, Ho, 0, 0, st)
+        t = {fa: [], fb: []}
+        try:
+            for _ in range(args.reps):
+                for f in (fa, fb):
+                    lib.dptx_debug_set_gemm_flags(f)
+                    t[f].append(timeit(fn) * 1e3)
+        finally:
+            lib.dptx_debug_set_gemm_flags(0)
+        med = {f: sorted(v)[len(v) // 2] for f, v in t.items()}
+        spr = {f: max(v) - min(v) for f, v in t.items()}
+        print(f"{name:12s} K={k * k * Cin:4d} N={Cout:4d} s={s} {'conv+gn' if gn else 'conv   '}  flag{fa} " + " ".join(f"{v:6.1f}" for v in t[fa]) +
+              f"  | flag{fb} " + " ".join(f"{v:6.1f}" for v in t[fb]) +
+              f"  | median {med[fa]:6.1f} vs {med[fb]:6.1f}  delta {med[fb] - med[fa]:+6.1f}  spread {spr[fa]:4.1f} / {spr[fb]:4.1f}")
+        del X, Wt, Y, Y2
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--only", default=None, help="comma separated shape names")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--batch", type=int, default=32, help="images (conv shapes only): 16 = what one of the two streams launches")
+    ap.add_argument("--ab-flags", default=None, help="two dptx_debug_set_gemm_flags values, e.g. 0,8: alternating A/B on the conv shapes")
+    ap.add_argument("--reps", type=int, default=5, help="repetitions per side of --ab-flags")
+    ap.add_argument("--gn", action="store_true", help="--ab-flags: GroupNorm records on (conv + apply pass) where the forward has them")
     args = ap.parse_args()
     global B
     B = args.batch
     only = set(args.only.split(",")) if args.only else None
     ITERS[0] = args.iters
-    build()
-    lib = load_library()
+    lib = load_library()  # builds the library first if it is missing or stale
     fp8 = args.dtype == "fp8"
     dt, tdt = DTYPES[args.dtype], (torch.bfloat16 if args.dtype in ("bf16", "fp8") else torch.float16)
     st = torch.cuda.current_stream().cuda_stream
+    if args.ab_flags:
+        return ab_conv(lib, dt, tdt, st, args, only)
     tot_ms, tot_flop = 0.0, 0.0
     # the ViT GEMMs run with the epilogue the engine gives them: fc1 bias + GELU; proj / fc2 bias + in-place fp32 residual
     EPI = {"vit.fc1": (2, False), "vit.proj": (0, True), "vit.fc2": (0, True)}
