@@ -6,7 +6,8 @@ It reads ./pretrained_models/omnidata_dpt_{normal,depth}_v2.ckpt (demo.py:36,62,
 <stem>_<task>.png and <stem>_rgb.png (demo.py:127,134) and iterates glob(img_path+'/*') for a
 directory (demo.py:158-160).  Extras for offline use: --weights PATH, --random-weights SEED,
 --dtype (default 'mixed': within 1e-3 of the reference's fp32 forward; bf16 / fp16 / fp8 are faster throughput
-modes that are not).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
+modes that are not), --batch_size N (N > 1: a directory runs N images per forward through omnidata_amd.batch_infer,
+same files, same pixels).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
 """
 import argparse
 import glob
@@ -30,6 +31,8 @@ def main(argv=None):
                         help="mixed (default) matches the reference within 1e-3; bf16 / fp16 / fp8 are ~2x faster and do not")
     parser.add_argument("--backbone", default="vitb_rn50_384", choices=["vitb_rn50_384", "vitl16_384"],
                         help="vitb_rn50_384 = DPT-Hybrid (the v2 checkpoints); vitl16_384 = DPT-Large (demo.py:81, the v1 depth model)")
+    parser.add_argument("--batch_size", type=int, default=1, metavar="N",
+                        help="N > 1: a directory goes through the batched pipeline (omnidata_amd.batch_infer), N images per forward")
     args = parser.parse_args(argv)
 
     if args.task not in ("normal", "depth"):
@@ -51,9 +54,18 @@ def main(argv=None):
         weights = "./pretrained_models/" + ("omnidata_dpt_normal_v2.ckpt" if args.task == "normal" else "omnidata_dpt_depth_v2.ckpt")
         if args.backbone == "vitl16_384" and args.task == "depth":
             weights = "./pretrained_models/omnidata_dpt_depth_v1.ckpt"  # the DPT-Large depth model (demo.py:80-81)
-    model = build_model(args.task, weights=weights, random_weights=args.random_weights, dtype=args.dtype, max_batch=1,
-                        backbone=args.backbone)
+    model = build_model(args.task, weights=weights, random_weights=args.random_weights, dtype=args.dtype,
+                        max_batch=max(args.batch_size, 1), backbone=args.backbone)
     model.to(device)
+    if args.batch_size > 1:
+        from omnidata_amd.batch_infer import BatchPredictor
+        p = Path(args.img_path)
+        if not (p.is_file() or p.is_dir()):
+            print("invalid file path!")
+            sys.exit()
+        files = [args.img_path] if p.is_file() else glob.glob(args.img_path + "/*")
+        BatchPredictor(model, args.task, batch_size=args.batch_size).predict_to_dir(files, args.output_path, verbose=True)
+        return
 
     def save_outputs(img_path, output_file_name):
         with torch.no_grad():

@@ -305,6 +305,43 @@ int dptx_postprocess_depth(const void* y_dev, void* out512_dev, void* stream);
 int dptx_resample_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_t* kk, int32_t kk_capacity,
                          int32_t* ksize);
 
+/* ---- The same for a whole batch of images of different sizes (no handle; DEVICE pointers unless stated otherwise) ----
+ * Every call is stream-ordered on `stream`, uses only the caller's workspace (no allocation, no host synchronisation, no
+ * process-lifetime cache: graph-capturable) and returns DPTX_E_INVALID for bad arguments before anything is launched.
+ *
+ * dptx_preprocess_u8_batch: B uint8 HWC images inside one packed pixel buffer -> x [B][3][S][S] fp32, per image what
+ * dptx_preprocess_u8 computes for S = 384 (bit-identical to Pillow's resampler).  `descs` is a HOST array of B descriptors,
+ * read before the call returns; image i starts at pixels_dev + descs[i].offset.  Image i's result depends on image i only.
+ * Range: 1 <= B <= 4096, S a multiple of 32 in [32, 1024], C in {1, 3}, 1 <= H, W <= 16384, row_stride_bytes >= W*C,
+ * min(H, W) <= 32*S.  The resample weights are computed on the device (fp64, Pillow's operations in Pillow's order) into the
+ * workspace, 32 images at a time; each block then forms the horizontal pass of the input rows its output tile needs once,
+ * in LDS.  Workspace: 17664 * S bytes, whatever B is (dptx_preprocess_batch_workspace_bytes; host-only). */
+typedef struct dptx_image_desc {
+  int64_t offset;            /* bytes from pixels_dev to the image's first pixel */
+  int32_t H, W, C;           /* rows, columns, channels (1 or 3)                 */
+  int32_t row_stride_bytes;  /* >= W*C                                           */
+} dptx_image_desc;
+int dptx_preprocess_batch_workspace_bytes(int32_t B, int32_t S, int64_t* bytes);
+int dptx_preprocess_u8_batch(const void* pixels_dev, const dptx_image_desc* descs, int32_t B, int32_t S,
+                             int32_t depth_normalize, void* x_dev, void* workspace, int64_t workspace_bytes, void* stream);
+/* One axis of the tables dptx_preprocess_u8_batch builds, as the device computes them: the layout of dptx_resample_coeffs
+ * in DEVICE memory (bounds_dev [out_size][2], kk_dev [out_size][*ksize_host_out]); *ksize_host_out is written on the host
+ * before the call returns.  1 <= in_size, out_size <= 2^20, ksize <= 4097, kk_capacity >= out_size * ksize. */
+int dptx_resample_coeffs_device(int32_t in_size, int32_t out_size, void* bounds_dev, void* kk_dev, int32_t kk_capacity,
+                                int32_t* ksize_host_out, void* stream);
+/* y [B][3][S][S] fp32 -> [B][S][S][3] uint8 (clamp, *255, truncate), one launch.  1 <= B <= 65535, 1 <= S <= 4096. */
+int dptx_postprocess_normal_u8_batch(const void* y_dev, int32_t B, int32_t S, void* rgb_u8_dev, void* stream);
+/* y [B][S][S] fp32 -> [B][512][512] fp32: dptx_postprocess_depth per image (bit-identical), one launch.
+ * 1 <= B <= 65535, 1 <= S <= 4096. */
+int dptx_postprocess_depth_batch(const void* y_dev, int32_t B, int32_t S, void* out512_dev, void* stream);
+/* plt.imsave's normalisation and colormap look-up: maps [B][N] fp32, lut [256][4] uint8 (the caller's colormap) ->
+ * rgba [B][N][4] uint8.  Per image lo / hi = exact min / max, n = (v - lo) / (hi - lo) in fp32 (0 when hi == lo),
+ * index = min((int)(n * 256), 255); a non-finite value reads some entry of the LUT, never outside it.  Two launches; the
+ * partial minima / maxima go through the workspace (512 * B bytes).  1 <= B <= 65535, 1 <= N <= 2^30. */
+int dptx_colorize_workspace_bytes(int32_t B, int64_t N, int64_t* bytes);
+int dptx_colorize_u8_batch(const void* maps_dev, const void* lut_dev, int32_t B, int64_t N, void* rgba_dev, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
 /* ---- 3D refocus augmentation (omnidata_tools/torch/data/refocus_augmentation.py; no handle; DEVICE pointers) ----
  * All three are stream-ordered on `stream` and use only the caller's workspace: no allocation, no host synchronisation, no
  * host read of the radii (graph-capturable).  Shapes: B >= 1, C >= 1, 1 <= H, W <= 8192, H*W <= 2^24, n_quantiles >= 1;

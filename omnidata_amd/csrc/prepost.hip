@@ -96,9 +96,12 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
   }
 }
 
+// blockIdx.y = image of the batch (the single-image entry points launch one)
 __global__ __launch_bounds__(256) void post_normal_kernel(const float* __restrict__ y, uint8_t* __restrict__ out, int HW) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= HW) return;
+  y += (size_t)blockIdx.y * 3 * HW;
+  out += (size_t)blockIdx.y * 3 * HW;
   for (int c = 0; c < 3; ++c) {
     float v = y[(size_t)c * HW + i];
     v = fminf(fmaxf(v, 0.f), 1.f);
@@ -112,6 +115,8 @@ __device__ __forceinline__ float cubic2(float x, float A) { return ((A * x - 5.f
 __global__ __launch_bounds__(256) void post_depth_kernel(const float* __restrict__ y, float* __restrict__ out, int S, int T) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= T * T) return;
+  y += (size_t)blockIdx.y * S * S;
+  out += (size_t)blockIdx.y * T * T;
   const int oy = idx / T, ox = idx - oy * T;
   const float scale = (float)S / (float)T;
   const float A = -0.75f;
@@ -221,6 +226,21 @@ int dptx_postprocess_depth(const void* y_dev, void* out512_dev, void* stream) {
   if (!y_dev || !out512_dev) return DPTX_E_INVALID;
   hipLaunchKernelGGL(post_depth_kernel, dim3((512 * 512 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)y_dev,
                      (float*)out512_dev, 384, 512);
+  return hipGetLastError() == hipSuccess ? DPTX_OK : DPTX_E_HIP;
+}
+
+int dptx_postprocess_normal_u8_batch(const void* y_dev, int32_t B, int32_t S, void* rgb_u8_dev, void* stream) {
+  if (!y_dev || !rgb_u8_dev || B < 1 || B > 65535 || S < 1 || S > 4096) return DPTX_E_INVALID;
+  const int HW = S * S;
+  hipLaunchKernelGGL(post_normal_kernel, dim3((HW + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, (const float*)y_dev,
+                     (uint8_t*)rgb_u8_dev, HW);
+  return hipGetLastError() == hipSuccess ? DPTX_OK : DPTX_E_HIP;
+}
+
+int dptx_postprocess_depth_batch(const void* y_dev, int32_t B, int32_t S, void* out512_dev, void* stream) {
+  if (!y_dev || !out512_dev || B < 1 || B > 65535 || S < 1 || S > 4096) return DPTX_E_INVALID;
+  hipLaunchKernelGGL(post_depth_kernel, dim3((512 * 512 + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, (const float*)y_dev,
+                     (float*)out512_dev, S, 512);
   return hipGetLastError() == hipSuccess ? DPTX_OK : DPTX_E_HIP;
 }
 

@@ -131,3 +131,140 @@ def depth_to_512_gpu(output: torch.Tensor) -> torch.Tensor:
     if rc != 0:
         raise RuntimeError(f"dptx_postprocess_depth failed ({rc})")
     return out
+
+
+# ------------------------------------------------------------------ batches of images of different sizes (prepost_batch.hip)
+import ctypes as _C
+
+MAX_SCALE = 32       # include/dptx.h dptx_preprocess_u8_batch: shorter side <= 32 * S
+MAX_SIDE = 16384
+
+
+class ImageDesc(_C.Structure):
+    """include/dptx.h dptx_image_desc."""
+    _fields_ = [("offset", _C.c_int64), ("H", _C.c_int32), ("W", _C.c_int32), ("C", _C.c_int32), ("row_stride_bytes", _C.c_int32)]
+
+
+_lut_cache: dict = {}
+
+
+def _as_hwc_u8(img) -> np.ndarray:
+    a = np.asarray(img)
+    if a.ndim == 2:
+        a = a[:, :, None]
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (1, 3):
+        raise ValueError("pack_images takes uint8 HW, HW1 or HW3 pixel arrays (PIL images of mode L or RGB)")
+    return np.ascontiguousarray(a)
+
+
+def batch_supported(img, image_size: int = 384) -> bool:
+    """Whether dptx_preprocess_u8_batch takes this image (mode RGB / L inside the supported range); the others go through PIL."""
+    if isinstance(img, Image.Image):
+        if img.mode not in ("RGB", "L"):
+            return False
+        w, h = img.size
+    else:
+        a = np.asarray(img) if not isinstance(img, torch.Tensor) else img
+        if a.dtype not in (np.uint8, torch.uint8) or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)):
+            return False
+        h, w = a.shape[:2]
+    return 1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE and min(h, w) <= MAX_SCALE * image_size
+
+
+def pack_images(images):
+    """-> (buf, descs): one uint8 buffer (pinned when a GPU is present) that holds the pixel arrays of `images` (PIL RGB / L
+    images or uint8 HW[C] arrays) back to back at 16-byte-aligned offsets, and the ctypes array of their dptx_image_desc."""
+    arrays = [_as_hwc_u8(im) for im in images]
+    descs = (ImageDesc * max(len(arrays), 1))()
+    off = 0
+    for i, a in enumerate(arrays):
+        H, W, Cn = a.shape
+        descs[i] = ImageDesc(off, H, W, Cn, W * Cn)
+        off = (off + a.size + 15) // 16 * 16
+    buf = torch.empty(max(off, 16), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    view = buf.numpy()
+    for d, a in zip(descs, arrays):
+        view[d.offset:d.offset + a.size] = a.reshape(-1)
+    return buf, descs
+
+
+def images_to_input_gpu(images, task: str, image_size: int = 384, device="cuda:0") -> torch.Tensor:
+    """[B,3,S,S] fp32 on `device`: image_to_input() of every image (bit-identical), from ONE host->device copy of the raw
+    pixels and one ragged-batch resize on the GPU.  Images the kernel does not take (other modes than RGB / L, sides outside
+    its range) go through image_to_input() and are copied into their slot."""
+    from ._native import call, workspace
+    images = list(images)
+    B, S = len(images), int(image_size)
+    device = torch.device(device)
+    x = torch.empty(B, 3, S, S, dtype=torch.float32, device=device)
+    if B == 0:
+        return x
+    fast = [i for i, im in enumerate(images) if batch_supported(im, S)]
+    slow = sorted(set(range(B)) - set(fast))
+    if fast:
+        buf, descs = pack_images([images[i] for i in fast])
+        ws = workspace("dptx_preprocess_batch_workspace_bytes", device, (min(len(fast), 4096), S),
+                       f"image_size {S} is not a multiple of 32 in [32, 1024]")
+        with torch.cuda.device(device):
+            dev = buf.to(device, non_blocking=True)
+            stream = torch.cuda.current_stream().cuda_stream
+            direct = len(fast) == B
+            xf = x if direct else torch.empty(len(fast), 3, S, S, dtype=torch.float32, device=device)
+            for b0 in range(0, len(fast), 4096):
+                n = min(4096, len(fast) - b0)
+                call("dptx_preprocess_u8_batch", dev.data_ptr(), _C.addressof(descs) + b0 * _C.sizeof(ImageDesc), n, S,
+                     int(task == "depth"), xf[b0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
+            if not direct:
+                x[torch.tensor(fast, device=device)] = xf
+    for i in slow:
+        im = images[i] if isinstance(images[i], Image.Image) else Image.fromarray(np.asarray(images[i]))
+        x[i:i + 1] = image_to_input(im, task, S).to(device)
+    return x
+
+
+def normals_to_u8_gpu(output: torch.Tensor) -> torch.Tensor:
+    """[B,3,S,S] float (cuda) -> [B,S,S,3] uint8 (cuda): clamp(0,1)*255 truncated, as ToPILImage does; one launch."""
+    from ._native import call, check_cuda
+    check_cuda("output", output)
+    y = output.detach().float().contiguous()
+    B, _, S, _ = y.shape
+    out = torch.empty(B, S, S, 3, dtype=torch.uint8, device=y.device)
+    with torch.cuda.device(y.device):
+        call("dptx_postprocess_normal_u8_batch", y.data_ptr(), B, S, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def depths_to_512_gpu(output: torch.Tensor) -> torch.Tensor:
+    """[B,S,S] (or [B,1,S,S]) float (cuda) -> [B,512,512] float (cuda): bicubic, clamp(0,1), 1-x per image; one launch."""
+    from ._native import call, check_cuda
+    check_cuda("output", output)
+    S = output.shape[-1]
+    y = output.detach().float().reshape(-1, S, S).contiguous()
+    out = torch.empty(y.shape[0], 512, 512, dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        call("dptx_postprocess_depth_batch", y.data_ptr(), y.shape[0], S, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def viridis_lut() -> np.ndarray:
+    """[256,4] uint8: the colormap entries plt.imsave looks up, scaled as colorize_viridis() scales them."""
+    from matplotlib import cm
+    return (cm.get_cmap("viridis")(np.arange(256)) * 255).astype(np.uint8)
+
+
+def depths_to_rgba_gpu(maps: torch.Tensor) -> torch.Tensor:
+    """[B,H,W] float (cuda) -> [B,H,W,4] uint8 (cuda): colorize_viridis() of every map (its own min / max), on the GPU."""
+    from ._native import call, check_cuda, workspace
+    check_cuda("maps", maps)
+    m = maps.detach().float().contiguous()
+    B, N = m.shape[0], m[0].numel()
+    key = str(m.device)
+    lut = _lut_cache.get(key)
+    if lut is None:
+        lut = _lut_cache[key] = torch.from_numpy(viridis_lut()).to(m.device)
+    ws = workspace("dptx_colorize_workspace_bytes", m.device, (B, N), f"colorize: unsupported shape {tuple(m.shape)}")
+    out = torch.empty(*m.shape, 4, dtype=torch.uint8, device=m.device)
+    with torch.cuda.device(m.device):
+        call("dptx_colorize_u8_batch", m.data_ptr(), lut.data_ptr(), B, N, out.data_ptr(), ws.data_ptr(), ws.numel(),
+             torch.cuda.current_stream().cuda_stream)
+    return out
