@@ -6,7 +6,8 @@ It reads ./pretrained_models/omnidata_dpt_{normal,depth}_v2.ckpt (demo.py:36,62,
 <stem>_<task>.png and <stem>_rgb.png (demo.py:127,134) and iterates glob(img_path+'/*') for a
 directory (demo.py:158-160).  Extras for offline use: --weights PATH, --random-weights SEED,
 --dtype (default 'mixed': within 1e-3 of the reference's fp32 forward; bf16 / fp16 / fp8 are faster throughput
-modes that are not), --batch_size N (N > 1: a directory runs N images per forward through omnidata_amd.batch_infer,
+modes that are not), --backbone unet (the version-1 UNet, demo.py:49-59: ./pretrained_models/omnidata_unet_normal_v1.pth;
+fp16 unless --dtype bf16; --task depth needs --weights), --batch_size N (N > 1: a directory runs N images per forward through omnidata_amd.batch_infer,
 same files, same pixels).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
 """
 import argparse
@@ -29,8 +30,9 @@ def main(argv=None):
     parser.add_argument("--random-weights", type=int, default=None, metavar="SEED", help="seeded synthetic weights (offline)")
     parser.add_argument("--dtype", default="mixed", choices=["mixed", "fp16x3", "bf16x3", "fp16", "bf16", "fp8"],
                         help="mixed (default) matches the reference within 1e-3; bf16 / fp16 / fp8 are ~2x faster and do not")
-    parser.add_argument("--backbone", default="vitb_rn50_384", choices=["vitb_rn50_384", "vitl16_384"],
-                        help="vitb_rn50_384 = DPT-Hybrid (the v2 checkpoints); vitl16_384 = DPT-Large (demo.py:81, the v1 depth model)")
+    parser.add_argument("--backbone", default="vitb_rn50_384", choices=["vitb_rn50_384", "vitl16_384", "unet"],
+                        help="vitb_rn50_384 = DPT-Hybrid (the v2 checkpoints); vitl16_384 = DPT-Large (demo.py:81, the v1 depth model); "
+                             "unet = the version-1 UNet (demo.py:49-59)")
     parser.add_argument("--batch_size", type=int, default=1, metavar="N",
                         help="N > 1: a directory goes through the batched pipeline (omnidata_amd.batch_infer), N images per forward")
     args = parser.parse_args(argv)
@@ -54,8 +56,22 @@ def main(argv=None):
         weights = "./pretrained_models/" + ("omnidata_dpt_normal_v2.ckpt" if args.task == "normal" else "omnidata_dpt_depth_v2.ckpt")
         if args.backbone == "vitl16_384" and args.task == "depth":
             weights = "./pretrained_models/omnidata_dpt_depth_v1.ckpt"  # the DPT-Large depth model (demo.py:80-81)
-    model = build_model(args.task, weights=weights, random_weights=args.random_weights, dtype=args.dtype,
-                        max_batch=max(args.batch_size, 1), backbone=args.backbone)
+    unet = args.backbone == "unet"
+    if unet:
+        # the version-1 model: rgb in [0, 1] (get_transform('rgb'), no normalisation) for both tasks, [B,out,H,W] results
+        from omnidata_amd.unet import build_unet
+        if args.weights is None and args.random_weights is None:
+            if args.task == "depth":
+                print("--backbone unet --task depth needs --weights (the reference publishes the v1 UNet for normals only)")
+                sys.exit()
+            weights = "./pretrained_models/omnidata_unet_normal_v1.pth"
+        model = build_unet(args.task, weights=weights, random_weights=args.random_weights,
+                           dtype="bf16" if args.dtype == "bf16" else "fp16", max_batch=min(max(args.batch_size, 1), 32))
+        if args.task == "depth":
+            args.batch_size = 1   # the batched pipeline's depth pre-processing normalises to [-1, 1]: per-image loop below
+    else:
+        model = build_model(args.task, weights=weights, random_weights=args.random_weights, dtype=args.dtype,
+                            max_batch=max(args.batch_size, 1), backbone=args.backbone)
     model.to(device)
     if args.batch_size > 1:
         from omnidata_amd.batch_infer import BatchPredictor
@@ -74,9 +90,11 @@ def main(argv=None):
             img = Image.open(img_path)
             # Resize/CenterCrop/ToTensor(/Normalize) run on the GPU from the raw uint8 pixels (bit-identical to
             # the PIL/torchvision path of the reference; RGBA and other modes fall back to PIL inside)
-            img_tensor = pp.image_to_input_gpu(img, args.task, device)
+            img_tensor = pp.image_to_input_gpu(img, "normal" if unet else args.task, device)
             pp.rgb_preview(img).save(os.path.join(args.output_path, f"{output_file_name}_rgb.png"))
             output = model(img_tensor).clamp(min=0, max=1)
+            if unet and args.task == "depth":
+                output = output.squeeze(1)   # [B,1,H,W] -> [B,H,W], what the DPT depth model returns
             if args.task == "depth":
                 d512 = pp.depth_to_512_gpu(output)          # bicubic 384->512, clamp, 1-x on the GPU
                 Image.fromarray(pp.colorize_viridis(d512.cpu().numpy())).save(save_path)

@@ -685,6 +685,86 @@ int dptx_op_head_tail(int32_t dtype, const void* H0, const void* W2, const float
                       const float* b4, float* y, int32_t B, int32_t Hs, int32_t Ws, int32_t C,
                       int32_t relu_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The reference's version-1 UNet (omnidata_tools/torch/modules/unet.py:8-105; checkpoint omnidata_unet_normal_v1.pth),
+ * inference forward: downsample = 6, in_channels = 3, out_channels 1..4, GroupNorm(8) + ReLU behind every 3x3
+ * convolution, 2x2 max-pool down, bilinear x2 (align_corners=False) up, torch.cat((up, skip)) into each up block.
+ * A handle type of its own with the conventions of dptx_handle.  UNetRelu, UNetV2 and other depths are not covered.
+ *
+ * Precision: NHWC 16-bit activations (fp16, the default, or bf16), 16-bit convolution weights, fp32 accumulation,
+ * fp32 norm vectors and biases.  Every convolution stores its raw output (bias added) in 16 bit; the GroupNorm
+ * statistics are those of the stored values; the last GroupNorm + ReLU + 1x1 convolution stay in fp32.  Results are
+ * bitwise reproducible and an image's result does not depend on the rest of its batch. */
+typedef struct dptx_unet_engine* dptx_unet_handle;
+typedef struct dptx_unet_config {
+  int32_t out_channels; /* 1..4 (normals 3, depth 1)                                                         */
+  int32_t max_batch;    /* 1..32: the arena is planned once for max_batch x max_height x max_width           */
+  int32_t dtype;        /* DPTX_DTYPE_FP16 (default) or DPTX_DTYPE_BF16; every other dtype: DPTX_E_INVALID   */
+  int32_t device_id;    /* HIP device ordinal; -1 = host-only handle (weight packing only)                   */
+  int32_t max_height;   /* multiples of 64 in 64..512                                                        */
+  int32_t max_width;
+  int32_t reserved[2];  /* must be zero                                                                      */
+} dptx_unet_config;
+/* out_channels 3, max_batch 32, fp16, device 0, 384 x 384 */
+void dptx_unet_default_config(dptx_unet_config* cfg);
+int dptx_unet_create(dptx_unet_handle* out, const dptx_unet_config* cfg);
+void dptx_unet_destroy(dptx_unet_handle h);
+const char* dptx_unet_last_error(dptx_unet_handle h);
+/* One tensor of the reference's state dict (174 keys: "down1.conv1.weight", "down_blocks.3.bn2.bias", "mid_conv1.weight",
+ * "bn1.weight", "up_blocks.5.conv1.weight", "last_conv2.bias", ...; OIHW convolution weights), fp32 on the host.  Unknown keys
+ * or wrong shapes -> DPTX_E_KEY. */
+int dptx_unet_load_tensor(dptx_unet_handle h, const char* ref_key, const float* host_fp32, const int64_t* shape, int32_t ndim);
+/* Strict: every key must have been loaded (DPTX_E_KEY, the message lists the missing ones).  Packs one blob -- the entries in
+ * state-dict order, each 256-byte aligned: 3x3 weights as 16-bit [O][ky][kx][I] (an up block's conv1 keeps torch.cat's order
+ * of I: the up-sampled channels, then the skip), down1.conv1 as 16-bit [16][32] with k = (ky*3 + kx)*3 + c and k = 27..31 zero,
+ * last_conv2.weight, biases and norm vectors verbatim in fp32 -- and, on a device handle, uploads it and allocates the arena. */
+int dptx_unet_finalize_weights(dptx_unet_handle h);
+size_t dptx_unet_packed_bytes(dptx_unet_handle h);
+/* byte offset and size of one state-dict tensor inside the packed blob */
+int dptx_unet_packed_entry(dptx_unet_handle h, const char* ref_key, int64_t* offset, int64_t* bytes);
+/* the packed blob (works on host-only handles) */
+int dptx_unet_export_packed_host(dptx_unet_handle h, void* dst_host, size_t bytes);
+/* packed weights + activation arena of a device handle */
+size_t dptx_unet_device_bytes(dptx_unet_handle h);
+/* x [B,3,H,W] NCHW of x_dtype (DPTX_IO_*), values in [0, 1] -> y [B,out_channels,H,W] NCHW fp32.  H and W: multiples of 64 in
+ * 64..max_height / max_width, 1 <= B <= max_batch, otherwise DPTX_E_INVALID.  Asynchronous on `stream`; no allocation and no
+ * synchronisation inside. */
+int dptx_unet_forward(dptx_unet_handle h, const void* x_dev, void* y_dev, int32_t batch, int32_t height, int32_t width,
+                      int32_t x_dtype, void* stream);
+/* Raw convolution outputs are stored before normalisation, so fp16 can overflow on weights nobody has seen.  The GroupNorm
+ * statistics read every stored element: a non-finite sum sets a STICKY device flag.  Waits for `stream`, stores the flag in
+ * *nonfinite and clears it when reset != 0 (the convention of dptx_range_status). */
+int dptx_unet_range_status(dptx_unet_handle h, int32_t* nonfinite, int32_t reset, void* stream);
+/* debug: every byte of the arena := byte_value (after a device synchronisation) */
+int dptx_unet_debug_arena_fill(dptx_unet_handle h, int32_t byte_value);
+/* debug / timing: a forward that enqueues only the launches of the classes in `classes` (1: small-channel convolutions and
+ * the im2col, 2: launch_gemm convolutions, 4: GroupNorm / up-sample / head passes; 7 = dptx_unet_forward).  Anything but 7
+ * leaves garbage in y: for timing the classes only (tools/unet_bench.py). */
+int dptx_unet_debug_forward_classes(dptx_unet_handle h, const void* x_dev, void* y_dev, int32_t batch, int32_t height,
+                                    int32_t width, int32_t x_dtype, int32_t classes, void* stream);
+
+/* Op-level entry points of the UNet kernels (unet.hip), BF16 / FP16, NHWC 16-bit.
+ * 3x3 convolution, pad 1, stride 1, bias, for (Cin, Cout) in {(3,16), (16,16), (16,32), (32,32), (32,64), (48,16), (96,32)}:
+ * X [B][H][W][x_pix_stride], the layer reads channels x_off .. x_off + Cin (both multiples of 8); Wt [Cout][3][3][Cin];
+ * Y [B][H][W][Cout] raw output; gn_part (may be NULL): B * dptx_op_unet_conv_records(H, W) * 8 float2 (sum, sum of squares)
+ * records of the stored values per (image, 8 x 32 tile, group of GroupNorm(8)).  Cin = 3: X is the fp32 NCHW image [B,3,H,W],
+ * Wt the padded [Cout][32] block (k = (ky*3 + kx)*3 + c) and `scratch` holds B*H*W*32 16-bit elements. */
+int dptx_op_unet_conv3x3(int32_t dtype, const void* X, int32_t x_pix_stride, int32_t x_off, const void* Wt, const float* bias,
+                         void* Y, float* gn_part, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* scratch,
+                         void* stream);
+int32_t dptx_op_unet_conv_records(int32_t H, int32_t W);
+/* GroupNorm(8) + ReLU of a dense X [B][H][W][C] (C % 16 == 0, 16..1024): statistics pass, (mean, rstd) in double, apply.
+ * Y (may be NULL): full size, into channels y_off .. y_off + C of pixels y_pix_stride apart; P (may be NULL; H, W even): the
+ * 2x2 / 2 max-pooled result, likewise.  scratch_f32: B * (dptx_op_unet_gn_records(H*W, C) * 16 + 16) floats. */
+int dptx_op_unet_groupnorm(int32_t dtype, const void* X, const float* gamma, const float* beta, void* Y, int32_t y_pix_stride,
+                           int32_t y_off, void* P, int32_t p_pix_stride, int32_t p_off, int32_t B, int32_t H, int32_t W,
+                           int32_t C, float eps, void* scratch_f32, void* stream);
+int32_t dptx_op_unet_gn_records(int32_t HW, int32_t C);
+/* bilinear x2, align_corners=False (torch's rule: weights 0.25 / 0.75, edge clamp): X [B][H][W][C] dense -> channels
+ * y_off .. y_off + C of Y [B][2H][2W][y_pix_stride] */
+int dptx_op_unet_upsample2x(int32_t dtype, const void* X, void* Y, int32_t B, int32_t H, int32_t W, int32_t C,
+                            int32_t y_pix_stride, int32_t y_off, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,27 @@ ABI = [
     ("dptx_op_gemm_stream", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("dptx_op_gemm_stream32", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("dptx_op_head_tail", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    # the version-1 UNet (omnidata_amd/unet.py): a handle type of its own, and the op-level entry points of its kernels
+    ("dptx_unet_default_config", None, [_vp]),
+    ("dptx_unet_create", C.c_int, [C.POINTER(_vp), _vp]),
+    ("dptx_unet_destroy", None, [_vp]),
+    ("dptx_unet_last_error", C.c_char_p, [_vp]),
+    ("dptx_unet_load_tensor", C.c_int, [_vp, C.c_char_p, _vp, _i64p, _i32]),
+    ("dptx_unet_finalize_weights", C.c_int, [_vp]),
+    ("dptx_unet_packed_bytes", _sz, [_vp]),
+    ("dptx_unet_packed_entry", C.c_int, [_vp, C.c_char_p, _i64p, _i64p]),
+    ("dptx_unet_export_packed_host", C.c_int, [_vp, _vp, _sz]),
+    ("dptx_unet_device_bytes", _sz, [_vp]),
+    ("dptx_unet_forward", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    ("dptx_unet_range_status", C.c_int, [_vp, C.POINTER(C.c_int32), _i32, _vp]),
+    ("dptx_unet_debug_arena_fill", C.c_int, [_vp, _i32]),
+    ("dptx_unet_debug_forward_classes", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("dptx_op_unet_conv3x3", C.c_int, [_i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    ("dptx_op_unet_conv_records", _i32, [_i32, _i32]),
+    ("dptx_op_unet_groupnorm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float,
+                                         _vp, _vp]),
+    ("dptx_op_unet_gn_records", _i32, [_i32, _i32]),
+    ("dptx_op_unet_upsample2x", C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
 ]
 
 _lib = None
