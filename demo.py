@@ -8,7 +8,10 @@ directory (demo.py:158-160).  Extras for offline use: --weights PATH, --random-w
 --dtype (default 'mixed': within 1e-3 of the reference's fp32 forward; bf16 / fp16 / fp8 are faster throughput
 modes that are not), --backbone unet (the version-1 UNet, demo.py:49-59: ./pretrained_models/omnidata_unet_normal_v1.pth;
 fp16 unless --dtype bf16; --task depth needs --weights), --batch_size N (N > 1: a directory runs N images per forward through omnidata_amd.batch_infer,
-same files, same pixels).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
+same files, same pixels), --full_frame {squash,aspect} [--renormalize] (the whole image instead of the centre crop, <stem>_<task>.png at
+the image's own size and <stem>_rgb.png = the image unchanged; any --batch_size; squash = a fixed 384x384 network input as
+paper_code/oasis_eval_tta.py:324-339, aspect = the aspect-preserving size of modules/midas/transforms.py:94-160; --renormalize
+makes the resized normals unit length again, oasis_eval_tta.py:339).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
 """
 import argparse
 import glob
@@ -35,6 +38,10 @@ def main(argv=None):
                              "unet = the version-1 UNet (demo.py:49-59)")
     parser.add_argument("--batch_size", type=int, default=1, metavar="N",
                         help="N > 1: a directory goes through the batched pipeline (omnidata_amd.batch_infer), N images per forward")
+    parser.add_argument("--full_frame", default=None, choices=["squash", "aspect"],
+                        help="keep the whole image (no centre crop) and write the map at the image's own size: squash = a fixed "
+                             "square network input, aspect = the reference's aspect-preserving network size per image")
+    parser.add_argument("--renormalize", action="store_true", help="--full_frame, normal: unit-length normals after the resize")
     args = parser.parse_args(argv)
 
     if args.task not in ("normal", "depth"):
@@ -57,6 +64,16 @@ def main(argv=None):
         if args.backbone == "vitl16_384" and args.task == "depth":
             weights = "./pretrained_models/omnidata_dpt_depth_v1.ckpt"  # the DPT-Large depth model (demo.py:80-81)
     unet = args.backbone == "unet"
+    if args.renormalize and (args.full_frame is None or args.task != "normal"):
+        print("--renormalize needs --full_frame and --task normal")
+        sys.exit()
+    if unet and args.full_frame == "aspect":
+        print("--backbone unet takes --full_frame squash only: its network sizes are multiples of 64 up to 512, which the "
+              "aspect-preserving size rule does not produce")
+        sys.exit()
+    if unet and args.full_frame is not None and args.task == "depth":
+        print("--backbone unet --task depth has no batched pre-processing (rgb in [0, 1]): --full_frame is not available")
+        sys.exit()
     if unet:
         # the version-1 model: rgb in [0, 1] (get_transform('rgb'), no normalisation) for both tasks, [B,out,H,W] results
         from omnidata_amd.unet import build_unet
@@ -73,14 +90,15 @@ def main(argv=None):
         model = build_model(args.task, weights=weights, random_weights=args.random_weights, dtype=args.dtype,
                             max_batch=max(args.batch_size, 1), backbone=args.backbone)
     model.to(device)
-    if args.batch_size > 1:
+    if args.batch_size > 1 or args.full_frame is not None:
         from omnidata_amd.batch_infer import BatchPredictor
         p = Path(args.img_path)
         if not (p.is_file() or p.is_dir()):
             print("invalid file path!")
             sys.exit()
         files = [args.img_path] if p.is_file() else glob.glob(args.img_path + "/*")
-        BatchPredictor(model, args.task, batch_size=args.batch_size).predict_to_dir(files, args.output_path, verbose=True)
+        BatchPredictor(model, args.task, batch_size=max(args.batch_size, 1), full_frame=args.full_frame,
+                       renormalize=args.renormalize).predict_to_dir(files, args.output_path, verbose=True)
         return
 
     def save_outputs(img_path, output_file_name):

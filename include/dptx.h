@@ -342,6 +342,49 @@ int dptx_colorize_workspace_bytes(int32_t B, int64_t N, int64_t* bytes);
 int dptx_colorize_u8_batch(const void* maps_dev, const void* lut_dev, int32_t B, int64_t N, void* rgba_dev, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* ---- Full-frame inference: the whole image in, a map of the image's own size out (no handle; DEVICE pointers unless stated) ----
+ * The reference's whole-image protocol (paper_code/oasis_eval_tta.py:324-339: a fixed network size regardless of the aspect,
+ * the prediction back to (orig_height, orig_width) with F.interpolate(mode='bilinear'), normalised again) and the aspect-
+ * preserving network size DPT is normally run with (modules/midas/transforms.py:94-160, Resize.get_size with
+ * keep_aspect_ratio=True, ensure_multiple_of=32).  Same conventions as the block above: stream-ordered, the caller's workspace
+ * only, no allocation, no host synchronisation, no cache (graph-capturable), DPTX_E_INVALID before anything is launched; `descs`
+ * is a HOST array read before the call returns; image i's result depends on image i only; no float atomics, bitwise
+ * reproducible.
+ *
+ * dptx_preprocess_u8_rect_batch: B uint8 HWC images (C in {1, 3}) of one packed buffer -> x [B][3][OH][OW] fp32; per image
+ * exactly ToTensor(img.resize((OW, OH), PIL.Image.BILINEAR)) -- the whole image, no crop, an independent scale per axis, either
+ * axis up or down (Pillow's antialiased two-pass 8-bit resampler, bit-identical) -- then the optional Normalize(0.5, 0.5) and
+ * the 1 -> 3 channel repeat.  Range: 1 <= B <= 4096; OH, OW multiples of 32 in [64, 1024]; 1 <= H, W <= 16384; H <= 32*OH;
+ * W <= 32*OW; row_stride_bytes >= W*C.  Workspace: 8832 * (OH + OW) bytes, whatever B is (host-only). */
+int dptx_preprocess_rect_batch_workspace_bytes(int32_t B, int32_t OH, int32_t OW, int64_t* bytes);
+int dptx_preprocess_u8_rect_batch(const void* pixels_dev, const dptx_image_desc* descs, int32_t B, int32_t OH, int32_t OW,
+                                  int32_t depth_normalize, void* x_dev, void* workspace, int64_t workspace_bytes, void* stream);
+/* dptx_postprocess_resize_batch: y [B][C][h][w] fp32 -> B outputs of DIFFERENT sizes in one packed buffer.  descs[i] gives
+ * output i: offset (bytes from out_dev), H, W and row_stride_bytes (rows may be padded; the field C is ignored); no byte outside
+ * [row start, row start + W * bytes per pixel) of a row is written.  Source coordinates are ATen's (align_corners=False):
+ * scale = in / out in fp32, src = scale * (dst + 0.5) - 0.5, clamped at 0 for bilinear only; an axis with in == out is copied.
+ *   DPTX_RESIZE_NORMAL_U8   C = 3: bilinear (not antialiased: F.interpolate), clamp(0, 1) * 255 truncated -> [H][W][3] uint8
+ *                           (demo.py:140,150 at the image's own size); 3 bytes per pixel, any byte alignment;
+ *   DPTX_RESIZE_NORMAL_F32  C = 3: the same value unquantised, planar [3][H][W] fp32, planes H * row_stride_bytes apart;
+ *   | DPTX_RESIZE_RENORM    (both NORMAL modes) after the interpolation and before the clamp: n = 2v - 1,
+ *                           n^ = n / max(||n||_2, 1e-12) (F.normalize, oasis_eval_tta.py:339,441-445), re-encoded (n^ + 1) / 2;
+ *   DPTX_RESIZE_DEPTH_F32   C = 1: bicubic (A = -0.75), clamp(0, 1), 1 - x (demo.py:143-145 at any size) -> [H][W] fp32;
+ *   DPTX_RESIZE_DEPTH_RGBA  C = 1: the same, then plt.imsave's normalisation and look-up as dptx_colorize_u8_batch defines
+ *                           them (lut_dev: [256][4] uint8) -> [H][W][4] uint8; per image min / max over exactly the
+ *                           DPTX_RESIZE_DEPTH_F32 values, 64 partials per image through the workspace in a fixed order.
+ * The 4-byte-per-pixel modes need offset, row_stride_bytes and out_dev to be multiples of 4.  lut_dev and the workspace
+ * (16384 bytes, whatever B is; host-only) are used by DPTX_RESIZE_DEPTH_RGBA only and may be NULL / 0 otherwise.
+ * Range: 1 <= B <= 4096; 1 <= h, w <= 4096; 1 <= H, W <= 16384; row_stride_bytes >= W * bytes per pixel. */
+#define DPTX_RESIZE_NORMAL_U8 1
+#define DPTX_RESIZE_NORMAL_F32 2
+#define DPTX_RESIZE_DEPTH_F32 3
+#define DPTX_RESIZE_DEPTH_RGBA 4
+#define DPTX_RESIZE_RENORM 16
+int dptx_postprocess_resize_workspace_bytes(int32_t B, int32_t mode, int64_t* bytes);
+int dptx_postprocess_resize_batch(const void* y_dev, int32_t B, int32_t C, int32_t h, int32_t w, const dptx_image_desc* descs,
+                                  int32_t mode, void* out_dev, const void* lut_dev, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
+
 /* ---- 3D refocus augmentation (omnidata_tools/torch/data/refocus_augmentation.py; no handle; DEVICE pointers) ----
  * All three are stream-ordered on `stream` and use only the caller's workspace: no allocation, no host synchronisation, no
  * host read of the radii (graph-capturable).  Shapes: B >= 1, C >= 1, 1 <= H, W <= 8192, H*W <= 2^24, n_quantiles >= 1;

@@ -3,6 +3,12 @@
 Per batch: decode in a thread pool -> one packed upload -> dptx_preprocess_u8_batch -> model(x) -> batched post-processing
 -> one download into pinned memory -> PNG encode in the thread pool.  Batch k+1 is decoded while batch k is on the GPU and
 batch k-1 is being encoded.  The files written are those of demo.py's per-image loop, pixel for pixel.
+
+full_frame="squash" / "aspect" keeps the whole image instead of the centre crop and returns maps of the image's own size:
+dptx_preprocess_u8_rect_batch -> model(x) at a rectangular network size -> dptx_postprocess_resize_batch.  "squash" is the
+reference's fixed-input protocol (paper_code/oasis_eval_tta.py:324-339: image_size x image_size whatever the aspect);
+"aspect" takes the network size per image from the reference's Resize.get_size (modules/midas/transforms.py:94-160), buckets
+the images by network shape and runs the largest shape first, so the model plans its arena once.
 """
 from __future__ import annotations
 
@@ -10,6 +16,9 @@ import os
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
 
+import warnings
+
+import numpy as np
 import torch
 from PIL import Image
 
@@ -26,12 +35,52 @@ def _decode(item):
     return item
 
 
+def _size_of(item):
+    """(w, h) of an input without decoding it: a path's header, a PIL image's size, an array's shape."""
+    if isinstance(item, (str, os.PathLike)):
+        with Image.open(item) as img:
+            return img.size
+    if isinstance(item, Image.Image):
+        return item.size
+    h, w = item.shape[:2]
+    return int(w), int(h)
+
+
+def plan_full_frame(sizes, mode: str, image_size: int = 384, batch_size: int = 32, multiple: int = 32):
+    """sizes [(w, h)] in input order -> (chunks, capped): chunks = [((net_h, net_w), [input indices])], every chunk one network
+    shape and at most batch_size images in input order, the shape with the largest net_h * net_w first (then by first
+    appearance); capped = the indices whose network size pp.full_frame_net_size() had to cut back.  mode "squash": one shape,
+    image_size x image_size."""
+    if mode not in ("squash", "aspect"):
+        raise ValueError('full_frame must be None, "squash" or "aspect"')
+    buckets, capped = {}, []
+    for i, (w, h) in enumerate(sizes):
+        if mode == "squash":
+            net = (image_size, image_size)
+        else:
+            nw, nh, cut = pp.full_frame_net_size(w, h, image_size, multiple)
+            net = (nh, nw)
+            if cut:
+                capped.append(i)
+        buckets.setdefault(net, []).append(i)
+    order = sorted(buckets, key=lambda net: (-net[0] * net[1], buckets[net][0]))
+    chunks = [(net, buckets[net][k:k + batch_size]) for net in order for k in range(0, len(buckets[net]), batch_size)]
+    return chunks, capped
+
+
 class BatchPredictor:
-    def __init__(self, model, task: str, batch_size: int = 32, workers: int = 8, image_size: int = 384):
+    def __init__(self, model, task: str, batch_size: int = 32, workers: int = 8, image_size: int = 384, full_frame=None,
+                 renormalize: bool = False):
         if task not in ("normal", "depth"):
             raise ValueError("task should be one of the following: normal, depth")
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")
+        if full_frame not in (None, "squash", "aspect"):
+            raise ValueError('full_frame must be None, "squash" or "aspect"')
+        if renormalize and (full_frame is None or task != "normal"):
+            raise ValueError("renormalize applies to full-frame surface normals only")
+        self.full_frame, self.renormalize = full_frame, bool(renormalize)
+        self.capped = []   # full_frame="aspect": input indices of the last run whose network size was cut back to the supported range
         self.model, self.task, self.batch_size, self.image_size = model, task, int(batch_size), int(image_size)
         self.workers = max(1, min(int(workers), MAX_WORKERS))
         self.device = next(model.parameters()).device
@@ -73,10 +122,82 @@ class BatchPredictor:
                 return
             futures = nxt
 
+    # ---- full frame: the whole image in, a map of the image's own size out
+    def _run_full(self, images, net_hw):
+        """-> list of device tensors, image i at its own size: normal [H,W,3] uint8, depth [H,W,4] uint8 (viridis RGBA)."""
+        with torch.no_grad():
+            x = pp.images_to_input_rect_gpu(images, self.task, net_hw, self.device)
+            y = self.model(x).clamp(min=0, max=1)
+            sizes = [_size_of(im)[::-1] for im in images]
+            if self.task == "depth":
+                return pp.resize_outputs_gpu(y, sizes, "depth_rgba")
+            return pp.resize_outputs_gpu(y, sizes, "normal_u8", self.renormalize)
+
+    def _full_chunks(self, items, pool):
+        """Yields (input indices, decoded images, outputs) per chunk of plan_full_frame(), in the plan's order; the next chunk is
+        decoded while this one is on the GPU.  The sizes come from the files' headers first: an unreadable file raises here,
+        before anything has run."""
+        sizes = list(pool.map(_size_of, items))
+        chunks, self.capped = plan_full_frame(sizes, self.full_frame, self.image_size, self.batch_size)
+        if self.capped:
+            warnings.warn(f"full_frame='aspect': the network size of {len(self.capped)} image(s) was cut back to a side of "
+                          f"{pp.MAX_NET_SIDE} (BatchPredictor.capped lists them)", stacklevel=3)
+        futures = [pool.submit(_decode, items[i]) for i in chunks[0][1]] if chunks else []
+        for k, (net_hw, idxs) in enumerate(chunks):
+            following = [pool.submit(_decode, items[i]) for i in chunks[k + 1][1]] if k + 1 < len(chunks) else []
+            images = [f.result() for f in futures]
+            yield idxs, images, self._run_full(images, net_hw)
+            futures = following
+
+    def _predict_full(self, items):
+        ready, nxt = {}, 0   # outputs that wait for an earlier input of another bucket stay on the device
+        with ThreadPoolExecutor(self.workers) as pool:
+            for idxs, _, outs in self._full_chunks(items, pool):
+                ready.update(zip(idxs, outs))
+                while nxt in ready:
+                    yield ready.pop(nxt)
+                    nxt += 1
+
+    def _predict_full_to_dir(self, paths, output_path, verbose):
+        def save(img, pixels, stem):
+            rgb = img if img.mode in ("1", "L", "LA", "P", "RGB", "RGBA", "I", "I;16") else img.convert("RGB")
+            rgb.save(os.path.join(output_path, f"{stem}_rgb.png"))
+            Image.fromarray(pixels).save(os.path.join(output_path, f"{stem}_{self.task}.png"))
+
+        writes, nxt = {}, 0   # input index -> (future, save_path)
+
+        def flush(everything):
+            nonlocal nxt
+            while nxt in writes and (everything or writes[nxt][0].done()):
+                f, save_path = writes.pop(nxt)
+                f.result()
+                if verbose:
+                    print(f"Reading input {paths[nxt]} ...")
+                    print(f"Writing output {save_path} ...")
+                nxt += 1
+
+        with ThreadPoolExecutor(self.workers) as pool:
+            for idxs, images, outs in self._full_chunks(paths, pool):
+                flat = torch.cat([o.reshape(-1) for o in outs])
+                host = torch.empty(flat.shape, dtype=flat.dtype, pin_memory=True)
+                host.copy_(flat, non_blocking=True)
+                torch.cuda.current_stream(self.device).synchronize()
+                arr, at = host.numpy(), 0
+                for i, img, o in zip(idxs, images, outs):
+                    stem = os.path.splitext(os.path.basename(paths[i]))[0]
+                    pixels = arr[at:at + o.numel()].reshape(tuple(o.shape))
+                    at += o.numel()
+                    writes[i] = (pool.submit(save, img, pixels, stem), os.path.join(output_path, f"{stem}_{self.task}.png"))
+                flush(False)
+            flush(True)
+
     def predict(self, images_or_paths):
-        """Yields one device tensor per input, in input order (normal: [S,S,3] uint8, depth: [512,512,4] uint8 RGBA).
-        Nothing is read back."""
+        """Yields one device tensor per input, in input order (normal: [S,S,3] uint8, depth: [512,512,4] uint8 RGBA; with
+        full_frame the image's own size: [H,W,3] uint8, depth [H,W,4] uint8 RGBA).  Nothing is read back."""
         items = list(images_or_paths)
+        if self.full_frame is not None:
+            yield from self._predict_full(items)
+            return
         with ThreadPoolExecutor(self.workers) as pool:
             for _, images, error in self._batches(items, pool):
                 if images:
@@ -89,6 +210,8 @@ class BatchPredictor:
         file, in input order.  An unreadable file raises what Image.open raises, after every earlier file has been written."""
         paths = [os.fspath(p) for p in paths]
         os.makedirs(output_path, exist_ok=True)
+        if self.full_frame is not None:   # <stem>_<task>.png at the image's own size, <stem>_rgb.png = the image unchanged
+            return self._predict_full_to_dir(paths, output_path, verbose)
         writes = deque()   # (future, path, save_path) in input order
 
         def save(img, pixels, stem):

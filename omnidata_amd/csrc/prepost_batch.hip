@@ -13,79 +13,12 @@
 //                         reads that tile: lanes run along the output columns, so the tile reads, the weight reads and the
 //                         fp32 stores are conflict-free / coalesced.
 //        The descriptors travel by value in the kernel arguments (32 per launch), so there is no device table to fill.
+//        The coefficient code and the tile live in resample_batch.h, shared with fullframe.hip (the whole image -> OH x OW).
 //  post: colorize (plt.imsave: per-image min / max -> normalise -> LUT) in two launches; the batched normal / depth post kernels
 //        are the single-image ones of prepost.hip with a batch index.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdint>
-
-#include "../../include/dptx.h"
-
-#pragma clang fp contract(off)
+#include "resample_batch.h"
 
 namespace {
-
-constexpr int PRECISION_BITS = 32 - 8 - 2;  // Pillow: 22
-constexpr int CHUNK = 32;                   // images per launch (descriptors by value: 32 * 56 B of kernel arguments)
-constexpr int KMAX = 67;                    // taps per output at the scale limit: ceil(support < 33) * 2 + 1
-constexpr int TC = 32;                      // output columns of a tile
-constexpr int TR_MAX = 16;                  // output rows of a tile (16 or 8)
-constexpr int ROWS_CAP = 304;               // input rows whose horizontal pass one tile holds
-constexpr int STAGE_DW = 3072;              // dwords of raw input rows staged at a time
-
-struct ImgArg {
-  long long offset;
-  int H, W, C, stride;
-  int oh, ow, top, left;  // resized size and the centre crop's origin in it
-  int ksh, ksv, tr, pad;
-};
-struct ImgArgs {
-  ImgArg d[CHUNK];
-};
-
-// one output coordinate of Pillow's bilinear (triangle, support 1) filter over the whole axis: bounds2 = {first tap, taps},
-// kk[0, ksize) = 22-bit fixed-point weights (zero behind the taps)
-__host__ __device__ inline int coeff_ksize(int in_size, int out_size) {
-  const double scale = (double)in_size / out_size;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 1.0 * filterscale;
-  return (int)ceil(support) * 2 + 1;
-}
-
-__device__ inline void coeff_one(int in_size, int out_size, int xx, int ksize, int* __restrict__ bounds2, int* __restrict__ kk) {
-  const double scale = (double)in_size / out_size;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = 1.0 * filterscale;
-  const double center = (xx + 0.5) * scale;
-  const double ss = 1.0 / filterscale;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  if (xmax > ksize) xmax = ksize;  // never taken (Pillow's own bound); keeps the stores inside the row whatever the input
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) {
-    double t = (x + xmin - center + 0.5) * ss;
-    if (t < 0.0) t = -t;
-    const double w = t < 1.0 ? 1.0 - t : 0.0;
-    ww += w;
-  }
-  for (int x = 0; x < ksize; ++x) {
-    int q = 0;
-    if (x < xmax) {
-      double t = (x + xmin - center + 0.5) * ss;
-      if (t < 0.0) t = -t;
-      double w = t < 1.0 ? 1.0 - t : 0.0;
-      if (ww != 0.0) w /= ww;
-      q = w < 0 ? (int)(-0.5 + w * (1 << PRECISION_BITS)) : (int)(0.5 + w * (1 << PRECISION_BITS));
-    }
-    kk[x] = q;
-  }
-  bounds2[0] = xmin;
-  bounds2[1] = xmax;
-}
 
 __global__ __launch_bounds__(256) void coeff_axis_kernel(int in_size, int out_size, int ksize, int* __restrict__ bounds,
                                                          int* __restrict__ kk) {
@@ -94,146 +27,22 @@ __global__ __launch_bounds__(256) void coeff_axis_kernel(int in_size, int out_si
   coeff_one(in_size, out_size, xx, ksize, bounds + 2 * (size_t)xx, kk + (size_t)xx * ksize);
 }
 
-// workspace of one image slot (ints): [bh 2S | kh S*KMAX | bv 2S | kv S*KMAX]; rows of kh / kv are ksh / ksv ints apart
-__host__ __device__ inline size_t slot_ints(int S) { return (size_t)2 * (2 + KMAX) * S; }
-
 __global__ __launch_bounds__(256) void coeff_kernel(ImgArgs args, int n_img, int S, int* __restrict__ ws) {
   const int j = blockIdx.x * 256 + threadIdx.x;  // [0, 2S): horizontal axis first
   const int i = blockIdx.y;
   if (i >= n_img || j >= 2 * S) return;
-  const ImgArg& a = args.d[i];
-  int* base = ws + (size_t)i * slot_ints(S);
-  if (j < S)
-    coeff_one(a.W, a.ow, a.left + j, a.ksh, base + 2 * j, base + 2 * S + (size_t)j * a.ksh);
-  else {
-    const int r = j - S;
-    base += (size_t)(2 + KMAX) * S;
-    coeff_one(a.H, a.oh, a.top + r, a.ksv, base + 2 * r, base + 2 * S + (size_t)r * a.ksv);
-  }
-}
-
-__device__ __forceinline__ int clip8(int v) {
-  v >>= PRECISION_BITS;
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
+  coeff_slot(args.d[i], i, j, S, S, ws);
 }
 
 __global__ __launch_bounds__(256) void resize_kernel(const uint8_t* __restrict__ pixels, ImgArgs args, int n_img, int S,
                                                      const int* __restrict__ ws, int depth_norm, float* __restrict__ out) {
-  __shared__ int s_wh[KMAX * TC];         // [tap][column]: lanes run along the columns
-  __shared__ int s_wv[TR_MAX * KMAX];     // [row][tap]: one row per half wave, broadcast
-  __shared__ int s_bh[TC * 2], s_bv[TR_MAX * 2];
-  __shared__ uint32_t s_hp[ROWS_CAP * TC];  // horizontal pass: [input row][column], channels packed in the bytes
-  __shared__ uint32_t s_in[STAGE_DW];       // raw input rows, from the dword that holds the tile's first byte
-
+  __shared__ ResizeTileLds s;
   const int i = blockIdx.y;
   if (i >= n_img) return;
   const ImgArg a = args.d[i];
-  const int TR = a.tr;
-  const int tiles_c = S / TC;
   const int tile = blockIdx.x;
-  if (tile >= tiles_c * (S / TR)) return;
-  const int c0 = (tile % tiles_c) * TC, r0 = (tile / tiles_c) * TR;
-  const int tid = threadIdx.x;
-  const int C = a.C, ksh = a.ksh, ksv = a.ksv;
-
-  const int* bh = ws + (size_t)i * slot_ints(S);
-  const int* kh = bh + 2 * S;
-  const int* bv = bh + (size_t)(2 + KMAX) * S;
-  const int* kv = bv + 2 * S;
-  if (tid < 2 * TC) s_bh[tid] = bh[2 * c0 + tid];
-  if (tid >= 64 && tid < 64 + 2 * TR) s_bv[tid - 64] = bv[2 * r0 + tid - 64];
-  for (int e = tid; e < TC * ksh; e += 256) {  // kh rows of the 32 columns are contiguous: coalesced
-    const int c = e / ksh, t = e - c * ksh;
-    s_wh[t * TC + c] = kh[(size_t)c0 * ksh + e];
-  }
-  for (int e = tid; e < TR * ksv; e += 256) {
-    const int r = e / ksv, t = e - r * ksv;
-    s_wv[r * KMAX + t] = kv[(size_t)r0 * ksv + e];
-  }
-  __syncthreads();
-
-  // bounds are non-decreasing along an axis: the tile's window is [first of the first, end of the last)
-  const int row0 = s_bv[0];
-  int nrows = s_bv[2 * (TR - 1)] + s_bv[2 * (TR - 1) + 1] - row0;
-  if (nrows > ROWS_CAP) nrows = ROWS_CAP;  // never taken: the host sizes TR from the scale
-  const int x0 = s_bh[0];
-  const int segbytes = (s_bh[2 * (TC - 1)] + s_bh[2 * (TC - 1) + 1] - x0) * C;
-  const int pitch = ((segbytes + 6) >> 2) | 1;  // dwords per staged row: up to 3 bytes of misalignment in front, odd
-  int rch = STAGE_DW / pitch;                   // rows staged at a time (>= 1: the host bounds the segment)
-  if (rch < 1) return;
-
-  const uint8_t* img = pixels + a.offset;
-  const size_t rowbytes = (size_t)a.W * C;
-  for (int rb = 0; rb < nrows; rb += rch) {
-    const int nr = min(rch, nrows - rb);
-    // ---- stage nr input rows: aligned dwords where the dword lies inside the image row, guarded bytes at its two ends
-    for (int e = tid; e < nr * pitch; e += 256) {
-      const int rr = e / pitch, d = e - rr * pitch;
-      const uint8_t* rowp = img + (size_t)(row0 + rb + rr) * a.stride;
-      const uintptr_t first = (uintptr_t)(rowp + (size_t)x0 * C);
-      const uintptr_t p = (first & ~(uintptr_t)3) + 4 * (uintptr_t)d;
-      const uintptr_t lo = (uintptr_t)rowp, hi = lo + rowbytes;
-      uint32_t v = 0;
-      if (p >= lo && p + 4 <= hi) {
-        v = *(const uint32_t*)p;
-      } else {
-        for (int b = 0; b < 4; ++b)
-          if (p + b >= lo && p + b < hi) v |= (uint32_t)(*(const uint8_t*)(p + b)) << (8 * b);
-      }
-      s_in[rr * pitch + d] = v;
-    }
-    __syncthreads();
-    // ---- horizontal pass of those rows for the tile's 32 columns
-    for (int e = tid; e < nr * TC; e += 256) {
-      const int rr = e >> 5, c = e & 31;
-      const uint8_t* rowp = img + (size_t)(row0 + rb + rr) * a.stride;
-      const int sh = (int)((uintptr_t)(rowp + (size_t)x0 * C) & 3);
-      const int xmin = s_bh[2 * c], nx = s_bh[2 * c + 1];
-      const uint8_t* src = (const uint8_t*)(s_in + rr * pitch) + sh + (xmin - x0) * C;
-      uint32_t packed;
-      if (C == 3) {
-        int h0 = 1 << (PRECISION_BITS - 1), h1 = h0, h2 = h0;
-        for (int t = 0; t < nx; ++t) {
-          const int w = s_wh[t * TC + c];
-          h0 += (int)src[3 * t] * w;
-          h1 += (int)src[3 * t + 1] * w;
-          h2 += (int)src[3 * t + 2] * w;
-        }
-        packed = (uint32_t)clip8(h0) | ((uint32_t)clip8(h1) << 8) | ((uint32_t)clip8(h2) << 16);
-      } else {
-        int h0 = 1 << (PRECISION_BITS - 1);
-        for (int t = 0; t < nx; ++t) h0 += (int)src[t] * s_wh[t * TC + c];
-        packed = (uint32_t)clip8(h0);
-      }
-      s_hp[(rb + rr) * TC + c] = packed;
-    }
-    __syncthreads();
-  }
-
-  // ---- vertical pass over the LDS tile, ToTensor / Normalize, 1 -> 3 channel repeat
-  const size_t plane = (size_t)S * S;
-  float* o = out + (size_t)i * 3 * plane;
-  for (int e = tid; e < TR * TC; e += 256) {
-    const int r = e >> 5, c = e & 31;
-    const int ymin = s_bv[2 * r] - row0;
-    int ny = s_bv[2 * r + 1];
-    if (ymin + ny > nrows) ny = nrows - ymin;  // never taken (see nrows)
-    int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-    for (int t = 0; t < ny; ++t) {
-      const uint32_t v = s_hp[(ymin + t) * TC + c];
-      const int w = s_wv[r * KMAX + t];
-      a0 += (int)(v & 255) * w;
-      a1 += (int)((v >> 8) & 255) * w;
-      a2 += (int)((v >> 16) & 255) * w;
-    }
-    const int v8[3] = {clip8(a0), C == 3 ? clip8(a1) : clip8(a0), C == 3 ? clip8(a2) : clip8(a0)};
-    const size_t at = (size_t)(r0 + r) * S + c0 + c;
-    for (int ch = 0; ch < 3; ++ch) {
-      float f = (float)v8[ch] / 255.0f;       // ToTensor
-      if (depth_norm) f = (f - 0.5f) / 0.5f;  // Normalize(mean=0.5, std=0.5)
-      o[ch * plane + at] = f;
-    }
-  }
+  if (tile >= (S / TC) * (S / a.tr)) return;
+  resize_tile(s, pixels, a, i, tile, S, S, ws, depth_norm, out + (size_t)i * 3 * S * S);
 }
 
 // resized size (torchvision Resize(int)): shorter side -> S, other = int(S*long/short); then the centre crop's origin
@@ -246,25 +55,13 @@ void resized_geometry(int H, int W, int S, int& oh, int& ow, int& top, int& left
 }
 
 bool fill_arg(const dptx_image_desc& d, int S, ImgArg& a) {
-  if (d.offset < 0 || (d.C != 1 && d.C != 3) || d.H < 1 || d.W < 1 || d.H > 16384 || d.W > 16384) return false;
-  if ((long long)d.row_stride_bytes < (long long)d.W * d.C) return false;
+  if (!desc_in_range(d)) return false;
   if ((d.H < d.W ? d.H : d.W) > 32 * S) return false;
   a.offset = d.offset;
   a.H = d.H; a.W = d.W; a.C = d.C; a.stride = d.row_stride_bytes;
   resized_geometry(d.H, d.W, S, a.oh, a.ow, a.top, a.left);
   if (a.oh < S || a.ow < S || a.top < 0 || a.left < 0 || a.top + S > a.oh || a.left + S > a.ow) return false;
-  a.ksh = coeff_ksize(d.W, a.ow);
-  a.ksv = coeff_ksize(d.H, a.oh);
-  if (a.ksh > KMAX || a.ksv > KMAX) return false;
-  // a tile's input window: rows [c(first) - s + .5, c(last) + s + .5) with centres (TR - 1) * scale apart, at most 2 more
-  const double sv = (double)d.H / a.oh, fv = sv < 1.0 ? 1.0 : sv;
-  a.tr = (int)std::ceil((TR_MAX - 1) * sv + 2 * fv) + 2 <= ROWS_CAP ? TR_MAX : TR_MAX / 2;
-  if ((int)std::ceil((a.tr - 1) * sv + 2 * fv) + 2 > ROWS_CAP) return false;
-  const double sh = (double)d.W / a.ow, fh = sh < 1.0 ? 1.0 : sh;
-  const long long segbytes = ((long long)std::ceil((TC - 1) * sh + 2 * fh) + 2) * d.C;
-  if ((((segbytes + 6) >> 2) | 1) > STAGE_DW) return false;
-  a.pad = 0;
-  return true;
+  return fill_tile_geometry(d, a);
 }
 
 constexpr int MM_PARTS = 64;  // partial minima / maxima per image
@@ -319,7 +116,7 @@ extern "C" {
 
 int dptx_preprocess_batch_workspace_bytes(int32_t B, int32_t S, int64_t* bytes) {
   if (!bytes || B < 1 || B > 4096 || S < 32 || S > 1024 || S % 32) return DPTX_E_INVALID;
-  *bytes = (int64_t)CHUNK * slot_ints(S) * sizeof(int);
+  *bytes = (int64_t)CHUNK * slot_ints(S, S) * sizeof(int);
   return DPTX_OK;
 }
 

@@ -93,6 +93,10 @@ ABI = [
     ("dptx_postprocess_depth_batch", C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     ("dptx_colorize_workspace_bytes", C.c_int, [_i32, C.c_int64, _i64p]),
     ("dptx_colorize_u8_batch", C.c_int, [_vp, _vp, _i32, C.c_int64, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_preprocess_rect_batch_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i64p]),
+    ("dptx_preprocess_u8_rect_batch", C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_postprocess_resize_workspace_bytes", C.c_int, [_i32, _i32, _i64p]),
+    ("dptx_postprocess_resize_batch", C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
     ("dptx_refocus_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64p]),
     ("dptx_refocus_quantiles", C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
     ("dptx_refocus", C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),

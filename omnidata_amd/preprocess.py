@@ -6,6 +6,8 @@ CenterCrop(384) -> ToTensor [-> Normalize(0.5,0.5) for depth]), :101-102 (512 RG
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -268,3 +270,163 @@ def depths_to_rgba_gpu(maps: torch.Tensor) -> torch.Tensor:
         call("dptx_colorize_u8_batch", m.data_ptr(), lut.data_ptr(), B, N, out.data_ptr(), ws.data_ptr(), ws.numel(),
              torch.cuda.current_stream().cuda_stream)
     return out
+
+
+# ------------------------------------------------------------------ full-frame inference (fullframe.hip)
+MAX_NET_SIDE = 1024          # include/dptx.h dptx_preprocess_u8_rect_batch: OH, OW <= 1024
+MAX_NET_ELEMS = 2 ** 31      # the engine indexes one image's 256-channel maps with 32 bits: net_h * net_w * 256 < 2^31
+RESIZE_MODES = {"normal_u8": 1, "normal_f32": 2, "depth_f32": 3, "depth_rgba": 4}   # include/dptx.h DPTX_RESIZE_*
+RESIZE_RENORM = 16
+
+
+def full_frame_size(w: int, h: int, size: int = 384, multiple: int = 32):
+    """-> (net_w, net_h): the reference's Resize(size, size, keep_aspect_ratio=True, ensure_multiple_of=multiple,
+    resize_method='lower_bound').get_size(w, h) (modules/midas/transforms.py:94-160): one scale, max(size / w, size / h), for
+    both sides; each side rounded (half to even, as np.round) to a multiple, and up where that falls below `size`."""
+    scale = max(size / w, size / h)
+
+    def constrain(x):
+        y = int(round(x / multiple) * multiple)
+        if y < size:
+            y = int(math.ceil(x / multiple) * multiple)
+        return y
+    return constrain(scale * w), constrain(scale * h)
+
+
+def full_frame_net_size(w: int, h: int, size: int = 384, multiple: int = 32):
+    """-> (net_w, net_h, capped): full_frame_size() with the long side cut back to what the kernels and the engine take
+    (a side <= 1024, net_h * net_w * 256 < 2^31); `capped` says whether that changed anything."""
+    nw, nh = full_frame_size(w, h, size, multiple)
+    top = MAX_NET_SIDE // multiple * multiple
+    cw, ch = min(nw, top), min(nh, top)
+    while cw * ch * 256 >= MAX_NET_ELEMS:      # not reached with sides <= 1024; kept with the rule it states
+        if cw >= ch:
+            cw -= multiple
+        else:
+            ch -= multiple
+    return cw, ch, (cw, ch) != (nw, nh)
+
+
+def image_to_input_rect(img: Image.Image, task: str, net_hw) -> torch.Tensor:
+    """-> [1,3,OH,OW] fp32: the whole image resized to the network's size (no crop), in the model's input convention."""
+    OH, OW = net_hw
+    t = to_tensor(img.resize((OW, OH), Image.BILINEAR))
+    if task == "depth":
+        t = (t - 0.5) / 0.5
+    t = t[:3].unsqueeze(0)
+    if t.shape[1] == 1:
+        t = t.repeat_interleave(3, 1)
+    return t
+
+
+def rect_supported(img, net_hw) -> bool:
+    """Whether dptx_preprocess_u8_rect_batch takes this image for the target (OH, OW); the others go through PIL."""
+    OH, OW = net_hw
+    if isinstance(img, Image.Image):
+        if img.mode not in ("RGB", "L"):
+            return False
+        w, h = img.size
+    else:
+        a = np.asarray(img) if not isinstance(img, torch.Tensor) else img
+        if a.dtype not in (np.uint8, torch.uint8) or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)):
+            return False
+        h, w = a.shape[:2]
+    return 1 <= h <= min(MAX_SIDE, MAX_SCALE * OH) and 1 <= w <= min(MAX_SIDE, MAX_SCALE * OW)
+
+
+def images_to_input_rect_gpu(images, task: str, net_hw, device="cuda:0") -> torch.Tensor:
+    """[B,3,OH,OW] fp32 on `device`: image_to_input_rect() of every image (bit-identical), from ONE host->device copy of the raw
+    pixels and one ragged-batch resize on the GPU.  Images the kernel does not take go through PIL into their slot."""
+    from ._native import call, workspace
+    images = list(images)
+    OH, OW = int(net_hw[0]), int(net_hw[1])
+    B = len(images)
+    device = torch.device(device)
+    x = torch.empty(B, 3, OH, OW, dtype=torch.float32, device=device)
+    if B == 0:
+        return x
+    fast = [i for i, im in enumerate(images) if rect_supported(im, (OH, OW))]
+    slow = sorted(set(range(B)) - set(fast))
+    if fast:
+        buf, descs = pack_images([images[i] for i in fast])
+        ws = workspace("dptx_preprocess_rect_batch_workspace_bytes", device, (min(len(fast), 4096), OH, OW),
+                       f"network size {(OH, OW)}: both sides must be multiples of 32 in [64, 1024]")
+        with torch.cuda.device(device):
+            dev = buf.to(device, non_blocking=True)
+            stream = torch.cuda.current_stream().cuda_stream
+            direct = len(fast) == B
+            xf = x if direct else torch.empty(len(fast), 3, OH, OW, dtype=torch.float32, device=device)
+            for b0 in range(0, len(fast), 4096):
+                n = min(4096, len(fast) - b0)
+                call("dptx_preprocess_u8_rect_batch", dev.data_ptr(), _C.addressof(descs) + b0 * _C.sizeof(ImageDesc), n, OH, OW,
+                     int(task == "depth"), xf[b0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
+            if not direct:
+                x[torch.tensor(fast, device=device)] = xf
+    for i in slow:
+        im = images[i] if isinstance(images[i], Image.Image) else Image.fromarray(np.asarray(images[i]))
+        x[i:i + 1] = image_to_input_rect(im, task, (OH, OW)).to(device)
+    return x
+
+
+def output_layout(sizes, mode: str):
+    """-> (descs, total bytes): the packed output buffer dptx_postprocess_resize_batch fills for outputs of `sizes`
+    [(H, W), ...]: tight rows, every output at a 16-byte-aligned offset."""
+    bpp = 3 if mode == "normal_u8" else 4
+    planes = 3 if mode == "normal_f32" else 1
+    descs = (ImageDesc * max(len(sizes), 1))()
+    off = 0
+    for i, (H, W) in enumerate(sizes):
+        descs[i] = ImageDesc(off, int(H), int(W), 3 if mode.startswith("normal") else 1, int(W) * bpp)
+        off = (off + planes * int(H) * int(W) * bpp + 15) // 16 * 16
+    return descs, off
+
+
+def resize_outputs_gpu(y: torch.Tensor, sizes, mode: str, renormalize: bool = False):
+    """y [B,3,h,w] (normal_*) or [B,h,w] / [B,1,h,w] (depth_*) float (cuda), sizes [(H, W)] * B -> list of B device tensors
+    (views of one packed buffer), output i at its own size: normal_u8 [H,W,3] uint8, normal_f32 [3,H,W] fp32, depth_f32 [H,W]
+    fp32, depth_rgba [H,W,4] uint8 (viridis over the map's own range).  One entry-point call per 4096 outputs."""
+    from ._native import call, check_cuda, workspace
+    check_cuda("y", y)
+    if mode not in RESIZE_MODES:
+        raise ValueError(f"mode must be one of {sorted(RESIZE_MODES)}")
+    normal = mode.startswith("normal")
+    if renormalize and not normal:
+        raise ValueError("renormalize applies to surface normals only")
+    h, w = y.shape[-2:]
+    y = y.detach().float().reshape(-1, 3 if normal else 1, h, w).contiguous()
+    sizes = [(int(H), int(W)) for H, W in sizes]
+    B = y.shape[0]
+    if len(sizes) != B:
+        raise ValueError(f"{B} maps but {len(sizes)} sizes")
+    if B == 0:
+        return []
+    if any(not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE) for H, W in sizes):
+        raise ValueError(f"output sides must be in [1, {MAX_SIDE}]")
+    descs, total = output_layout(sizes, mode)
+    code = RESIZE_MODES[mode] | (RESIZE_RENORM if renormalize else 0)
+    out = torch.empty(max(total, 16), dtype=torch.uint8, device=y.device)
+    lut_ptr = ws_ptr = ws_n = 0
+    if mode == "depth_rgba":
+        key = str(y.device)
+        lut = _lut_cache.get(key)
+        if lut is None:
+            lut = _lut_cache[key] = torch.from_numpy(viridis_lut()).to(y.device)
+        ws = workspace("dptx_postprocess_resize_workspace_bytes", y.device, (min(B, 4096), code), "unsupported mode")
+        lut_ptr, ws_ptr, ws_n = lut.data_ptr(), ws.data_ptr(), ws.numel()
+    with torch.cuda.device(y.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for b0 in range(0, B, 4096):
+            n = min(4096, B - b0)
+            call("dptx_postprocess_resize_batch", y[b0:].data_ptr(), n, y.shape[1], h, w,
+                 _C.addressof(descs) + b0 * _C.sizeof(ImageDesc), code, out.data_ptr(), lut_ptr, ws_ptr, ws_n, stream)
+    res = []
+    for d, (H, W) in zip(descs, sizes):
+        if mode == "normal_u8":
+            res.append(out[d.offset:d.offset + H * W * 3].view(H, W, 3))
+        elif mode == "normal_f32":
+            res.append(out[d.offset:d.offset + 12 * H * W].view(torch.float32).view(3, H, W))
+        elif mode == "depth_f32":
+            res.append(out[d.offset:d.offset + 4 * H * W].view(torch.float32).view(H, W))
+        else:
+            res.append(out[d.offset:d.offset + 4 * H * W].view(H, W, 4))
+    return res
