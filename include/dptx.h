@@ -686,8 +686,9 @@ int dptx_debug_arena_checksums(dptx_handle h, void* out_dev, int32_t capacity, v
 /* Debug / tests: switches (per calling host thread) of the 256x256 GEMM kernel's launch form -- 1: staged epilogue instead of the
  * register-direct one, 2: one block per tile instead of the persistent tile loop, 4: the lockstep loop instead of the ping-pong
  * schedule in the two-plane 128x128 kernel -- and of the streaming kernel for the small-K 1x1 convolutions -- 8: never take it,
- * 16: take it for every launch it can serve, not only in the shape classes it was adopted for.  Results do not depend on
- * them. */
+ * 16: take it for every launch it can serve, not only in the shape classes it was adopted for -- and of the forward's
+ * folding of norm3 into a second pass of that kernel -- 32: never (conv3, then the GroupNorm apply pass), 64: wherever the
+ * folded form can run, not only in the shape classes it was adopted for.  Results do not depend on them. */
 int dptx_debug_set_gemm_flags(int32_t flags);
 /* NHWC conv on OCP e4m3 operands (the fp8 dtype's convolution): X8[B,H,W,Cin] and Wt8[Cout][k][k][Cin] are e4m3 bytes
  * (Cin % 128 == 0), fp32 accumulate on the block-scaled fp8 MFMA at unit scale; Y = act(out_scale * conv + bias) (+R) in
@@ -703,6 +704,18 @@ int dptx_op_conv_groupnorm(int32_t dtype, const void* X, const void* Wt, void* Y
                            const void* R, void* Y, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                            int32_t ksize, int32_t stride, int32_t pad_t, int32_t pad_l, int32_t Ho, int32_t Wo,
                            int32_t relu, float eps, void* scratch_f32, void* stream);
+/* The same result for a 1x1 stride-1 convolution with Cin in {64, 128, 256} (bf16 / fp16), computed the way the forward
+ * folds norm3 into its conv3: the streaming kernel runs twice -- a statistics pass that writes the records and nothing else,
+ * a finalize launch that turns them into per-(image, channel) affines, and a second pass that multiplies again and applies
+ * GroupNorm + R + ReLU in its epilogue -- so that the raw map is never stored.  Y = act( gn(conv(X)) + R' ), R' = R, or
+ * gn_r(R) with (r_gamma, r_beta) and the records r_records of R (as dptx_op_conv_groupnorm leaves them in its scratch) --
+ * the first block of a stage, whose shortcut is the downsample branch.  Bit-identical to dptx_op_conv_groupnorm.
+ * records_f32: B * (H*W/32) * 64 floats; tables_f32: B * 4 * Cout floats.  H*W % 32 == 0, Cout % 64 == 0, Y != R.
+ * passes: 1 = statistics pass (Y is not touched), 2 = finalize, 4 = epilogue pass; 7 = all three. */
+int dptx_op_conv_groupnorm_fused(int32_t dtype, const void* X, const void* Wt, const float* gamma, const float* beta,
+                                 const void* R, const float* r_gamma, const float* r_beta, const float* r_records, void* Y,
+                                 int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t relu, float eps,
+                                 void* records_f32, void* tables_f32, int32_t passes, void* stream);
 /* bilinear x2, align_corners=True, NHWC 16-bit. */
 int dptx_op_upsample2x(int32_t dtype, const void* X, void* Y, int32_t B, int32_t H, int32_t W,
                        int32_t C, void* stream);

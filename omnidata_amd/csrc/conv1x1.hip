@@ -22,7 +22,21 @@
 //   that LDS receives packed 16-bit column pairs: half the bytes and half the ds_write_b32 of the fp32 staging.  The
 //   staging is wave-private (16 rows x 64 columns at a time), read back as 16-byte row pieces: no block barrier.
 //
+// Forms (template parameter FORM; kernels.h C1_*).  A stride-1 convolution followed by a GroupNorm runs the kernel twice
+// instead of storing the raw map and reading it back (K is small: the second product costs fewer bytes than the round trip):
+// * C1_STATS: the MFMAs and gn_records() of the plain form -- the same records, bit for bit -- and nothing else: no bias, no
+//   staging, no store; p.C is never touched.
+// * C1_GN: the plain form up to the 16-byte row piece a lane reads back from the staging -- the rounded value the plain form
+//   stores and gn_apply_kernel (norm.hip) loads -- then gn_apply_kernel's arithmetic on it, same order, same roundings:
+//   x a[c] + d[c] (one fma), + the shortcut piece of p.R1 (itself r ra[c] + rd[c] behind a downsample branch), ReLU,
+//   rounding, one 16-byte store.  The affines are the tables of launch_gn_finalize (p.gn_tab[img][4][N]): a 32-row block lies
+//   in one image (rows per image % 32 == 0), so the table row is wave-uniform.  In the forward a wave's next row block lies
+//   in another image (the stride is the whole grid), so nothing is kept across row blocks: the affines of a lane's 8 columns
+//   and its shortcut pieces are fetched per 64-column pass, before the stores of the pass in front of it, so that waiting for
+//   them never waits for a store.
+//
 // LDS: K = 64: 32 + 16 + 9 KB (BN = 256), K = 128: 32 + 32 + 9 KB (BN = 128) -- two blocks per CU; K = 256: 64 + 64 + 9 KB.
+// (C1_GN at K = 64: BN = 128, 16 + 16 + 9 KB -- launch_c1_dt.)
 #include "gemm_impl.h"
 
 namespace dptx {
@@ -36,7 +50,17 @@ constexpr size_t conv1x1_smem_bytes() {
   return (size_t)KT * BN * 128 + (size_t)C1_WAVES * KT * 32 * 128 + (size_t)C1_WAVES * C1_STG_WAVE;
 }
 
-template <int DT, int KT, int BN>
+// 8 packed 16-bit values <-> floats (common.h unpack8 / pack8 on the kernel's vector type)
+template <int DT>
+__device__ __forceinline__ void c1_unpack8(const u32x4_t v, float* f) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = T16<DT>::tof((uint16_t)(v[i] & 0xffffu));
+    f[2 * i + 1] = T16<DT>::tof((uint16_t)(v[i] >> 16));
+  }
+}
+
+template <int DT, int KT, int BN, int FORM>
 __global__ __launch_bounds__(64 * C1_WAVES, KT <= 2 ? 2 : 1) void conv1x1_stream_kernel(const GemmParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int NSUB = BN / 64;            // 64-column passes over the panel
@@ -107,7 +131,7 @@ __global__ __launch_bounds__(64 * C1_WAVES, KT <= 2 ? 2 : 1) void conv1x1_stream
 #pragma unroll
   for (int s = 0; s < NSUB; ++s)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) bias_c[s][j] = p.bias != nullptr ? p.bias[n0 + s * 64 + j * 32 + lr] : 0.f;
+    for (int j = 0; j < 2; ++j) bias_c[s][j] = FORM == C1_PLAIN && p.bias != nullptr ? p.bias[n0 + s * 64 + j * 32 + lr] : 0.f;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();  // the only block barrier: the W panel is in LDS
 
@@ -115,8 +139,37 @@ __global__ __launch_bounds__(64 * C1_WAVES, KT <= 2 ? 2 : 1) void conv1x1_stream
   const unsigned sel = (lr & 1) ? 0x03020706u : 0x05040100u;    // v_perm_b32 selector of the column-pair exchange
   const int cn = lane & 7, rr = lane >> 3;
 
+  // C1_GN: what the epilogue of 64-column pass s reads besides the staging -- the affines of this lane's 8 columns (table
+  // row of the block's image) and its four shortcut pieces.  Fetched one pass ahead, in front of the stores of the pass before
+  const bool has_r = FORM == C1_GN && p.R1 != nullptr;
+  const bool r_gn = has_r && p.gn_tab_rgn != 0;
+
   for (; rb < rb_total; rb += slots) {
     const int m0 = rb * 32;
+    float ga[NSUB][8], gd[NSUB][8], gra[NSUB][8], grd[NSUB][8];
+    u32x4_t rq[NSUB][4];
+    auto load_epi = [&](int s) {
+      const int img = m0 / p.gn_hw;  // wave-uniform: rows per image % 32 == 0
+      const float* tab = p.gn_tab + (long long)img * 4 * p.N + n0 + s * 64 + cn * 8;
+      if (has_r) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int m = m0 + 16 * (i >> 1) + rr + 8 * (i & 1);  // < M: M % 32 == 0 in this form
+          rq[s][i] = *(const u32x4_t*)((const uint16_t*)p.R1 + (long long)(p.c_row_off + m) * p.ldc + (n0 + s * 64 + cn * 8));
+        }
+      }
+      *(float4*)&ga[s][0] = *(const float4*)(tab);
+      *(float4*)&ga[s][4] = *(const float4*)(tab + 4);
+      *(float4*)&gd[s][0] = *(const float4*)(tab + p.N);
+      *(float4*)&gd[s][4] = *(const float4*)(tab + p.N + 4);
+      if (r_gn) {
+        *(float4*)&gra[s][0] = *(const float4*)(tab + 2 * p.N);
+        *(float4*)&gra[s][4] = *(const float4*)(tab + 2 * p.N + 4);
+        *(float4*)&grd[s][0] = *(const float4*)(tab + 3 * p.N);
+        *(float4*)&grd[s][4] = *(const float4*)(tab + 3 * p.N + 4);
+      }
+    };
+    if (FORM == C1_GN) load_epi(0);
     // ---- A fragments of this row block (landed: waited for below, or in the prologue) -> registers
     u32x4_t af[KS];
 #pragma unroll
@@ -153,7 +206,9 @@ __global__ __launch_bounds__(64 * C1_WAVES, KT <= 2 ? 2 : 1) void conv1x1_stream
         __builtin_amdgcn_sched_barrier(0);  // behind the MFMAs, not among them
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      if (p.gn_part != nullptr) gn_records<1, 2>(p, m0, n0 + s * 64, 0, 0, lr, lh, acc);
+      if (FORM == C1_STATS || (FORM == C1_PLAIN && p.gn_part != nullptr)) gn_records<1, 2>(p, m0, n0 + s * 64, 0, 0, lr, lh, acc);
+      if (FORM == C1_STATS) continue;
+      if (FORM == C1_GN && s + 1 < NSUB) load_epi(s + 1);  // ahead of this pass's stores
 
 #pragma unroll
       for (int h = 0; h < 2; ++h) {  // registers 8 h .. 8 h + 7 = tile rows 16 h .. 16 h + 15
@@ -164,7 +219,7 @@ __global__ __launch_bounds__(64 * C1_WAVES, KT <= 2 ? 2 : 1) void conv1x1_stream
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
             float v0 = acc[0][j][8 * h + 2 * t] + bias_c[s][j], v1 = acc[0][j][8 * h + 2 * t + 1] + bias_c[s][j];
-            if (p.act == 1) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
+            if (FORM != C1_GN && p.act == 1) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }  // C1_GN: the ReLU follows the GroupNorm
             // own = (row r, row r + 1) of column lr.  Even lanes keep row r and take the neighbour's: (lr, lr + 1) of row r;
             // odd lanes keep row r + 1: (lr - 1, lr) of row r + 1
             const uint32_t own = T16<DT>::pack2(v0, v1);
@@ -178,9 +233,31 @@ __global__ __launch_bounds__(64 * C1_WAVES, KT <= 2 ? 2 : 1) void conv1x1_stream
 #pragma unroll
         for (int pp = 0; pp < 2; ++pp) {
           const int rl = rr + 8 * pp;
-          const u32x4_t d = *(const u32x4_t*)(stg + rl * C1_STG_PITCH + cn * 16);
+          u32x4_t d = *(const u32x4_t*)(stg + rl * C1_STG_PITCH + cn * 16);
           const int m = m0 + 16 * h + rl;
-          if (m < p.M) *(u32x4_t*)((uint16_t*)p.C + (long long)(p.c_row_off + m) * p.ldc + (n0 + s * 64 + cn * 8)) = d;
+          if (FORM == C1_GN) {  // gn_apply_kernel on the value it would have loaded: one fma each, a rounded add, ReLU
+            float f[8];
+            c1_unpack8<DT>(d, f);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] = __builtin_fmaf(f[e], ga[s][e], gd[s][e]);
+            if (has_r) {
+              float r[8];
+              c1_unpack8<DT>(rq[s][2 * h + pp], r);
+              if (r_gn) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) r[e] = __builtin_fmaf(r[e], gra[s][e], grd[s][e]);
+              }
+#pragma unroll
+              for (int e = 0; e < 8; ++e) f[e] = __fadd_rn(f[e], r[e]);
+            }
+            if (p.act == 1) {
+#pragma unroll
+              for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d[e] = T16<DT>::pack2(f[2 * e], f[2 * e + 1]);
+          }
+          if (FORM == C1_GN || m < p.M) *(u32x4_t*)((uint16_t*)p.C + (long long)(p.c_row_off + m) * p.ldc + (n0 + s * 64 + cn * 8)) = d;
         }
       }
     }
@@ -216,7 +293,25 @@ bool conv1x1_stream_adopted(const GemmParams& p) {
   return false;
 }
 
-template <int DT, int KT, int BN>
+// the folded GroupNorm (C1_STATS + C1_GN); p: the plain convolution in front of the GroupNorm
+bool conv1x1_gn_eligible(int mode, const GemmParams& p) {
+  if (!conv1x1_stream_eligible(mode, p) || p.stride != 1 || p.bias != nullptr || p.act != 0) return false;
+  const int cpg = p.N / 32;
+  if (p.a_rpi % 32 != 0 || p.M % p.a_rpi != 0 || p.N > 1024 || (cpg & (cpg - 1)) != 0) return false;  // whole records; gn_records
+  return p.c_row_off == 0 && p.ldc == p.N;  // the shortcut and the tables are addressed like a dense [M][N] map
+}
+
+// The (K, N) classes in which statistics pass + finalize + GroupNorm-epilogue pass measured faster than conv + apply pass by
+// more than the spread of five alternating repetitions at B = 32 and B = 16 (profiles/conv1x1_gn_epilogue.md): conv3 of
+// stages 0 and 1.  Left on conv + apply pass: K = 256, N = 1024 (stage 2: 1.5 us slower at B = 32, a tie at B = 16 -- eight
+// W panels of 64 KB per 18 row blocks of an image, fetched twice).
+bool conv1x1_gn_adopted(const GemmParams& p) {
+  if (p.K == 64) return p.N == 256;
+  if (p.K == 128) return p.N == 512;
+  return false;
+}
+
+template <int DT, int KT, int BN, int FORM>
 static hipError_t launch_c1(const GemmParams& p, hipStream_t stream) {
   constexpr size_t smem = conv1x1_smem_bytes<KT, BN>();
   static_assert(smem <= 160 * 1024 && (KT > 2 || 2 * smem <= 160 * 1024), "two blocks per CU at K <= 128");
@@ -227,26 +322,51 @@ static hipError_t launch_c1(const GemmParams& p, hipStream_t stream) {
   if (cap < 8) cap = 8;
   int groups = want < cap ? want : cap;
   groups = (groups + 7) / 8 * 8;
-  auto k = conv1x1_stream_kernel<DT, KT, BN>;
+  auto k = conv1x1_stream_kernel<DT, KT, BN, FORM>;
   set_smem_attr(k, smem);
   hipLaunchKernelGGL(k, dim3(groups * npan), dim3(64 * C1_WAVES), smem, stream, p);
   return hipGetLastError();
 }
 
-template <int DT>
+template <int DT, int FORM>
 static hipError_t launch_c1_dt(const GemmParams& p, hipStream_t stream) {
   if (p.K == 64) {
-    if (p.N % 256 == 0) return launch_c1<DT, 1, 256>(p, stream);
-    if (p.N % 128 == 0) return launch_c1<DT, 1, 128>(p, stream);
-    return launch_c1<DT, 1, 64>(p, stream);
+    // (the GroupNorm epilogue holds two passes' affines and shortcut pieces next to the accumulators: four passes of them do
+    // not fit the 256 registers of two blocks per CU, so that form takes the 128-column panel)
+    if constexpr (FORM != C1_GN)
+      if (p.N % 256 == 0) return launch_c1<DT, 1, 256, FORM>(p, stream);
+    if (p.N % 128 == 0) return launch_c1<DT, 1, 128, FORM>(p, stream);
+    return launch_c1<DT, 1, 64, FORM>(p, stream);
   }
-  if (p.K == 128) return p.N % 128 == 0 ? launch_c1<DT, 2, 128>(p, stream) : launch_c1<DT, 2, 64>(p, stream);
-  return p.N % 128 == 0 ? launch_c1<DT, 4, 128>(p, stream) : launch_c1<DT, 4, 64>(p, stream);
+  if (p.K == 128) return p.N % 128 == 0 ? launch_c1<DT, 2, 128, FORM>(p, stream) : launch_c1<DT, 2, 64, FORM>(p, stream);
+  return p.N % 128 == 0 ? launch_c1<DT, 4, 128, FORM>(p, stream) : launch_c1<DT, 4, 64, FORM>(p, stream);
 }
 
-hipError_t launch_conv1x1_stream(int mode, const GemmParams& p, hipStream_t stream) {
-  if (!conv1x1_stream_eligible(mode, p)) return hipErrorInvalidValue;
-  return mode == MODE_BF16 ? launch_c1_dt<DT_BF16>(p, stream) : launch_c1_dt<DT_FP16>(p, stream);
+template <int FORM>
+static hipError_t launch_c1_form(int mode, const GemmParams& p, hipStream_t stream) {
+  return mode == MODE_BF16 ? launch_c1_dt<DT_BF16, FORM>(p, stream) : launch_c1_dt<DT_FP16, FORM>(p, stream);
+}
+
+hipError_t launch_conv1x1_stream(int mode, const GemmParams& p0, hipStream_t stream, int form) {
+  if (form == C1_PLAIN) {
+    if (!conv1x1_stream_eligible(mode, p0) || p0.gn_tab != nullptr) return hipErrorInvalidValue;
+    return launch_c1_form<C1_PLAIN>(mode, p0, stream);
+  }
+  // the two GroupNorm forms are launched directly: what launch_gemm fills in, and the checks on the plain convolution
+  GemmParams p = p0;
+  p.trace = nullptr;
+  p.a_rpi_rcp = 1.0f / (float)(p.a_rpi > 0 ? p.a_rpi : 1);
+  p.wout_rcp = 1.0f / (float)(p.Wout > 0 ? p.Wout : 1);
+  GemmParams q = p;
+  q.R1 = nullptr; q.act = 0; q.gn_tab = nullptr; q.gn_tab_rgn = 0; q.r1_fp32 = 0;
+  if (p.M <= 0 || p.ldw < p.K || p.ldw % 8 != 0 || !conv1x1_gn_eligible(mode, q) || p.r1_fp32) return hipErrorInvalidValue;
+  p.gn_hw = p.a_rpi; p.gn_blocks = p.a_rpi / 32; p.gn_cpg = p.N / 32;
+  if (form == C1_STATS) {
+    if (p.gn_part == nullptr || p.R1 != nullptr || p.act != 0 || p.gn_tab != nullptr) return hipErrorInvalidValue;
+    return launch_c1_form<C1_STATS>(mode, p, stream);
+  }
+  if (form != C1_GN || p.gn_tab == nullptr || p.gn_part != nullptr || p.C == nullptr || p.C == p.R1) return hipErrorInvalidValue;
+  return launch_c1_form<C1_GN>(mode, p, stream);
 }
 
 }  // namespace dptx

@@ -463,7 +463,7 @@ struct dptx_engine {
   // arena slices
   int max_h = 384, max_w = 384;   // largest supported input (cfg.max_height/max_width; 0 = 384)
   Buf pos_alt;
-  Buf sraw, stem, S[3], T1, T2, PA, PB, DS, part[4], X, Hn, QKV, AO, F1, R3, R4, L3, T4, L4, clsb, lrn[4], tA, tB,
+  Buf sraw, stem, S[3], T1, T2, PA, PB, DS, part[4], gntab, X, Hn, QKV, AO, F1, R3, R4, L3, T4, L4, clsb, lrn[4], tA, tB,
       tC, P[4], H0, H0U, H1, lnst;
   // every buffer of the plan with its name, in plan order (recorded by plan_arena_for: what it takes is what
   // dptx_debug_arena_layout lists and dptx_debug_arena_checksums sums)
@@ -538,6 +538,7 @@ size_t plan_arena_for(dptx_engine* e, size_t B, bool half) {
   take("DS", e->DS, B * p4 * 256, 2);
   // GroupNorm partial records (32 groups x float2): p2/256 chunks for the stem, p4/32 MFMA row blocks for a stage conv
   for (int i = 0; i < 4; ++i) take(idx("part", i), e->part[i], B * (std::max(p2 / 256, p4 / 32) + 64) * 64, 4);
+  take("gntab", e->gntab, B * 4 * 1024, 4);  // norm3 folded into conv3: the affines (a, d, ra, rd) per image and channel (<= 1024)
   take("X", e->X, B * S * DV, 4);
   take("lnst", e->lnst, B * S * 8 * 2, 4);  // LayerNorm fold: (sum, sum of squares) per token row and 128-column block (<= 8 blocks)
   take("Hn", e->Hn, B * S * DV, 2);
@@ -912,6 +913,37 @@ struct Run {
     chk(launch_gn_apply(dt, g, e->pl, st), nkey.c_str(), 2);
   }
 
+  // conv3 + norm3 of a bottleneck without the raw map (conv1x1.hip C1_STATS / C1_GN): the streaming kernel runs a statistics
+  // pass that stores nothing but the records, gn_finalize turns them (and, in a stage's first block, those of the downsample
+  // branch) into affine tables, and a second pass of the kernel applies GroupNorm + shortcut + ReLU in its epilogue -- the
+  // bits of conv() followed by gn_apply().  Returns false, having launched nothing, where the form cannot run or was not
+  // adopted for the (K, N) class (debug flags 32 / 64): the caller then takes that schedule.
+  bool conv_gn_folded(const void* in, int H, int W, int Cin, const std::string& wkey, int Cout, void* out, const std::string& nkey,
+                      float* part, int relu, const void* R, const std::string& rkey = "", const float* rpart = nullptr) {
+    const int flags = gemm_debug_flags();
+    if ((flags & (8 | 32)) || !gn_fusable(H * W) || out == R || (e->fp8_use(wkey) && !e->calibrating)) return false;
+    GemmParams p;
+    gemm_params_conv(p, B, H, W, Cin, Cout, 1, 1, 0, 0, H, W, 2);
+    p.A = in; p.W = e->w(wkey); p.C = out; p.planes = e->pl;
+    if (!conv1x1_gn_eligible(dt, p) || !((flags & 64) || conv1x1_gn_adopted(p))) return false;
+    float* tab = (float*)A(e->gntab);
+    const double macs = (double)p.M / B * p.N * p.K;
+    GemmParams q = p;
+    q.gn_part = part;
+    exec_macs += macs; cat_macs[0] += macs;
+    chk(launch_conv1x1_stream(dt, q, st, C1_STATS), (wkey + ".stats").c_str(), 0);
+    const bool r_gn = !rkey.empty();
+    chk(launch_gn_finalize(part, e->f(nkey + ".weight"), e->f(nkey + ".bias"), r_gn ? rpart : nullptr,
+                           r_gn ? e->f(rkey + ".weight") : nullptr, r_gn ? e->f(rkey + ".bias") : nullptr, tab, B, H * W, Cout,
+                           H * W / 32, 1e-5f, st),
+        (nkey + ".finalize").c_str(), 2);
+    q = p;
+    q.R1 = R; q.act = relu; q.gn_tab = tab; q.gn_tab_rgn = r_gn;
+    exec_macs += macs; cat_macs[0] += macs;
+    chk(launch_conv1x1_stream(dt, q, st, C1_GN), wkey.c_str(), 0);
+    return true;
+  }
+
   // RCU (blocks.py:263-286): out = conv2(relu(conv1(relu(x)))) + x (+ o.R2)
   // Of `o` the unit reads R2 (the extra summand), q (fp8 dtype: e4m3 copy of the unit's output -- 2 when its consumer
   // pre-activates (another RCU), 1 otherwise) and out_lo (MIXED per-layer policy: does a consumer of the unit's output need
@@ -992,12 +1024,18 @@ int Run::forward(const void* x, void* y, void* y2) {
       conv(A(E->T1), H, Wd, mid, p + "conv2.weight", 3, stride, pad, pad, Ho, Wo, mid, A(E->T2), GemmOpt().gn_part(f_out ? part1 : nullptr));
       if (!f_out) gn_stats(A(E->T2), part1, Ho * Wo, mid);
       gn_apply(A(E->T2), p + "norm2", part1, Ho * Wo, mid, 1);
-      conv(A(E->T2), Ho, Wo, mid, p + "conv3.weight", 1, 1, 0, 0, Ho, Wo, cout, out, GemmOpt().gn_part(f_out ? part2 : nullptr));
-      if (!f_out) gn_stats(out, part2, Ho * Wo, cout);
-      if (b == 0)
-        gn_apply(out, p + "norm3", part2, Ho * Wo, cout, 1, A(E->DS), p + "downsample.norm", part3);
-      else
-        gn_apply(out, p + "norm3", part2, Ho * Wo, cout, 1, cur);
+      // conv3 + norm3 (+ shortcut + ReLU): folded into two passes of the streaming kernel where that was adopted
+      const bool folded = b == 0 ? conv_gn_folded(A(E->T2), Ho, Wo, mid, p + "conv3.weight", cout, out, p + "norm3", part2, 1, A(E->DS),
+                                                  p + "downsample.norm", part3)
+                                 : conv_gn_folded(A(E->T2), Ho, Wo, mid, p + "conv3.weight", cout, out, p + "norm3", part2, 1, cur);
+      if (!folded) {
+        conv(A(E->T2), Ho, Wo, mid, p + "conv3.weight", 1, 1, 0, 0, Ho, Wo, cout, out, GemmOpt().gn_part(f_out ? part2 : nullptr));
+        if (!f_out) gn_stats(out, part2, Ho * Wo, cout);
+        if (b == 0)
+          gn_apply(out, p + "norm3", part2, Ho * Wo, cout, 1, A(E->DS), p + "downsample.norm", part3);
+        else
+          gn_apply(out, p + "norm3", part2, Ho * Wo, cout, 1, cur);
+      }
       cur = out;
       H = Ho;
       Wd = Wo;

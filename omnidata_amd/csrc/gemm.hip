@@ -33,6 +33,7 @@ static thread_local long long* g_trace = nullptr;
 void gemm_set_trace(long long* dev_buf) { g_trace = dev_buf; }
 static thread_local int g_debug_flags = 0;
 void gemm_set_debug_flags(int flags) { g_debug_flags = flags; }
+int gemm_debug_flags() { return g_debug_flags; }
 static thread_local float g_cu_share = 1.0f;
 void gemm_set_cu_share(float share) { g_cu_share = share > 0.f && share <= 1.f ? share : 1.0f; }
 

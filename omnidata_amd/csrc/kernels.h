@@ -83,8 +83,14 @@ struct GemmParams {
   float ln_eps, ln_inv_dim;
   long long* trace;  // debug: s_memtime stamps of block 0 (dptx_debug_set_trace); null in production
   int debug_flags;   // debug (dptx_debug_set_gemm_flags): 1 = staged epilogue everywhere, 2 = one block per tile, 4 = lockstep two-plane 128x128 kernel,
-                     // 8 = never take the streaming 1x1 kernel, 16 = take it wherever it can run (not only in the adopted classes)
+                     // 8 = never take the streaming 1x1 kernel, 16 = take it wherever it can run (not only in the adopted classes),
+                     // 32 / 64 = never / wherever eligible: the GroupNorm-epilogue schedule of the streaming kernel (read by the callers)
   float a_rpi_rcp, wout_rcp;  // 1 / a_rpi, 1 / Wout (filled in by launch_gemm: row -> (image, y, x) without integer division)
+  // conv1x1.hip, GroupNorm-epilogue form (launch_conv1x1_stream form C1_GN): the per-(image, channel) affines of
+  // launch_gn_finalize, gn_tab[img][4][N] = (a, d, ra, rd); the epilogue stores act( x a + d + (R1 ? (gn_tab_rgn ? r ra + rd : r) : 0) )
+  // with x the rounded 16-bit convolution output and r the 16-bit R1 (same addressing as C), act = ReLU when p.act == 1
+  const float* gn_tab;
+  int gn_tab_rgn;
 };
 
 // Fills the "plain dense row-major" defaults for A [M,K] (lda = K) and C [M,N].
@@ -99,9 +105,11 @@ hipError_t launch_gemm(int dtype, const GemmParams& p, hipStream_t stream);
 // ([wave][64 k-tiles][4] int64; null switches it off)
 void gemm_set_trace(long long* dev_buf);
 // debug / tests: 1 = no register-direct epilogue, 2 = no persistent launch, 4 = no two-plane ping-pong kernel, 8 = never take
-// the streaming 1x1 kernel, 16 = take it for every launch it can serve, also outside the classes it was adopted for (same
-// results either way)
+// the streaming 1x1 kernel, 16 = take it for every launch it can serve, also outside the classes it was adopted for, 32 = never
+// fold a GroupNorm into a second pass of the streaming kernel (conv1x1_gn_*: the schedule conv -> gn_apply), 64 = fold it
+// wherever that form can run, adopted or not (same results either way)
 void gemm_set_debug_flags(int flags);
+int gemm_debug_flags();
 // conv1x1.hip: the streaming kernel for dense / strided 1x1 convolutions with K = Cin in {64, 128, 256}, N % 64 == 0, one 16-bit
 // plane, optional per-column bias, ReLU and GroupNorm records (bf16 / fp16 modes): conv1x1_stream_eligible().  launch_gemm
 // sends there what is eligible AND belongs to a (K, N, stride) class in which the kernel measured faster
@@ -109,7 +117,17 @@ void gemm_set_debug_flags(int flags);
 // of the tiled kernels.
 bool conv1x1_stream_eligible(int mode, const GemmParams& p);
 bool conv1x1_stream_adopted(const GemmParams& p);
-hipError_t launch_conv1x1_stream(int mode, const GemmParams& p, hipStream_t stream);
+// Two more forms of the same kernel fold the GroupNorm behind a stride-1 convolution into a SECOND pass over it (K is small:
+// multiplying twice moves fewer bytes than storing the raw map and reading it back): C1_STATS runs the MFMAs and writes the
+// records p.gn_part and nothing else (p.C is not touched); launch_gn_finalize turns the records into affines; C1_GN multiplies
+// again and applies GroupNorm + shortcut (p.R1) + ReLU (p.act) to the rounded 16-bit value in the epilogue (p.gn_tab) -- the
+// bits of conv -> launch_gn_apply.  conv1x1_gn_eligible() takes the parameters of the plain convolution (no R1, act 0) and
+// needs rows per image % 32 == 0; conv1x1_gn_adopted() lists the (K, N) classes in which the folded schedule measured faster
+// (debug flag 64 drops that condition, 32 switches the form off).  Direct launches: they do not pass through launch_gemm.
+enum { C1_PLAIN = 0, C1_STATS = 1, C1_GN = 2 };
+bool conv1x1_gn_eligible(int mode, const GemmParams& p);
+bool conv1x1_gn_adopted(const GemmParams& p);
+hipError_t launch_conv1x1_stream(int mode, const GemmParams& p, hipStream_t stream, int form = C1_PLAIN);
 // tile selection: the following launches share the chip with (1 / share - 1) concurrent streams of the same forward
 void gemm_set_cu_share(float share);
 
@@ -131,6 +149,12 @@ struct GnParams {
   int nrec;  // partial records per image in `partial` / `r_partial`: 0 = gn_chunks(HW, C) (written by launch_gn_stats),
              // HW / 32 when a GEMM epilogue wrote them (GemmParams::gn_part)
 };
+// the affines launch_gn_apply computes in its prologue, as tables for the GroupNorm epilogue of the streaming 1x1 kernel
+// (GemmParams::gn_tab): tab[b][0..1][C] = (a, d) of (partial, gamma, beta), tab[b][2..3][C] those of the r_ triple (skipped
+// when r_partial is null); nrec records per image.  One launch, one block per (image, triple).
+hipError_t launch_gn_finalize(const float* partial, const float* gamma, const float* beta, const float* r_partial,
+                              const float* r_gamma, const float* r_beta, float* tab, int B, int HW, int C, int nrec, float eps,
+                              hipStream_t stream);
 int gn_chunks(int HW, int C);  // blocks per image of the GroupNorm stats/apply grids = partial records per image
 hipError_t launch_gn_stats(int mode, const void* X, float* partial, int B, int HW, int C, Planes pl, hipStream_t stream);
 hipError_t launch_gn_apply(int mode, const GnParams& p, Planes pl, hipStream_t stream);

@@ -146,6 +146,10 @@ hipError_t launch_gn_stats(int mode, const void* X, float* partial, int B, int H
 // The chunk partials are summed in double by 8 slices of 32 threads (slice s takes chunks s, s+8, ...: the loads of
 // one slice are independent, so the latency is nchunks/8 dependent adds instead of nchunks dependent loads) and the
 // slices are combined in a fixed order: the result depends on HW and C only, never on the batch or the run.
+// sa / sd: LDS (the apply kernels) or global memory (gn_finalize_kernel: the tables of the streaming 1x1 kernel's GroupNorm
+// epilogue, conv1x1.hip).  The roundings are spelled out -- a = rstd * gamma rounded, d = fma(-a, mean, beta), and
+// y = fma(x, a, d) at the users -- so that every site, in whichever kernel, applies the same ones (they are what
+// -ffp-contract=fast made of `beta - mean * a` and `x * a + d` here before).
 __device__ __forceinline__ void gn_affine_to_lds(const float* __restrict__ partial, int nchunks, int b,
                                                  const float* __restrict__ gamma, const float* __restrict__ beta, int C,
                                                  int HW, float eps, float* sa, float* sd, float* smr) {
@@ -179,9 +183,9 @@ __device__ __forceinline__ void gn_affine_to_lds(const float* __restrict__ parti
   __syncthreads();
   for (int c = tid; c < C; c += blockDim.x) {
     const int g = c / cpg;
-    const float a = smr[2 * g + 1] * gamma[c];
+    const float a = __fmul_rn(smr[2 * g + 1], gamma[c]);
     sa[c] = a;
-    sd[c] = beta[c] - smr[2 * g] * a;
+    sd[c] = __builtin_fmaf(-a, smr[2 * g], beta[c]);
   }
   __syncthreads();
 }
@@ -207,16 +211,16 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const GnParams p, int pix
     float f[8];
     load8f<DT, PL>(X + off, plane, f);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = f[e] * sa[v * 8 + e] + sd[v * 8 + e];
+    for (int e = 0; e < 8; ++e) f[e] = __builtin_fmaf(f[e], sa[v * 8 + e], sd[v * 8 + e]);
     if (R != nullptr) {
       float r[8];
       load8f<DT, PL>(R + off, plane, r);
       if (r_gn) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) r[e] = r[e] * ra[v * 8 + e] + rd[v * 8 + e];
+        for (int e = 0; e < 8; ++e) r[e] = __builtin_fmaf(r[e], ra[v * 8 + e], rd[v * 8 + e]);
       }
 #pragma unroll
-      for (int e = 0; e < 8; ++e) f[e] += r[e];
+      for (int e = 0; e < 8; ++e) f[e] = __fadd_rn(f[e], r[e]);
     }
     if (p.relu) {
 #pragma unroll
@@ -242,6 +246,30 @@ hipError_t launch_gn_apply(int mode, const GnParams& p, Planes pl, hipStream_t s
   const int pix = (p.HW + nb - 1) / nb;
   dim3 grid((p.HW + pix - 1) / pix, p.B);
   DPTX_DISPATCH_MODE(mode, hipLaunchKernelGGL((gn_apply_kernel<DT, PL>), grid, dim3(256), 0, stream, p, pix, nrec, pl.act));
+  return hipGetLastError();
+}
+
+// The affines of gn_apply_kernel's prologue as tables in global memory, tab[b][4][C] = (a, d, ra, rd): block (b, t) reduces
+// the records of image b of triple t (0: partial / gamma / beta, 1: the r_ triple) with gn_affine_to_lds -- the same code,
+// so the same bits -- for the GroupNorm epilogue of the streaming 1x1 kernel.
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ partial, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, const float* __restrict__ r_partial,
+                                                          const float* __restrict__ r_gamma, const float* __restrict__ r_beta,
+                                                          float* __restrict__ tab, int nrec, int C, int HW, float eps) {
+  __shared__ float smr[64];
+  const int b = blockIdx.x, t = blockIdx.y;
+  float* const ta = tab + ((long long)b * 4 + 2 * t) * C;
+  gn_affine_to_lds(t ? r_partial : partial, nrec, b, t ? r_gamma : gamma, t ? r_beta : beta, C, HW, eps, ta, ta + C, smr);
+}
+
+hipError_t launch_gn_finalize(const float* partial, const float* gamma, const float* beta, const float* r_partial,
+                              const float* r_gamma, const float* r_beta, float* tab, int B, int HW, int C, int nrec, float eps,
+                              hipStream_t stream) {
+  if (C % 64 != 0 || C > 1024 || B <= 0 || nrec <= 0 || partial == nullptr || gamma == nullptr || beta == nullptr || tab == nullptr)
+    return hipErrorInvalidValue;
+  if (r_partial != nullptr && (r_gamma == nullptr || r_beta == nullptr)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(B, r_partial != nullptr ? 2 : 1), dim3(256), 0, stream, partial, gamma, beta,
+                     r_partial, r_gamma, r_beta, tab, nrec, C, HW, eps);
   return hipGetLastError();
 }
 

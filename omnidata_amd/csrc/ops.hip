@@ -160,6 +160,39 @@ int dptx_op_conv_groupnorm(int32_t dtype, const void* X, const void* Wt, void* Y
   return rc(launch_gn_apply(dtype, g, g_op_planes, (hipStream_t)stream));
 }
 
+// conv1x1 (stride 1) + GroupNorm as the forward's folded schedule runs it (kernels.h C1_STATS / C1_GN): statistics pass,
+// launch_gn_finalize, GroupNorm-epilogue pass.  passes: 1 = statistics pass (records; Y is the launch's C and is not touched),
+// 2 = finalize (records, and r_records when R has a GroupNorm of its own -> tables), 4 = epilogue pass (-> Y); 7 = the whole op
+int dptx_op_conv_groupnorm_fused(int32_t dtype, const void* X, const void* Wt, const float* gamma, const float* beta, const void* R,
+                                 const float* r_gamma, const float* r_beta, const float* r_records, void* Y, int32_t B, int32_t H,
+                                 int32_t W, int32_t Cin, int32_t Cout, int32_t relu, float eps, void* records_f32, void* tables_f32,
+                                 int32_t passes, void* stream) {
+  if (records_f32 == nullptr || tables_f32 == nullptr || (passes & ~7) != 0 || passes == 0 || H <= 0 || W <= 0) return DPTX_E_INVALID;
+  if ((r_gamma != nullptr) != (r_beta != nullptr) || (r_gamma != nullptr) != (r_records != nullptr)) return DPTX_E_INVALID;
+  if (r_gamma != nullptr && R == nullptr) return DPTX_E_INVALID;
+  GemmParams p;
+  gemm_params_conv(p, B, H, W, Cin, Cout, 1, 1, 0, 0, H, W, 2);
+  p.A = X; p.W = Wt; p.C = Y; p.planes = g_op_planes;
+  if (!conv1x1_gn_eligible(dtype, p)) return DPTX_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  if (passes & 1) {
+    GemmParams q = p;
+    q.gn_part = (float*)records_f32;
+    if (launch_conv1x1_stream(dtype, q, st, C1_STATS) != hipSuccess) return DPTX_E_HIP;
+  }
+  if (passes & 2) {
+    if (launch_gn_finalize((const float*)records_f32, gamma, beta, r_records, r_gamma, r_beta, (float*)tables_f32, B, H * W, Cout,
+                           H * W / 32, eps, st) != hipSuccess)
+      return DPTX_E_HIP;
+  }
+  if (passes & 4) {
+    GemmParams q = p;
+    q.R1 = R; q.act = relu ? 1 : 0; q.gn_tab = (const float*)tables_f32; q.gn_tab_rgn = r_gamma != nullptr;
+    if (launch_conv1x1_stream(dtype, q, st, C1_GN) != hipSuccess) return DPTX_E_HIP;
+  }
+  return DPTX_OK;
+}
+
 int dptx_op_upsample2x(int32_t dtype, const void* X, void* Y, int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
   return rc(launch_upsample2x(dtype, X, Y, B, H, W, C, g_op_planes, (hipStream_t)stream));
 }

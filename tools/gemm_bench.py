@@ -1,6 +1,7 @@
 """Per-shape micro-benchmark of the implicit-GEMM kernel on the DPT-Hybrid layer shapes (B=32).
 Usage (GPU box): python tools/gemm_bench.py [--dtype bf16]
-                 python tools/gemm_bench.py --ab-flags 0,8 --gn --reps 5 --only s0.c3,s1.c3   (A/B of two launch forms)"""
+                 python tools/gemm_bench.py --ab-flags 0,8 --gn --reps 5 --only s0.c3,s1.c3   (A/B of two launch forms)
+                 python tools/gemm_bench.py --ab-gn-fold --reps 5 --iters 20 [--batch 16]      (conv3 + norm3: unfused vs folded)"""
 import argparse
 import os
 import sys
@@ -87,6 +88,51 @@ def ab_conv(lib, dt, tdt, st, args, only):
         del X, Wt, Y, Y2
 
 
+def ab_gn_fold(lib, dt, tdt, st, args, only):
+    """conv3 + norm3 of the three stage classes, with shortcut and ReLU as the later blocks of a stage run them: conv + apply pass
+    (dptx_op_conv_groupnorm on the forward's dispatch) against statistics pass + finalize + GroupNorm-epilogue pass
+    (dptx_op_conv_groupnorm_fused), alternating, --reps repetitions of --iters calls per side; then the statistics pass and the
+    finalize launch alone.  Prints every repetition, the medians, each side's spread (max - min) and the verdict of the adoption
+    rule: the folded side is faster by more than the larger spread."""
+    print(f"# conv3 + norm3 unfused vs folded, {args.reps} x {args.iters} calls, B = {B}, {args.dtype}; us per call")
+    for name, H, Cin, Cout, k, s, pad, Ho in CONV:
+        if name not in ("s0.c3", "s1.c3", "s2.c3") or (only and name not in only):
+            continue
+        X = torch.randn(B, H, H, Cin, device="cuda").to(tdt)
+        Wt = (torch.randn(Cout, 1, 1, Cin, device="cuda") * Cin ** -0.5).to(tdt)
+        R = torch.randn(B, H, H, Cout, device="cuda").to(tdt)
+        Yraw, Y = torch.empty_like(R), torch.empty_like(R)
+        beta, g = torch.randn(Cout, device="cuda"), torch.randn(Cout, device="cuda")
+        rec = torch.zeros(B * (H * H // 32 + 1) * 64, device="cuda")
+        tab = torch.zeros(B * 4 * Cout, device="cuda")
+
+        def fused(passes):
+            return lambda: lib.dptx_op_conv_groupnorm_fused(dt, X.data_ptr(), Wt.data_ptr(), g.data_ptr(), beta.data_ptr(), R.data_ptr(), None,
+                                                            None, None, Y.data_ptr(), B, H, H, Cin, Cout, 1, 1e-5, rec.data_ptr(),
+                                                            tab.data_ptr(), passes, st)
+        sides = {"unfused": lambda: lib.dptx_op_conv_groupnorm(dt, X.data_ptr(), Wt.data_ptr(), Yraw.data_ptr(), g.data_ptr(), beta.data_ptr(),
+                                                               R.data_ptr(), Y.data_ptr(), B, H, H, Cin, Cout, 1, 1, 0, 0, H, H, 1, 1e-5,
+                                                               rec.data_ptr(), st),
+                 "folded": fused(7)}
+        assert sides["unfused"]() == 0 and sides["folded"]() == 0
+        t = {n: [] for n in sides}
+        for _ in range(args.reps):
+            for n, fn in sides.items():
+                t[n].append(timeit(fn) * 1e3)
+        med = {n: sorted(v)[len(v) // 2] for n, v in t.items()}
+        spr = {n: max(v) - min(v) for n, v in t.items()}
+        gain = med["unfused"] - med["folded"]
+        print(f"{name:6s} K={Cin:4d} N={Cout:4d}  unfused " + " ".join(f"{v:6.1f}" for v in t["unfused"]) + "  | folded " +
+              " ".join(f"{v:6.1f}" for v in t["folded"]) + f"  | median {med['unfused']:6.1f} vs {med['folded']:6.1f}  gain {gain:+6.1f}"
+              f"  spread {spr['unfused']:4.1f} / {spr['folded']:4.1f}  -> {'faster' if gain > max(spr.values()) else 'not faster'}")
+        parts = {"stats": fused(1), "finalize": fused(2), "epilogue": fused(4)}
+        tp = {n: sorted(timeit(fn) * 1e3 for _ in range(args.reps)) for n, fn in parts.items()}
+        a_mb = B * H * H * Cin * 2 / 1e6
+        print(f"{'':6s} alone: " + "  ".join(f"{n} {v[len(v) // 2]:6.1f} ({v[0]:.1f} .. {v[-1]:.1f})" for n, v in tp.items()) +
+              f"   [statistics pass reads A = {a_mb:.1f} MB: {a_mb / tp['stats'][len(tp['stats']) // 2]:.2f} TB/s]")
+        del X, Wt, R, Yraw, Y
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
@@ -95,6 +141,8 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="images (conv shapes only): 16 = what one of the two streams launches")
     ap.add_argument("--ab-flags", default=None, help="two dptx_debug_set_gemm_flags values, e.g. 0,8: alternating A/B on the conv shapes")
     ap.add_argument("--reps", type=int, default=5, help="repetitions per side of --ab-flags")
+    ap.add_argument("--ab-gn-fold", action="store_true",
+                    help="conv3 + norm3 of the three stage classes: conv + apply pass vs statistics + finalize + GroupNorm-epilogue pass")
     ap.add_argument("--gn", action="store_true", help="--ab-flags: GroupNorm records on (conv + apply pass) where the forward has them")
     args = ap.parse_args()
     global B
@@ -105,6 +153,8 @@ def main():
     fp8 = args.dtype == "fp8"
     dt, tdt = DTYPES[args.dtype], (torch.bfloat16 if args.dtype in ("bf16", "fp8") else torch.float16)
     st = torch.cuda.current_stream().cuda_stream
+    if args.ab_gn_fold:
+        return ab_gn_fold(lib, dt, tdt, st, args, only)
     if args.ab_flags:
         return ab_conv(lib, dt, tdt, st, args, only)
     tot_ms, tot_flop = 0.0, 0.0
