@@ -11,7 +11,9 @@ fp16 unless --dtype bf16; --task depth needs --weights), --batch_size N (N > 1: 
 same files, same pixels), --full_frame {squash,aspect} [--renormalize] (the whole image instead of the centre crop, <stem>_<task>.png at
 the image's own size and <stem>_rgb.png = the image unchanged; any --batch_size; squash = a fixed 384x384 network input as
 paper_code/oasis_eval_tta.py:324-339, aspect = the aspect-preserving size of modules/midas/transforms.py:94-160; --renormalize
-makes the resized normals unit length again, oasis_eval_tta.py:339).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
+makes the resized normals unit length again, oasis_eval_tta.py:339), --tta NAME [--tta_merger median|mean] (--task normal: test-time
+augmentation, omnidata_amd/tta.py: the views of preset flip / whole / crops / oasis -- oasis_eval_tta.py:487-534, 40 views -- merged per pixel;
+files as with --full_frame).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
 """
 import argparse
 import glob
@@ -42,6 +44,9 @@ def main(argv=None):
                         help="keep the whole image (no centre crop) and write the map at the image's own size: squash = a fixed "
                              "square network input, aspect = the reference's aspect-preserving network size per image")
     parser.add_argument("--renormalize", action="store_true", help="--full_frame, normal: unit-length normals after the resize")
+    parser.add_argument("--tta", default=None, choices=["flip", "whole", "crops", "oasis"],
+                        help="--task normal: test-time augmentation with this view preset (omnidata_amd/tta.py), merged per pixel")
+    parser.add_argument("--tta_merger", default="median", choices=["median", "mean"], help="--tta: how the views are merged")
     args = parser.parse_args(argv)
 
     if args.task not in ("normal", "depth"):
@@ -67,6 +72,9 @@ def main(argv=None):
     if args.renormalize and (args.full_frame is None or args.task != "normal"):
         print("--renormalize needs --full_frame and --task normal")
         sys.exit()
+    if args.tta is not None and (args.task != "normal" or args.full_frame is not None):
+        print("--tta needs --task normal and excludes --full_frame")
+        sys.exit()
     if unet and args.full_frame == "aspect":
         print("--backbone unet takes --full_frame squash only: its network sizes are multiples of 64 up to 512, which the "
               "aspect-preserving size rule does not produce")
@@ -90,15 +98,18 @@ def main(argv=None):
         model = build_model(args.task, weights=weights, random_weights=args.random_weights, dtype=args.dtype,
                             max_batch=max(args.batch_size, 1), backbone=args.backbone)
     model.to(device)
-    if args.batch_size > 1 or args.full_frame is not None:
+    if args.batch_size > 1 or args.full_frame is not None or args.tta is not None:
         from omnidata_amd.batch_infer import BatchPredictor
         p = Path(args.img_path)
         if not (p.is_file() or p.is_dir()):
             print("invalid file path!")
             sys.exit()
         files = [args.img_path] if p.is_file() else glob.glob(args.img_path + "/*")
+        # the version-1 UNet takes sides that are multiples of 64 up to 512 (the model oasis_eval_tta.py evaluates)
+        tta_options = dict(multiple=64, max_side=512) if unet and args.tta is not None else None
         BatchPredictor(model, args.task, batch_size=max(args.batch_size, 1), full_frame=args.full_frame,
-                       renormalize=args.renormalize).predict_to_dir(files, args.output_path, verbose=True)
+                       renormalize=args.renormalize, tta=args.tta, tta_merger=args.tta_merger,
+                       tta_options=tta_options).predict_to_dir(files, args.output_path, verbose=True)
         return
 
     def save_outputs(img_path, output_file_name):

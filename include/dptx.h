@@ -359,6 +359,16 @@ int dptx_colorize_u8_batch(const void* maps_dev, const void* lut_dev, int32_t B,
 int dptx_preprocess_rect_batch_workspace_bytes(int32_t B, int32_t OH, int32_t OW, int64_t* bytes);
 int dptx_preprocess_u8_rect_batch(const void* pixels_dev, const dptx_image_desc* descs, int32_t B, int32_t OH, int32_t OW,
                                   int32_t depth_normalize, void* x_dev, void* workspace, int64_t workspace_bytes, void* stream);
+/* dptx_preprocess_u8_views_batch: dptx_preprocess_u8_rect_batch with a mirror per image -- the views of test-time augmentation.
+ * A descriptor may be a WINDOW of an uploaded image: offset points at the window's first pixel, H / W are the window's and
+ * row_stride_bytes is the parent's, so an image is uploaded once however many views it has; no byte outside a window's own
+ * pixels is read.  flips: HOST array of B bytes (read before the call returns), NULL = no view is mirrored.  Per view exactly
+ * ToTensor(ImageOps.mirror(img.crop(box).resize((OW, OH), BILINEAR))), bit-identical to Pillow: the mirror follows the resize
+ * (the value of output column x is stored at column OW - 1 - x).  Ranges, workspace (dptx_preprocess_rect_batch_workspace_bytes)
+ * and conventions are those of dptx_preprocess_u8_rect_batch; with flips = NULL so are the bits. */
+int dptx_preprocess_u8_views_batch(const void* pixels_dev, const dptx_image_desc* descs, const uint8_t* flips, int32_t B, int32_t OH,
+                                   int32_t OW, int32_t depth_normalize, void* x_dev, void* workspace, int64_t workspace_bytes,
+                                   void* stream);
 /* dptx_postprocess_resize_batch: y [B][C][h][w] fp32 -> B outputs of DIFFERENT sizes in one packed buffer.  descs[i] gives
  * output i: offset (bytes from out_dev), H, W and row_stride_bytes (rows may be padded; the field C is ignored); no byte outside
  * [row start, row start + W * bytes per pixel) of a row is written.  Source coordinates are ATen's (align_corners=False):
@@ -384,6 +394,43 @@ int dptx_postprocess_resize_workspace_bytes(int32_t B, int32_t mode, int64_t* by
 int dptx_postprocess_resize_batch(const void* y_dev, int32_t B, int32_t C, int32_t h, int32_t w, const dptx_image_desc* descs,
                                   int32_t mode, void* out_dev, const void* lut_dev, void* workspace, int64_t workspace_bytes,
                                   void* stream);
+
+/* ---- Test-time augmentation for surface normals: the merge of an image's views (no handle; DEVICE pointers unless stated) ----
+ * The protocol of paper_code/oasis_eval_tta.py:440-448,487-534 (SurfaceNormalsTTAWrapper, MedianMerger): every view -- a window
+ * of the image, possibly mirrored, at its own network size -- is mapped back into its window, and the views that cover a pixel
+ * are merged per channel.  Same conventions as the blocks above: stream-ordered, no workspace, no allocation, no host
+ * synchronisation (graph-capturable), DPTX_E_INVALID before anything is launched; `views` and `outs` are HOST arrays read before
+ * the call returns; no atomics, a fixed order, bitwise reproducible; an image's result does not depend on the batch.
+ *
+ * View v is the network's map m [3][h][w] fp32 (values in [0, 1], contiguous) at views_dev + offset.  outs[i] describes output i
+ * as in dptx_postprocess_resize_batch (offset from out_dev, H, W, row_stride_bytes; C ignored; no byte outside a row's own
+ * pixels is written).  Output pixel (Y, X) of image i:
+ *   1. the views of image i, in order, whose window [y0, y0 + ch) x [x0, x0 + cw) contains the pixel;
+ *   2. n = 2m - 1 at the view's own resolution, then n / max(||n||_2, 1e-12) there unless DPTX_TTA_RAW_VIEWS
+ *      (oasis_eval_tta.py:441-445; the OASIS z-sign change of line 442 is not reproduced);
+ *   3. the value of F.interpolate(n, (ch, cw), mode='bilinear', align_corners=False) at (Y - y0, X - x0) -- with `flip` at
+ *      (Y - y0, cw - 1 - (X - x0)) and the x component (channel 0) negated; coordinates as dptx_postprocess_resize_batch;
+ *   4. per channel np.median over those values: the middle one or (a + b) * 0.5 of the two middle ones (NOT torch's lower
+ *      median); with DPTX_TTA_MEAN the fp32 sum in view order divided by the count;
+ *   5. F.normalize (eps 1e-12), (n + 1) / 2, then clamp and quantisation of DPTX_RESIZE_NORMAL_U8 / DPTX_RESIZE_NORMAL_F32;
+ *   6. a pixel no view covers: the zero vector, encoded 0.5, 0.5, 0.5.
+ * Inputs are assumed finite; non-finite ones neither fault nor hang (the affected pixels are unspecified).
+ * mode = DPTX_RESIZE_NORMAL_U8 or DPTX_RESIZE_NORMAL_F32, | DPTX_TTA_MEAN, | DPTX_TTA_RAW_VIEWS; nothing else.
+ * Range: 1 <= B <= 4096; every image has 1..64 views, consecutive in `views`, images ascending from 0 to B - 1 (so
+ * B <= n_views <= 64 * B); 1 <= h, w <= 4096; offset >= 0 and a multiple of 4, as views_dev; the window inside the image;
+ * outs as for dptx_postprocess_resize_batch.  One launch per image. */
+typedef struct dptx_tta_view {
+  int64_t offset;         /* bytes from views_dev to this view's [3][h][w] fp32 planes, contiguous, multiple of 4 */
+  int32_t h, w;           /* the network's map for this view, 1..4096 */
+  int32_t image;          /* output image it belongs to; views of one image are consecutive, images ascending */
+  int32_t y0, x0, ch, cw; /* its window in the output image, inside [0,H) x [0,W) */
+  int32_t flip;           /* the network saw the mirrored window */
+} dptx_tta_view;
+#define DPTX_TTA_MEAN 32
+#define DPTX_TTA_RAW_VIEWS 64
+#define DPTX_TTA_MAX_VIEWS 64
+int dptx_tta_merge_normals(const void* views_dev, const dptx_tta_view* views, int32_t n_views, const dptx_image_desc* outs,
+                           int32_t B, int32_t mode, void* out_dev, void* stream);
 
 /* ---- 3D refocus augmentation (omnidata_tools/torch/data/refocus_augmentation.py; no handle; DEVICE pointers) ----
  * All three are stream-ordered on `stream` and use only the caller's workspace: no allocation, no host synchronisation, no

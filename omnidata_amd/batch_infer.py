@@ -9,6 +9,10 @@ dptx_preprocess_u8_rect_batch -> model(x) at a rectangular network size -> dptx_
 reference's fixed-input protocol (paper_code/oasis_eval_tta.py:324-339: image_size x image_size whatever the aspect);
 "aspect" takes the network size per image from the reference's Resize.get_size (modules/midas/transforms.py:94-160), buckets
 the images by network shape and runs the largest shape first, so the model plans its arena once.
+
+tta=<preset> (surface normals only) runs the test-time augmentation of paper_code/oasis_eval_tta.py:440-534 instead
+(omnidata_amd/tta.py: every image through the preset's views, merged per pixel): maps of the image's own size, files as in the
+full-frame modes.
 """
 from __future__ import annotations
 
@@ -70,7 +74,7 @@ def plan_full_frame(sizes, mode: str, image_size: int = 384, batch_size: int = 3
 
 class BatchPredictor:
     def __init__(self, model, task: str, batch_size: int = 32, workers: int = 8, image_size: int = 384, full_frame=None,
-                 renormalize: bool = False):
+                 renormalize: bool = False, tta=None, tta_merger: str = "median", tta_options=None):
         if task not in ("normal", "depth"):
             raise ValueError("task should be one of the following: normal, depth")
         if batch_size < 1:
@@ -79,6 +83,8 @@ class BatchPredictor:
             raise ValueError('full_frame must be None, "squash" or "aspect"')
         if renormalize and (full_frame is None or task != "normal"):
             raise ValueError("renormalize applies to full-frame surface normals only")
+        if tta is not None and (task != "normal" or full_frame is not None):
+            raise ValueError("tta applies to surface normals only and excludes full_frame")
         self.full_frame, self.renormalize = full_frame, bool(renormalize)
         self.capped = []   # full_frame="aspect": input indices of the last run whose network size was cut back to the supported range
         self.model, self.task, self.batch_size, self.image_size = model, task, int(batch_size), int(image_size)
@@ -86,6 +92,10 @@ class BatchPredictor:
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
             raise RuntimeError("BatchPredictor needs the model on an AMD GPU: the forward is implemented as HIP kernels only")
+        self.tta = None
+        if tta is not None:   # tta_options: NormalsTTA's multiple / max_side / chunk_images / normalize_views
+            from .tta import NormalsTTA
+            self.tta = NormalsTTA(model, tta, tta_merger, batch_size=self.batch_size, **(tta_options or {}))
 
     # ---- GPU side of one batch: decoded images -> final pixels, still on the device
     def _run(self, images) -> torch.Tensor:
@@ -149,10 +159,24 @@ class BatchPredictor:
             yield idxs, images, self._run_full(images, net_hw)
             futures = following
 
+    def _tta_chunks(self, items, pool):
+        """_full_chunks for tta: chunks of NormalsTTA.chunk_images inputs in input order (one upload and one merge each)."""
+        n = self.tta.chunk_images
+        chunks = [list(range(i, min(i + n, len(items)))) for i in range(0, len(items), n)]
+        futures = [pool.submit(_decode, items[i]) for i in chunks[0]] if chunks else []
+        for k, idxs in enumerate(chunks):
+            following = [pool.submit(_decode, items[i]) for i in chunks[k + 1]] if k + 1 < len(chunks) else []
+            images = [f.result() for f in futures]
+            yield idxs, images, self.tta(images)
+            futures = following
+
+    def _chunks(self, items, pool):
+        return self._tta_chunks(items, pool) if self.tta is not None else self._full_chunks(items, pool)
+
     def _predict_full(self, items):
         ready, nxt = {}, 0   # outputs that wait for an earlier input of another bucket stay on the device
         with ThreadPoolExecutor(self.workers) as pool:
-            for idxs, _, outs in self._full_chunks(items, pool):
+            for idxs, _, outs in self._chunks(items, pool):
                 ready.update(zip(idxs, outs))
                 while nxt in ready:
                     yield ready.pop(nxt)
@@ -177,7 +201,7 @@ class BatchPredictor:
                 nxt += 1
 
         with ThreadPoolExecutor(self.workers) as pool:
-            for idxs, images, outs in self._full_chunks(paths, pool):
+            for idxs, images, outs in self._chunks(paths, pool):
                 flat = torch.cat([o.reshape(-1) for o in outs])
                 host = torch.empty(flat.shape, dtype=flat.dtype, pin_memory=True)
                 host.copy_(flat, non_blocking=True)
@@ -193,9 +217,9 @@ class BatchPredictor:
 
     def predict(self, images_or_paths):
         """Yields one device tensor per input, in input order (normal: [S,S,3] uint8, depth: [512,512,4] uint8 RGBA; with
-        full_frame the image's own size: [H,W,3] uint8, depth [H,W,4] uint8 RGBA).  Nothing is read back."""
+        full_frame or tta the image's own size: [H,W,3] uint8, depth [H,W,4] uint8 RGBA).  Nothing is read back."""
         items = list(images_or_paths)
-        if self.full_frame is not None:
+        if self.full_frame is not None or self.tta is not None:
             yield from self._predict_full(items)
             return
         with ThreadPoolExecutor(self.workers) as pool:
@@ -210,7 +234,7 @@ class BatchPredictor:
         file, in input order.  An unreadable file raises what Image.open raises, after every earlier file has been written."""
         paths = [os.fspath(p) for p in paths]
         os.makedirs(output_path, exist_ok=True)
-        if self.full_frame is not None:   # <stem>_<task>.png at the image's own size, <stem>_rgb.png = the image unchanged
+        if self.full_frame is not None or self.tta is not None:   # <stem>_<task>.png at the image's own size, <stem>_rgb.png = the image unchanged
             return self._predict_full_to_dir(paths, output_path, verbose)
         writes = deque()   # (future, path, save_path) in input order
 

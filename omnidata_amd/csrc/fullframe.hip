@@ -6,6 +6,8 @@
 //        coefficient arithmetic and the tile of prepost_batch.hip (resample_batch.h) with an independent scale per axis and no
 //        crop.  The grid is the sum of the images' tile counts (16- or 8-row tiles): a block finds its image from the first-tile
 //        prefix that travels with the descriptors.
+//  views: the same with a mirror per image, for test-time augmentation (dptx_preprocess_u8_views_batch): a descriptor may be a
+//        window of an uploaded image (the parent's row stride), and the store of a mirrored view goes to column OW - 1 - x.
 //  post: ATen's upsample_bilinear2d / upsample_bicubic2d (align_corners=False) from y [B][C][h][w] to every image's H x W.
 //        Block = 128 output columns x 8 rows of ONE image, lanes along the columns; the 4 / 16 taps come from cache (one image's
 //        source is <= 1.8 MB and is read by all of its tiles).  fp32 and RGBA outputs are one dword per lane, coalesced.  uint8
@@ -39,6 +41,18 @@ __global__ __launch_bounds__(256) void resize_rect_kernel(const uint8_t* __restr
   resize_tile(s, pixels, a, i, blk - a.pad, OH, OW, ws, depth_norm, out + (size_t)i * 3 * OH * OW);
 }
 
+// the views of test-time augmentation: the same tile with the mirrored store
+__global__ __launch_bounds__(256) void resize_views_kernel(const uint8_t* __restrict__ pixels, ImgArgs args, int n_img, int OH, int OW,
+                                                           const int* __restrict__ ws, int depth_norm, float* __restrict__ out) {
+  __shared__ ResizeTileLds s;
+  const int blk = blockIdx.x;
+  int i = 0;
+  for (int k = 1; k < CHUNK; ++k)
+    if (k < n_img && blk >= args.d[k].pad) i = k;
+  const ImgArg a = args.d[i];
+  resize_tile<true>(s, pixels, a, i, blk - a.pad, OH, OW, ws, depth_norm, out + (size_t)i * 3 * OH * OW);
+}
+
 bool fill_rect_arg(const dptx_image_desc& d, int OH, int OW, ImgArg& a) {
   if (!desc_in_range(d)) return false;
   if (d.H > 32 * OH || d.W > 32 * OW) return false;
@@ -51,7 +65,7 @@ bool fill_rect_arg(const dptx_image_desc& d, int OH, int OW, ImgArg& a) {
 // ------------------------------------------------------------------------------------------------ post
 constexpr int PW = 128, PH = 8;        // output tile: columns x rows
 static_assert(256 % PW == 0 && PH % (256 / PW) == 0, "a thread keeps one column of the tile");
-constexpr int ROW_DW = 3 * PW / 4 + 4; // dwords of one uint8 RGB tile row in LDS (384 bytes + 3 of misalignment, padded)
+constexpr int ROW_DW = row_dw(PW);     // dwords of one uint8 RGB tile row in LDS (384 bytes + 3 of misalignment, padded)
 constexpr int MM_PARTS = 64;           // partial minima / maxima per image
 constexpr int M_NORMAL_U8 = DPTX_RESIZE_NORMAL_U8, M_NORMAL_F32 = DPTX_RESIZE_NORMAL_F32, M_DEPTH_F32 = DPTX_RESIZE_DEPTH_F32,
               M_DEPTH_RGBA = DPTX_RESIZE_DEPTH_RGBA;
@@ -67,29 +81,7 @@ struct OutArgs {
 
 __host__ __device__ inline int tiles_of(int H, int W) { return ((W + PW - 1) / PW) * ((H + PH - 1) / PH); }
 
-// ATen area_pixel_compute_scale / area_pixel_compute_source_index (align_corners=False) + guard_index_and_lambda
-__device__ __forceinline__ float src_coord(float scale, int dst) { return scale * ((float)dst + 0.5f) - 0.5f; }
-__device__ __forceinline__ void guard(float real, int in, int& idx, float& lam) {
-  idx = min((int)floorf(real), in - 1);
-  lam = fminf(fmaxf(real - (float)idx, 0.f), 1.f);
-}
-struct Lin {
-  int i0, i1;
-  float l0, l1;
-};
-__device__ __forceinline__ Lin lin_axis(int in, int out, float scale, int dst) {
-  Lin a;
-  if (in == out) {  // ATen copies
-    a.i0 = a.i1 = dst; a.l0 = 1.f; a.l1 = 0.f;
-    return a;
-  }
-  float real = src_coord(scale, dst);
-  if (real < 0.f) real = 0.f;
-  guard(real, in, a.i0, a.l1);
-  a.i1 = a.i0 + (a.i0 < in - 1 ? 1 : 0);
-  a.l0 = 1.f - a.l1;
-  return a;
-}
+// source coordinates: src_coord / guard / lin_axis of resample_batch.h
 __device__ __forceinline__ float bilinear(const float* __restrict__ p, int w, const Lin& y, const Lin& x) {
   const float* r0 = p + y.i0 * w;  // h * w <= 2^24
   const float* r1 = p + y.i1 * w;
@@ -202,8 +194,7 @@ __global__ __launch_bounds__(256) void post_resize_kernel(const float* __restric
         for (int ch = 0; ch < 3; ++ch)
           *(float*)(o + ((size_t)ch * H + oy) * a.stride + (size_t)ox * 4) = v[ch];
       } else {
-        const int sh = (int)((uintptr_t)(o + (size_t)oy * a.stride + (size_t)c0 * 3) & 3);
-        uint8_t* row = (uint8_t*)(s_row + r * ROW_DW) + sh + 3 * c;
+        uint8_t* row = u8_row_slot<PW>(s_row, o, a.stride, oy, c0, r, c);
         for (int ch = 0; ch < 3; ++ch) row[ch] = (uint8_t)(v[ch] * 255.0f);  // ToPILImage: mul(255).byte() truncates
       }
     } else {
@@ -221,21 +212,7 @@ __global__ __launch_bounds__(256) void post_resize_kernel(const float* __restric
 
   if (MODE == M_NORMAL_U8) {
     __syncthreads();
-    const int nbytes = 3 * min(PW, W - c0);
-    for (int e = tid; e < PH * ROW_DW; e += 256) {
-      const int r = e / ROW_DW, d = e - r * ROW_DW;
-      if (r0 + r >= H) break;
-      const uintptr_t p0 = (uintptr_t)(o + (size_t)(r0 + r) * a.stride + (size_t)c0 * 3), p1 = p0 + nbytes;
-      const uintptr_t q = (p0 & ~(uintptr_t)3) + 4 * (uintptr_t)d;
-      if (q >= p1) continue;
-      const uint32_t v = s_row[r * ROW_DW + d];
-      if (q >= p0 && q + 4 <= p1) {
-        *(uint32_t*)q = v;
-      } else {
-        for (int b = 0; b < 4; ++b)
-          if (q + b >= p0 && q + b < p1) *(uint8_t*)(q + b) = (uint8_t)(v >> (8 * b));
-      }
-    }
+    flush_u8_rows<PW, PH>(s_row, o, a.stride, r0, c0, H, W);
   }
 }
 
@@ -302,8 +279,13 @@ int dptx_preprocess_rect_batch_workspace_bytes(int32_t B, int32_t OH, int32_t OW
   return DPTX_OK;
 }
 
-int dptx_preprocess_u8_rect_batch(const void* pixels_dev, const dptx_image_desc* descs, int32_t B, int32_t OH, int32_t OW,
-                                  int32_t depth_normalize, void* x_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+// both rectangular entries; flips = nullptr and MIRROR = false: the plain one
+template <bool MIRROR>
+int rect_batch(const void* pixels_dev, const dptx_image_desc* descs, const uint8_t* flips, int32_t B, int32_t OH, int32_t OW,
+               int32_t depth_normalize, void* x_dev, void* workspace, int64_t workspace_bytes, void* stream) {
   int64_t need = 0;
   if (!pixels_dev || !descs || !x_dev || !workspace || dptx_preprocess_rect_batch_workspace_bytes(B, OH, OW, &need) != DPTX_OK ||
       workspace_bytes < need || ((uintptr_t)workspace & 3) || ((uintptr_t)x_dev & 3))
@@ -318,15 +300,31 @@ int dptx_preprocess_u8_rect_batch(const void* pixels_dev, const dptx_image_desc*
     for (int i = 0; i < n; ++i) {
       fill_rect_arg(descs[b0 + i], OH, OW, args.d[i]);
       args.d[i].pad = tiles;
+      args.d[i].flip = MIRROR && flips && flips[b0 + i] ? 1 : 0;
       tiles += (OW / TC) * (OH / args.d[i].tr);
     }
     // the chunks share the workspace: they are ordered on the stream
     hipLaunchKernelGGL(coeff_rect_kernel, dim3((OH + OW + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, args, n, OH, OW,
                        (int*)workspace);
-    hipLaunchKernelGGL(resize_rect_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)pixels_dev, args, n, OH, OW,
-                       (const int*)workspace, depth_normalize, (float*)x_dev + (size_t)b0 * 3 * OH * OW);
+    hipLaunchKernelGGL(MIRROR ? resize_views_kernel : resize_rect_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream,
+                       (const uint8_t*)pixels_dev, args, n, OH, OW, (const int*)workspace, depth_normalize,
+                       (float*)x_dev + (size_t)b0 * 3 * OH * OW);
   }
   return hipGetLastError() == hipSuccess ? DPTX_OK : DPTX_E_HIP;
+}
+}  // namespace
+
+extern "C" {
+
+int dptx_preprocess_u8_rect_batch(const void* pixels_dev, const dptx_image_desc* descs, int32_t B, int32_t OH, int32_t OW,
+                                  int32_t depth_normalize, void* x_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+  return rect_batch<false>(pixels_dev, descs, nullptr, B, OH, OW, depth_normalize, x_dev, workspace, workspace_bytes, stream);
+}
+
+int dptx_preprocess_u8_views_batch(const void* pixels_dev, const dptx_image_desc* descs, const uint8_t* flips, int32_t B, int32_t OH,
+                                   int32_t OW, int32_t depth_normalize, void* x_dev, void* workspace, int64_t workspace_bytes,
+                                   void* stream) {
+  return rect_batch<true>(pixels_dev, descs, flips, B, OH, OW, depth_normalize, x_dev, workspace, workspace_bytes, stream);
 }
 
 int dptx_postprocess_resize_workspace_bytes(int32_t B, int32_t mode, int64_t* bytes) {

@@ -1,6 +1,8 @@
 // resample_batch.h -- device code shared by the ragged-batch resamplers (prepost_batch.hip: shorter side -> S, centre crop;
-// fullframe.hip: the whole image -> OH x OW): Pillow's coefficient arithmetic and the tile that forms the horizontal pass of the
-// input rows it needs once, in LDS, then runs the vertical pass with lanes along the output columns.
+// fullframe.hip: the whole image -> OH x OW, and the mirrored views of test-time augmentation): Pillow's coefficient arithmetic
+// and the tile that forms the horizontal pass of the input rows it needs once, in LDS, then runs the vertical pass with lanes
+// along the output columns.  Behind them, what the writers of ragged outputs share (fullframe.hip, tta.hip): ATen's bilinear
+// source coordinates and the tile rows of 3-byte pixels that leave LDS as aligned dwords.
 // Contraction must be off where this is compiled: a fused a*b+c would change `center`, `xmin` and the rounded fixed-point weights.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,7 +17,7 @@
 namespace {
 
 constexpr int PRECISION_BITS = 32 - 8 - 2;  // Pillow: 22
-constexpr int CHUNK = 32;                   // images per launch (descriptors by value: 32 * 56 B of kernel arguments)
+constexpr int CHUNK = 32;                   // images per launch (descriptors by value: 32 * 64 B of kernel arguments)
 constexpr int KMAX = 67;                    // taps per output at the scale limit: ceil(support < 33) * 2 + 1
 constexpr int TC = 32;                      // output columns of a tile
 constexpr int TR_MAX = 16;                  // output rows of a tile (16 or 8)
@@ -27,6 +29,7 @@ struct ImgArg {
   int H, W, C, stride;
   int oh, ow, top, left;  // resized size and the origin of the output window in it
   int ksh, ksv, tr, pad;  // pad: unused by the square entry; the rectangular one keeps the image's first tile of the launch here
+  int flip, pad2;         // the views entry: the output is mirrored (column x is stored at OW - 1 - x); 0 elsewhere
 };
 struct ImgArgs {
   ImgArg d[CHUNK];
@@ -106,6 +109,8 @@ struct ResizeTileLds {
 };
 
 // Output tile `tile` (TC columns x a.tr rows, row-major over the OH x OW window) of image slot i -> o [3][OH][OW] fp32.
+// MIRROR: the entry honours a.flip.
+template <bool MIRROR = false>
 __device__ __forceinline__ void resize_tile(ResizeTileLds& s, const uint8_t* __restrict__ pixels, const ImgArg& a, int i, int tile,
                                             int OH, int OW, const int* __restrict__ ws, int depth_norm, float* __restrict__ o) {
   const int TR = a.tr;
@@ -204,7 +209,8 @@ __device__ __forceinline__ void resize_tile(ResizeTileLds& s, const uint8_t* __r
       a2 += (int)((v >> 16) & 255) * w;
     }
     const int v8[3] = {clip8(a0), C == 3 ? clip8(a1) : clip8(a0), C == 3 ? clip8(a2) : clip8(a0)};
-    const size_t at = (size_t)(r0 + r) * OW + c0 + c;
+    const int oc = MIRROR && a.flip ? OW - 1 - (c0 + c) : c0 + c;
+    const size_t at = (size_t)(r0 + r) * OW + oc;
     for (int ch = 0; ch < 3; ++ch) {
       float f = (float)v8[ch] / 255.0f;       // ToTensor
       if (depth_norm) f = (f - 0.5f) / 0.5f;  // Normalize(mean=0.5, std=0.5)
@@ -226,12 +232,68 @@ inline bool fill_tile_geometry(const dptx_image_desc& d, ImgArg& a) {
   const long long segbytes = ((long long)std::ceil((TC - 1) * sh + 2 * fh) + 2) * d.C;
   if ((((segbytes + 6) >> 2) | 1) > STAGE_DW) return false;
   a.pad = 0;
+  a.flip = a.pad2 = 0;
   return true;
 }
 
 inline bool desc_in_range(const dptx_image_desc& d) {
   if (d.offset < 0 || (d.C != 1 && d.C != 3) || d.H < 1 || d.W < 1 || d.H > 16384 || d.W > 16384) return false;
   return (long long)d.row_stride_bytes >= (long long)d.W * d.C;
+}
+
+// ------------------------------------------------------------------------------------------------ ragged outputs
+// ATen area_pixel_compute_scale / area_pixel_compute_source_index (align_corners=False) + guard_index_and_lambda
+__device__ __forceinline__ float src_coord(float scale, int dst) { return scale * ((float)dst + 0.5f) - 0.5f; }
+__device__ __forceinline__ void guard(float real, int in, int& idx, float& lam) {
+  idx = min((int)floorf(real), in - 1);
+  lam = fminf(fmaxf(real - (float)idx, 0.f), 1.f);
+}
+struct Lin {
+  int i0, i1;
+  float l0, l1;
+};
+__device__ __forceinline__ Lin lin_axis(int in, int out, float scale, int dst) {
+  Lin a;
+  if (in == out) {  // ATen copies
+    a.i0 = a.i1 = dst; a.l0 = 1.f; a.l1 = 0.f;
+    return a;
+  }
+  float real = src_coord(scale, dst);
+  if (real < 0.f) real = 0.f;
+  guard(real, in, a.i0, a.l1);
+  a.i1 = a.i0 + (a.i0 < in - 1 ? 1 : 0);
+  a.l0 = 1.f - a.l1;
+  return a;
+}
+
+// A tile of RH rows x RW columns of 3-byte pixels at (r0, c0) of an [H][W][3] uint8 output whose rows start at any byte:
+// s_row holds row r at dword r * row_dw(RW), its bytes at the misalignment of the row's first byte in memory (u8_row_slot).
+// The rows go out as aligned dwords, with byte stores for the (at most 3 + 3) bytes at the two ends of a tile row: no byte
+// outside [row start, row start + 3 * W) is written.  All 256 threads of the block call it, after a __syncthreads().
+__host__ __device__ constexpr int row_dw(int RW) { return 3 * RW / 4 + 4; }  // 3 * RW bytes + 3 of misalignment, padded
+template <int RW>
+__device__ __forceinline__ uint8_t* u8_row_slot(uint32_t* s_row, const uint8_t* o, int stride, int oy, int c0, int r, int c) {
+  const int sh = (int)((uintptr_t)(o + (size_t)oy * stride + (size_t)c0 * 3) & 3);
+  return (uint8_t*)(s_row + r * row_dw(RW)) + sh + 3 * c;
+}
+template <int RW, int RH>
+__device__ __forceinline__ void flush_u8_rows(const uint32_t* s_row, uint8_t* o, int stride, int r0, int c0, int H, int W) {
+  constexpr int ROW_DW = row_dw(RW);
+  const int nbytes = 3 * min(RW, W - c0);
+  for (int e = threadIdx.x; e < RH * ROW_DW; e += 256) {  // blocks of 256 threads
+    const int r = e / ROW_DW, d = e - r * ROW_DW;
+    if (r0 + r >= H) break;
+    const uintptr_t p0 = (uintptr_t)(o + (size_t)(r0 + r) * stride + (size_t)c0 * 3), p1 = p0 + nbytes;
+    const uintptr_t q = (p0 & ~(uintptr_t)3) + 4 * (uintptr_t)d;
+    if (q >= p1) continue;
+    const uint32_t v = s_row[r * ROW_DW + d];
+    if (q >= p0 && q + 4 <= p1) {
+      *(uint32_t*)q = v;
+    } else {
+      for (int b = 0; b < 4; ++b)
+        if (q + b >= p0 && q + b < p1) *(uint8_t*)(q + b) = (uint8_t)(v >> (8 * b));
+    }
+  }
 }
 
 }  // namespace

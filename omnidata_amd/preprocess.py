@@ -430,3 +430,93 @@ def resize_outputs_gpu(y: torch.Tensor, sizes, mode: str, renormalize: bool = Fa
         else:
             res.append(out[d.offset:d.offset + 4 * H * W].view(H, W, 4))
     return res
+
+
+# ------------------------------------------------------------------ test-time augmentation (fullframe.hip views entry, tta.hip)
+TTA_MEAN = 32                # include/dptx.h DPTX_TTA_MEAN
+TTA_RAW_VIEWS = 64           # include/dptx.h DPTX_TTA_RAW_VIEWS
+TTA_MAX_VIEWS = 64           # include/dptx.h DPTX_TTA_MAX_VIEWS: views per image
+
+
+class TtaView(_C.Structure):
+    """include/dptx.h dptx_tta_view."""
+    _fields_ = [("offset", _C.c_int64), ("h", _C.c_int32), ("w", _C.c_int32), ("image", _C.c_int32), ("y0", _C.c_int32),
+                ("x0", _C.c_int32), ("ch", _C.c_int32), ("cw", _C.c_int32), ("flip", _C.c_int32)]
+
+
+def window_desc(d: ImageDesc, box) -> ImageDesc:
+    """The descriptor of the window box = (left, top, right, bottom) of the image d describes, as PIL's img.crop(box) cuts it:
+    the parent's row stride, the offset of the window's first pixel.  The pixels are not copied."""
+    left, top, right, bottom = (int(v) for v in box)
+    if not (0 <= left < right <= d.W and 0 <= top < bottom <= d.H):
+        raise ValueError(f"window {box} is not inside the {d.W}x{d.H} image")
+    return ImageDesc(d.offset + top * d.row_stride_bytes + left * d.C, bottom - top, right - left, d.C, d.row_stride_bytes)
+
+
+def views_to_input_gpu(pixels_dev: torch.Tensor, descs, flips, net_hw, task: str = "normal") -> torch.Tensor:
+    """[B,3,OH,OW] fp32: per descriptor ToTensor(ImageOps.mirror(window.resize((OW, OH), BILINEAR))) -- mirrored where flips[i]
+    -- bit-identical to Pillow.  pixels_dev: the packed uint8 pixels on the device (pack_images, uploaded once); descs: ImageDesc
+    of whole images or of windows of them (window_desc); flips: one truth value per descriptor, or None.  One entry-point call
+    per 4096 views (dptx_preprocess_u8_views_batch)."""
+    from ._native import call, check_cuda, workspace
+    check_cuda("pixels_dev", pixels_dev)
+    descs = list(descs)
+    B, (OH, OW) = len(descs), (int(net_hw[0]), int(net_hw[1]))
+    x = torch.empty(B, 3, OH, OW, dtype=torch.float32, device=pixels_dev.device)
+    if B == 0:
+        return x
+    if flips is not None and len(flips) != B:
+        raise ValueError(f"{B} views but {len(flips)} flips")
+    arr = (ImageDesc * B)(*descs)
+    fl = (_C.c_uint8 * B)(*[1 if f else 0 for f in flips]) if flips is not None else None
+    ws = workspace("dptx_preprocess_rect_batch_workspace_bytes", pixels_dev.device, (min(B, 4096), OH, OW),
+                   f"network size {(OH, OW)}: both sides must be multiples of 32 in [64, 1024]")
+    with torch.cuda.device(pixels_dev.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for b0 in range(0, B, 4096):
+            n = min(4096, B - b0)
+            call("dptx_preprocess_u8_views_batch", pixels_dev.data_ptr(), _C.addressof(arr) + b0 * _C.sizeof(ImageDesc),
+                 _C.addressof(fl) + b0 if fl is not None else None, n, OH, OW, int(task == "depth"), x[b0:].data_ptr(),
+                 ws.data_ptr(), ws.numel(), stream)
+    return x
+
+
+def merge_normal_views_gpu(maps: torch.Tensor, views, sizes, merger: str = "median", normalize_views: bool = True,
+                           output: str = "u8"):
+    """The merge of test-time augmentation (dptx_tta_merge_normals), one call: maps is ONE fp32 cuda tensor that holds every
+    view's [3,h,w] map (values as the network returns them, in [0, 1]); views is a sequence of TtaView -- offset in BYTES into
+    maps, the views of an image consecutive, images ascending --; sizes [(H, W)] per output image.  Per pixel the views that
+    cover it are decoded (2m - 1), normalised at their own resolution (normalize_views), resized into their windows
+    (F.interpolate bilinear; a flipped view un-mirrored with x negated), merged per channel by np.median ("median") or the mean
+    in view order ("mean"), normalised again and encoded.  -> list of device tensors (views of one packed buffer): [H,W,3] uint8
+    (output "u8") or [3,H,W] fp32 ("f32"); a pixel no view covers is the zero vector (0.5 / 127)."""
+    from ._native import call, check_cuda
+    check_cuda("maps", maps)
+    if maps.dtype != torch.float32 or not maps.is_contiguous():
+        raise ValueError("maps must be a contiguous fp32 tensor")
+    if merger not in ("median", "mean"):
+        raise ValueError('merger must be "median" or "mean"')
+    if output not in ("u8", "f32"):
+        raise ValueError('output must be "u8" or "f32"')
+    views = list(views)
+    sizes = [(int(H), int(W)) for H, W in sizes]
+    if not sizes:
+        return []
+    mode = "normal_u8" if output == "u8" else "normal_f32"
+    for v in views:
+        if v.offset < 0 or v.offset + 12 * v.h * v.w > maps.numel() * 4:
+            raise ValueError("a view lies outside maps")
+    descs, total = output_layout(sizes, mode)
+    code = RESIZE_MODES[mode] | (TTA_MEAN if merger == "mean" else 0) | (0 if normalize_views else TTA_RAW_VIEWS)
+    out = torch.empty(max(total, 16), dtype=torch.uint8, device=maps.device)
+    arr = (TtaView * max(len(views), 1))(*views)
+    with torch.cuda.device(maps.device):
+        call("dptx_tta_merge_normals", maps.data_ptr(), _C.addressof(arr), len(views), _C.addressof(descs), len(sizes), code,
+             out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    res = []
+    for d, (H, W) in zip(descs, sizes):
+        if output == "u8":
+            res.append(out[d.offset:d.offset + H * W * 3].view(H, W, 3))
+        else:
+            res.append(out[d.offset:d.offset + 12 * H * W].view(torch.float32).view(3, H, W))
+    return res
