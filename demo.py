@@ -13,7 +13,8 @@ the image's own size and <stem>_rgb.png = the image unchanged; any --batch_size;
 paper_code/oasis_eval_tta.py:324-339, aspect = the aspect-preserving size of modules/midas/transforms.py:94-160; --renormalize
 makes the resized normals unit length again, oasis_eval_tta.py:339), --tta NAME [--tta_merger median|mean] (--task normal: test-time
 augmentation, omnidata_amd/tta.py: the views of preset flip / whole / crops / oasis -- oasis_eval_tta.py:487-534, 40 views -- merged per pixel;
-files as with --full_frame).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
+files as with --full_frame; --task depth --tta NAME --tta_align lstsq: the same for depth, every view fitted to a whole-image
+anchor view by least squares before the merge, omnidata_amd/tta.py DepthTTA, DPT backbones only).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
 """
 import argparse
 import glob
@@ -47,6 +48,9 @@ def main(argv=None):
     parser.add_argument("--tta", default=None, choices=["flip", "whole", "crops", "oasis"],
                         help="--task normal: test-time augmentation with this view preset (omnidata_amd/tta.py), merged per pixel")
     parser.add_argument("--tta_merger", default="median", choices=["median", "mean"], help="--tta: how the views are merged")
+    parser.add_argument("--tta_align", default=None, choices=["lstsq"],
+                        help="--task depth --tta: fit every view to the whole-image anchor view (least-squares scale and shift) "
+                             "before the merge; required for depth")
     args = parser.parse_args(argv)
 
     if args.task not in ("normal", "depth"):
@@ -54,6 +58,18 @@ def main(argv=None):
         sys.exit()
     if args.img_path is None or args.output_path is None:
         print("invalid file path!")
+        sys.exit()
+    if args.tta is not None and args.full_frame is not None:
+        print("--tta excludes --full_frame")
+        sys.exit()
+    if args.tta is not None and args.task == "depth" and args.tta_align is None:
+        print("--tta with --task depth needs --tta_align lstsq: the views of a depth map agree only up to a scale and a shift")
+        sys.exit()
+    if args.tta_align is not None and (args.tta is None or args.task != "depth"):
+        print("--tta_align needs --task depth and --tta")
+        sys.exit()
+    if args.backbone == "unet" and args.tta is not None and args.task == "depth":
+        print("--backbone unet --task depth has no --tta: the alignment is defined for the DPT depth models")
         sys.exit()
 
     from omnidata_amd.model import build_model
@@ -71,9 +87,6 @@ def main(argv=None):
     unet = args.backbone == "unet"
     if args.renormalize and (args.full_frame is None or args.task != "normal"):
         print("--renormalize needs --full_frame and --task normal")
-        sys.exit()
-    if args.tta is not None and (args.task != "normal" or args.full_frame is not None):
-        print("--tta needs --task normal and excludes --full_frame")
         sys.exit()
     if unet and args.full_frame == "aspect":
         print("--backbone unet takes --full_frame squash only: its network sizes are multiples of 64 up to 512, which the "
@@ -109,7 +122,7 @@ def main(argv=None):
         tta_options = dict(multiple=64, max_side=512) if unet and args.tta is not None else None
         BatchPredictor(model, args.task, batch_size=max(args.batch_size, 1), full_frame=args.full_frame,
                        renormalize=args.renormalize, tta=args.tta, tta_merger=args.tta_merger,
-                       tta_options=tta_options).predict_to_dir(files, args.output_path, verbose=True)
+                       tta_options=tta_options, tta_align=args.tta_align).predict_to_dir(files, args.output_path, verbose=True)
         return
 
     def save_outputs(img_path, output_file_name):

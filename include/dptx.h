@@ -432,6 +432,44 @@ typedef struct dptx_tta_view {
 int dptx_tta_merge_normals(const void* views_dev, const dptx_tta_view* views, int32_t n_views, const dptx_image_desc* outs,
                            int32_t B, int32_t mode, void* out_dev, void* stream);
 
+/* ---- Test-time augmentation for depth: align the views to an anchor, then merge them (no handle; DEVICE pointers unless stated) ----
+ * The network's depth is defined up to a scale and a shift per forward (it is trained with the least-squares alignment of
+ * losses/midas_loss.py:10-30, compute_scale_and_shift), so the views of an image cannot be merged as they are: every view is
+ * first fitted to one ANCHOR view that covers the whole image.  The reference has no depth TTA script; this block pins the
+ * protocol.  Conventions as above: stream-ordered, the caller's workspace only, no allocation, no host synchronisation (graph-
+ * capturable), DPTX_E_INVALID before anything is launched; `views`, `anchors` and `outs` are HOST arrays read before the call
+ * returns; no float atomics, fixed orders, bitwise reproducible; an image's result does not depend on the batch.
+ *
+ * dptx_tta_view is reused; offset points at a [1][h][w] fp32 plane m.  For image i of size H x W:
+ *   1. View value: d = clamp(m, 0, 1) at the network's resolution (demo.py:140); its value at image pixel (Y, X) of the window
+ *      is that of F.interpolate(d, (ch, cw), mode='bilinear', align_corners=False) at (Y - y0, X - x0), with `flip` at
+ *      (Y - y0, cw - 1 - (X - x0)); no sign changes.  Coordinates and blend order are those of dptx_tta_merge_normals.
+ *   2. Anchor: anchors[i] is the index (into `views`) of a view of image i with y0 = x0 = 0, ch = H, cw = W.  Its coefficients
+ *      are exactly (1, 0).
+ *   3. Alignment of a view k that is not the anchor, over all n = ch * cw pixels of its window, r = the view's value and a = the
+ *      anchor's value at the same image pixel (both fp32 as step 1 computes them): fp64 sums in a fixed order Sr, Srr, Sa, Sra;
+ *      det = n Srr - Sr^2; scale = (n Sra - Sr Sa) / det, shift = (Srr Sa - Sr Sra) / det, solved in fp64 and rounded once to
+ *      fp32.  A degenerate view, !(det > 1e-10 n Srr) (flatter than 1e-5 of its own level), gets scale = 1 and
+ *      shift = (Sa - Sr) / n.  The scale is not clamped.
+ *   4. Merge: the candidates scale_k * r_k + shift_k (an fp32 multiply, then an add) of the views that cover the pixel, in view
+ *      order; np.median -- the middle one or (a + b) * 0.5 of the two middle ones -- or with DPTX_TTA_MEAN the fp32 sum in view
+ *      order divided by the count; then clamp(0, 1) and 1 - x, the convention of DPTX_RESIZE_DEPTH_F32 -> [H][W] fp32 at
+ *      outs[i] (offset, row_stride_bytes and out_dev multiples of 4).  coeffs_dev = NULL merges the views unaligned; a pixel
+ *      no view covers (possible only then) is 0 before the inversion.
+ *   5. Inputs are assumed finite; non-finite ones neither fault nor hang and affect only the image they belong to.
+ * dptx_tta_align_depth writes coeffs_dev [n_views][2] fp32 (scale, shift).  Its workspace (dptx_tta_depth_workspace_bytes,
+ * host-only; 8-byte aligned) holds every anchor resized to [H][W] fp32 and one record of the four sums per 64 x 16 tile of every
+ * view's window; a view's records depend on its window alone.  dptx_tta_merge_depth samples the anchor from its view like any
+ * other, so it reads nothing of `ws` (pass what the alignment wrote, or NULL).  mode = DPTX_RESIZE_DEPTH_F32, | DPTX_TTA_MEAN;
+ * nothing else.  Ranges are those of dptx_tta_merge_normals; in addition an anchor index that is not a view of its image, or an
+ * anchor that does not cover the whole image, is DPTX_E_INVALID. */
+int dptx_tta_depth_workspace_bytes(const dptx_tta_view* views, int32_t n_views, const dptx_image_desc* outs, int32_t B,
+                                   int64_t* bytes);
+int dptx_tta_align_depth(const void* views_dev, const dptx_tta_view* views, int32_t n_views, const int32_t* anchors,
+                         const dptx_image_desc* outs, int32_t B, float* coeffs_dev, void* ws, int64_t ws_bytes, void* stream);
+int dptx_tta_merge_depth(const void* views_dev, const dptx_tta_view* views, int32_t n_views, const float* coeffs_dev,
+                         const dptx_image_desc* outs, int32_t B, int32_t mode, void* out_dev, const void* ws, void* stream);
+
 /* ---- 3D refocus augmentation (omnidata_tools/torch/data/refocus_augmentation.py; no handle; DEVICE pointers) ----
  * All three are stream-ordered on `stream` and use only the caller's workspace: no allocation, no host synchronisation, no
  * host read of the radii (graph-capturable).  Shapes: B >= 1, C >= 1, 1 <= H, W <= 8192, H*W <= 2^24, n_quantiles >= 1;

@@ -12,7 +12,8 @@ the images by network shape and runs the largest shape first, so the model plans
 
 tta=<preset> (surface normals only) runs the test-time augmentation of paper_code/oasis_eval_tta.py:440-534 instead
 (omnidata_amd/tta.py: every image through the preset's views, merged per pixel): maps of the image's own size, files as in the
-full-frame modes.
+full-frame modes.  With task="depth" it needs tta_align="lstsq" (tta.DepthTTA: every view is fitted to a whole-image anchor
+view by least squares before the merge) and writes <stem>_depth.png as RGBA at the image's own size.
 """
 from __future__ import annotations
 
@@ -74,7 +75,7 @@ def plan_full_frame(sizes, mode: str, image_size: int = 384, batch_size: int = 3
 
 class BatchPredictor:
     def __init__(self, model, task: str, batch_size: int = 32, workers: int = 8, image_size: int = 384, full_frame=None,
-                 renormalize: bool = False, tta=None, tta_merger: str = "median", tta_options=None):
+                 renormalize: bool = False, tta=None, tta_merger: str = "median", tta_options=None, tta_align=None):
         if task not in ("normal", "depth"):
             raise ValueError("task should be one of the following: normal, depth")
         if batch_size < 1:
@@ -83,8 +84,15 @@ class BatchPredictor:
             raise ValueError('full_frame must be None, "squash" or "aspect"')
         if renormalize and (full_frame is None or task != "normal"):
             raise ValueError("renormalize applies to full-frame surface normals only")
-        if tta is not None and (task != "normal" or full_frame is not None):
-            raise ValueError("tta applies to surface normals only and excludes full_frame")
+        if tta_align not in (None, "lstsq"):
+            raise ValueError('tta_align must be None or "lstsq"')
+        if tta_align is not None and (tta is None or task != "depth"):
+            raise ValueError("tta_align applies to depth with tta only")
+        if tta is not None and full_frame is not None:
+            raise ValueError("tta excludes full_frame")
+        if tta is not None and task == "depth" and tta_align is None:
+            raise ValueError('tta for depth needs tta_align="lstsq": the views of a scale-and-shift-ambiguous map cannot be '
+                             "merged without the alignment step")
         self.full_frame, self.renormalize = full_frame, bool(renormalize)
         self.capped = []   # full_frame="aspect": input indices of the last run whose network size was cut back to the supported range
         self.model, self.task, self.batch_size, self.image_size = model, task, int(batch_size), int(image_size)
@@ -93,7 +101,10 @@ class BatchPredictor:
         if self.device.type != "cuda":
             raise RuntimeError("BatchPredictor needs the model on an AMD GPU: the forward is implemented as HIP kernels only")
         self.tta = None
-        if tta is not None:   # tta_options: NormalsTTA's multiple / max_side / chunk_images / normalize_views
+        if tta is not None and task == "depth":   # tta_options: DepthTTA's multiple / max_side / chunk_images
+            from .tta import DepthTTA
+            self.tta = DepthTTA(model, tta, tta_merger, tta_align, batch_size=self.batch_size, **(tta_options or {}))
+        elif tta is not None:   # tta_options: NormalsTTA's multiple / max_side / chunk_images / normalize_views
             from .tta import NormalsTTA
             self.tta = NormalsTTA(model, tta, tta_merger, batch_size=self.batch_size, **(tta_options or {}))
 
@@ -160,7 +171,8 @@ class BatchPredictor:
             futures = following
 
     def _tta_chunks(self, items, pool):
-        """_full_chunks for tta: chunks of NormalsTTA.chunk_images inputs in input order (one upload and one merge each)."""
+        """_full_chunks for tta: chunks of chunk_images inputs in input order (one upload and one merge each); NormalsTTA returns
+        [H,W,3] uint8 and DepthTTA [H,W,4] uint8 RGBA by default."""
         n = self.tta.chunk_images
         chunks = [list(range(i, min(i + n, len(items)))) for i in range(0, len(items), n)]
         futures = [pool.submit(_decode, items[i]) for i in chunks[0]] if chunks else []

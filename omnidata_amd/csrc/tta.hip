@@ -17,28 +17,11 @@
 // The alternative, per-thread columns in LDS, needs 3 x 64 KB per 256 threads for K = 64 (one channel at a time would form the
 // taps three times) and ~K^2 / 4 LDS round trips per channel; see DESIGN.md.
 // Contraction is off (resample_batch.h): two runs, and the same image in another batch, compute the same bits.
-#include "resample_batch.h"
+#include "tta_common.h"
 
 namespace {
 
-constexpr int TW = 64, TH = 4;  // output tile: columns x rows; 256 threads, one pixel each
-constexpr int MAXV = DPTX_TTA_MAX_VIEWS;
 constexpr int M_U8 = DPTX_RESIZE_NORMAL_U8, M_F32 = DPTX_RESIZE_NORMAL_F32;
-
-struct ViewArg {
-  long long first;  // index of the view's first float in views_dev
-  int h, w;
-  int y0, x0, ch, cw;
-  int flip, pad;
-  float sy, sx;  // ATen's area_pixel_compute_scale: (float)in / (float)out, divided once on the host
-};
-struct ViewArgs {
-  ViewArg v[MAXV];  // 64 * 48 B of kernel arguments
-};
-struct MergeOut {
-  long long offset;
-  int H, W, stride, pad;
-};
 
 // 2m - 1, then F.normalize over the channels (eps 1e-12)
 __device__ __forceinline__ void decode(const float* __restrict__ p, int plane, int at, int raw, float n[3]) {
@@ -51,31 +34,6 @@ __device__ __forceinline__ void decode(const float* __restrict__ p, int plane, i
     for (int c = 0; c < 3; ++c) n[c] = n[c] / d;
   }
 }
-
-template <int M>
-struct Lowest {  // the M smallest values so far, ascending
-  float a[M > 0 ? M : 1];
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int j = 0; j < M; ++j) a[j] = INFINITY;
-  }
-  __device__ __forceinline__ void insert(float v) {
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-      const float lo = fminf(a[j], v);
-      v = fmaxf(a[j], v);
-      a[j] = lo;
-    }
-  }
-  // a[i]: the list is ascending, so it is the largest of a[0..i].  (Written as a chain of `j == i ? a[j] : r` the compiler
-  // turns the selects back into an indexed load, and the list into scratch.)
-  __device__ __forceinline__ float at(int i) const {
-    float r = a[0];
-#pragma unroll
-    for (int j = 1; j < M; ++j) r = fmaxf(r, j <= i ? a[j] : -INFINITY);
-    return r;
-  }
-};
 
 template <int M, int MODE>
 __global__ __launch_bounds__(256) void tta_merge_kernel(const float* __restrict__ views, ViewArgs args, int nv, MergeOut o, int raw,
@@ -159,18 +117,6 @@ void launch(int base, int tiles, hipStream_t st, const float* views, const ViewA
   else hipLaunchKernelGGL((tta_merge_kernel<M, M_F32>), dim3(tiles), dim3(256), 0, st, views, args, nv, o, raw, out);
 }
 
-bool out_ok(const dptx_image_desc& d, int base) {
-  if (d.offset < 0 || d.H < 1 || d.W < 1 || d.H > 16384 || d.W > 16384) return false;
-  if ((long long)d.row_stride_bytes < (long long)d.W * (base == M_U8 ? 3 : 4)) return false;
-  return base == M_U8 || !((d.offset & 3) || (d.row_stride_bytes & 3));  // dword stores
-}
-
-bool view_ok(const dptx_tta_view& v, const dptx_image_desc& d) {
-  if (v.offset < 0 || (v.offset & 3) || v.h < 1 || v.w < 1 || v.h > 4096 || v.w > 4096) return false;
-  if (v.y0 < 0 || v.x0 < 0 || v.ch < 1 || v.cw < 1) return false;
-  return (long long)v.y0 + v.ch <= d.H && (long long)v.x0 + v.cw <= d.W;
-}
-
 }  // namespace
 
 extern "C" int dptx_tta_merge_normals(const void* views_dev, const dptx_tta_view* views, int32_t n_views, const dptx_image_desc* outs,
@@ -183,17 +129,8 @@ extern "C" int dptx_tta_merge_normals(const void* views_dev, const dptx_tta_view
   if (base == M_F32 && ((uintptr_t)out_dev & 3)) return DPTX_E_INVALID;
   // the whole call is checked before the first launch: every image has 1..64 consecutive views, images ascending
   for (int i = 0; i < B; ++i)
-    if (!out_ok(outs[i], base)) return DPTX_E_INVALID;
-  int expect = 0, count = 0;
-  for (int k = 0; k < n_views; ++k) {
-    const int img = views[k].image;
-    if (img == expect + 1 && count > 0) {
-      expect = img;
-      count = 0;
-    }
-    if (img != expect || img >= B || ++count > MAXV || !view_ok(views[k], outs[img])) return DPTX_E_INVALID;
-  }
-  if (expect != B - 1) return DPTX_E_INVALID;
+    if (!out_ok(outs[i], base == M_U8 ? 3 : 4)) return DPTX_E_INVALID;
+  if (!views_ok(views, n_views, outs, B)) return DPTX_E_INVALID;
 
   const int raw = (mode & DPTX_TTA_RAW_VIEWS) ? 1 : 0;
   const bool mean = (mode & DPTX_TTA_MEAN) != 0;
@@ -201,16 +138,7 @@ extern "C" int dptx_tta_merge_normals(const void* views_dev, const dptx_tta_view
   for (int i = 0; i < B; ++i) {
     ViewArgs args = {};
     int nv = 0;
-    for (; k < n_views && views[k].image == i; ++k, ++nv) {
-      const dptx_tta_view& v = views[k];
-      ViewArg& a = args.v[nv];
-      a.first = v.offset / 4;
-      a.h = v.h; a.w = v.w;
-      a.y0 = v.y0; a.x0 = v.x0; a.ch = v.ch; a.cw = v.cw;
-      a.flip = v.flip ? 1 : 0;
-      a.sy = (float)v.h / (float)v.ch;
-      a.sx = (float)v.w / (float)v.cw;
-    }
+    for (; k < n_views && views[k].image == i; ++k, ++nv) args.v[nv] = view_arg(views[k]);
     const dptx_image_desc& d = outs[i];
     const MergeOut o = {d.offset, d.H, d.W, d.row_stride_bytes, 0};
     const int tiles = ((d.W + TW - 1) / TW) * ((d.H + TH - 1) / TH);  // <= 2^20

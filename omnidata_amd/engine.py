@@ -97,6 +97,9 @@ ABI = [
     ("dptx_preprocess_u8_rect_batch", C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
     ("dptx_preprocess_u8_views_batch", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
     ("dptx_tta_merge_normals", C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    ("dptx_tta_depth_workspace_bytes", C.c_int, [_vp, _i32, _vp, _i32, _i64p]),
+    ("dptx_tta_align_depth", C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_tta_merge_depth", C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
     ("dptx_postprocess_resize_workspace_bytes", C.c_int, [_i32, _i32, _i64p]),
     ("dptx_postprocess_resize_batch", C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
     ("dptx_refocus_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64p]),

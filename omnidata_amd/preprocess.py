@@ -432,7 +432,7 @@ def resize_outputs_gpu(y: torch.Tensor, sizes, mode: str, renormalize: bool = Fa
     return res
 
 
-# ------------------------------------------------------------------ test-time augmentation (fullframe.hip views entry, tta.hip)
+# ------------------------------------------------------------------ test-time augmentation (fullframe.hip views entry, tta.hip, tta_depth.hip)
 TTA_MEAN = 32                # include/dptx.h DPTX_TTA_MEAN
 TTA_RAW_VIEWS = 64           # include/dptx.h DPTX_TTA_RAW_VIEWS
 TTA_MAX_VIEWS = 64           # include/dptx.h DPTX_TTA_MAX_VIEWS: views per image
@@ -519,4 +519,78 @@ def merge_normal_views_gpu(maps: torch.Tensor, views, sizes, merger: str = "medi
             res.append(out[d.offset:d.offset + H * W * 3].view(H, W, 3))
         else:
             res.append(out[d.offset:d.offset + 12 * H * W].view(torch.float32).view(3, H, W))
+    return res
+
+
+def _check_depth_views(maps, views, sizes):
+    from ._native import check_cuda
+    check_cuda("maps", maps)
+    if maps.dtype != torch.float32 or not maps.is_contiguous():
+        raise ValueError("maps must be a contiguous fp32 tensor")
+    views = list(views)
+    sizes = [(int(H), int(W)) for H, W in sizes]
+    for v in views:
+        if v.offset < 0 or v.offset + 4 * v.h * v.w > maps.numel() * 4:
+            raise ValueError("a view lies outside maps")
+    return views, sizes
+
+
+def align_depth_views_gpu(maps: torch.Tensor, views, anchors, sizes):
+    """The alignment step of test-time augmentation for depth (dptx_tta_align_depth), one call: maps is ONE fp32 cuda tensor
+    that holds every view's [1,h,w] map as the network returns it; views is a sequence of TtaView as merge_normal_views_gpu
+    takes it; anchors[i] is the index (into views) of the view of image i that covers the whole image; sizes [(H, W)] per
+    image.  Every view is fitted to its image's anchor by least squares over its window (include/dptx.h: fp64 sums, solved in
+    fp64); the anchor's coefficients are exactly (1, 0).  -> (coeffs [n_views, 2] cuda fp32: scale, shift; the workspace the
+    call wrote, for merge_depth_views_gpu)."""
+    from ._native import call
+    views, sizes = _check_depth_views(maps, views, sizes)
+    anchors = [int(a) for a in anchors]
+    if len(anchors) != len(sizes):
+        raise ValueError(f"{len(sizes)} images but {len(anchors)} anchors")
+    if not sizes:
+        raise ValueError("no image")
+    descs, _ = output_layout(sizes, "depth_f32")
+    arr = (TtaView * max(len(views), 1))(*views)
+    anc = (_C.c_int32 * len(anchors))(*anchors)
+    nbytes = _C.c_int64()
+    call("dptx_tta_depth_workspace_bytes", _C.addressof(arr), len(views), _C.addressof(descs), len(sizes), _C.byref(nbytes))
+    ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=maps.device)
+    coeffs = torch.empty(len(views), 2, dtype=torch.float32, device=maps.device)
+    with torch.cuda.device(maps.device):
+        call("dptx_tta_align_depth", maps.data_ptr(), _C.addressof(arr), len(views), _C.addressof(anc), _C.addressof(descs),
+             len(sizes), coeffs.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    return coeffs, ws
+
+
+def merge_depth_views_gpu(maps: torch.Tensor, views, sizes, coeffs=None, ws=None, merger: str = "median", output: str = "f32"):
+    """The merge of test-time augmentation for depth (dptx_tta_merge_depth), one call: per pixel the views that cover it are
+    clamped to [0, 1] at their own resolution, resized into their windows (F.interpolate bilinear; a flipped view un-mirrored),
+    mapped by their coefficients (scale * r + shift; coeffs / ws as align_depth_views_gpu returned them, None = unaligned) and
+    merged by np.median ("median") or the mean in view order ("mean"); then clamp(0, 1) and 1 - x.  -> list of device tensors:
+    [H,W] fp32 (output "f32", views of one packed buffer) or [H,W,4] uint8 ("rgba": depths_to_rgba_gpu of each map, viridis over
+    its own range, as the full-frame depth path writes)."""
+    from ._native import call
+    views, sizes = _check_depth_views(maps, views, sizes)
+    if merger not in ("median", "mean"):
+        raise ValueError('merger must be "median" or "mean"')
+    if output not in ("f32", "rgba"):
+        raise ValueError('output must be "f32" or "rgba"')
+    if not sizes:
+        return []
+    if coeffs is not None:
+        from ._native import check_cuda
+        check_cuda("coeffs", coeffs)
+        if coeffs.dtype != torch.float32 or not coeffs.is_contiguous() or tuple(coeffs.shape) != (len(views), 2):
+            raise ValueError("coeffs must be a contiguous fp32 tensor [n_views, 2]")
+    descs, total = output_layout(sizes, "depth_f32")
+    code = RESIZE_MODES["depth_f32"] | (TTA_MEAN if merger == "mean" else 0)
+    out = torch.empty(max(total, 16), dtype=torch.uint8, device=maps.device)
+    arr = (TtaView * max(len(views), 1))(*views)
+    with torch.cuda.device(maps.device):
+        call("dptx_tta_merge_depth", maps.data_ptr(), _C.addressof(arr), len(views), coeffs.data_ptr() if coeffs is not None else None,
+             _C.addressof(descs), len(sizes), code, out.data_ptr(), ws.data_ptr() if ws is not None else None,
+             torch.cuda.current_stream().cuda_stream)
+    res = [out[d.offset:d.offset + 4 * H * W].view(torch.float32).view(H, W) for d, (H, W) in zip(descs, sizes)]
+    if output == "rgba":
+        res = [depths_to_rgba_gpu(m[None])[0] for m in res]
     return res

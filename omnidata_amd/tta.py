@@ -19,7 +19,24 @@ Definitions
   A view is decoded (2m - 1) and normalised at the network's resolution (oasis_eval_tta.py:441-445; the OASIS z-sign change of
     line 442 is not reproduced), resized with F.interpolate(mode='bilinear', align_corners=False); the merge is normalised again.
 
-Depth is out of scope: crops of a scale-and-shift-ambiguous map cannot be merged without an alignment step.
+Depth (DepthTTA; the reference has no depth TTA script, so these definitions pin the protocol -- include/dptx.h states them
+for the C entry points).  The network's depth is defined up to a scale and a shift per forward, and it is trained with the
+least-squares alignment of losses/midas_loss.py:10-30 (compute_scale_and_shift): that alignment is the model's own notion of
+"equal up to an affine map", and it is the step that makes crops mergeable.
+  View value: d = clamp(m, 0, 1) at the network's resolution (demo.py:140), resized into its window with
+    F.interpolate(mode='bilinear', align_corners=False); a flipped view is un-mirrored, no sign changes.  Coordinates and blend
+    order are those of the normals merge.
+  Anchor: one view per image that covers the whole image; its coefficients are exactly (1, 0).  DepthTTA takes the first
+    unflipped whole-image view of the plan; a plan without one ("crops") gets ((0, 0, w, h), False, 384, net) prepended, and a
+    plan that would then exceed 64 views raises.
+  Alignment of a view k that is not the anchor: over all n = ch * cw pixels of its window, with r the view's value and a the
+    anchor's value at the same image pixel (fp32 both), fp64 sums in a fixed order Sr, Srr, Sa, Sra; det = n Srr - Sr^2;
+    scale = (n Sra - Sr Sa) / det, shift = (Srr Sa - Sr Sra) / det, solved in fp64 and rounded once to fp32.  A degenerate view,
+    not (det > 1e-10 n Srr) -- flatter than 1e-5 of its own level --, gets scale = 1 and shift = (Sa - Sr) / n.  The solved scale
+    is not clamped.
+  Merge: the candidates scale_k * r_k + shift_k (an fp32 multiply, then an add) of the covering views in view order; np.median
+    or the fp32 mean in view order; then clamp(0, 1) and 1 - x, the convention of resize_outputs_gpu(..., "depth_f32").
+  Inputs are assumed finite; non-finite ones neither fault nor hang and affect only the image they belong to.
 """
 from __future__ import annotations
 
@@ -76,6 +93,53 @@ def _as_image(img):
     return img
 
 
+def plan_depth_views(w: int, h: int, preset="whole", multiple: int = 32, max_side: int = 1024):
+    """-> (plan_views(...) with an anchor in it, the anchor's index): the anchor is the first unflipped view of the whole image;
+    a plan without one gets ((0, 0, w, h), False, 384, net) prepended.  More than 64 views then raises."""
+    views = plan_views(w, h, preset, multiple, max_side)
+    for k, (box, flip, _, _) in enumerate(views):
+        if box == (0, 0, w, h) and not flip:
+            return views, k
+    if len(views) + 1 > pp.TTA_MAX_VIEWS:
+        raise ValueError(f"the preset gives {len(views)} views and none of the whole image: with the anchor that is more than "
+                         f"{pp.TTA_MAX_VIEWS} per image")
+    top = max_side // multiple * multiple
+    nw, nh, _ = pp.full_frame_net_size(w, h, 384, multiple)
+    return [((0, 0, w, h), False, 384, (min(nh, top), min(nw, top)))] + views, 0
+
+
+def _forward_views(model, images, plans, batch_size: int, device, channels: int, task: str):
+    """What NormalsTTA and DepthTTA share: the images uploaded once, every view of plans(descs)[i] (plan_views' tuples per
+    image, from the images' descriptors) through the network -- bucketed by network shape, the largest shape first, batch_size views per forward -- and the maps laid
+    out for the merge.  -> (maps: one fp32 device tensor, [TtaView] in the merge's image-major order with offsets into maps,
+    [(H, W)] per image).  channels: of the network's map per view; task: what views_to_input_gpu normalises for."""
+    buf, descs = pp.pack_images(images)                      # every image is uploaded once
+    flat = [(i, v) for i, plan in enumerate(plans(descs[:len(images)])) for v in plan]   # the merge's order: image-major
+    buckets = {}
+    for k, (_, (_, _, _, net)) in enumerate(flat):
+        buckets.setdefault(net, []).append(k)
+    order = sorted(buckets, key=lambda net: (-net[0] * net[1], buckets[net][0]))   # the largest shape first: one arena plan
+    # the maps are stored bucket by bucket, so a forward's output is one contiguous copy
+    at, total = {}, 0
+    for net in order:
+        for k in buckets[net]:
+            at[k] = total
+            total += channels * net[0] * net[1]
+    dev = buf.to(device, non_blocking=True)
+    maps = torch.empty(total, dtype=torch.float32, device=device)
+    for net in order:
+        ks = buckets[net]
+        for b0 in range(0, len(ks), batch_size):
+            part = ks[b0:b0 + batch_size]
+            x = pp.views_to_input_gpu(dev, [pp.window_desc(descs[flat[k][0]], flat[k][1][0]) for k in part],
+                                      [flat[k][1][1] for k in part], net, task)
+            n = len(part) * channels * net[0] * net[1]
+            maps[at[part[0]]:at[part[0]] + n].view(len(part), channels, *net).copy_(model(x).reshape(len(part), channels, *net))
+    views = [pp.TtaView(4 * at[k], net[0], net[1], i, box[1], box[0], box[3] - box[1], box[2] - box[0], int(flip))
+             for k, (i, (box, flip, _, net)) in enumerate(flat)]
+    return maps, views, [(d.H, d.W) for d in descs[:len(images)]]
+
+
 class NormalsTTA:
     """model: a surface-normal network on the GPU, x [B,3,h,w] in [0, 1] -> [B,3,h,w] (encoded normals), for any h, w that are
     multiples of `multiple` up to `max_side` and B <= batch_size.  The version-1 UNet takes multiple=64, max_side=512."""
@@ -95,34 +159,10 @@ class NormalsTTA:
 
     def _chunk(self, images, output):
         images = [_as_image(im) for im in images]
-        buf, descs = pp.pack_images(images)                      # every image is uploaded once
-        plans = [plan_views(d.W, d.H, self.preset, self.multiple, self.max_side) for d in descs[:len(images)]]
-        flat = [(i, v) for i, plan in enumerate(plans) for v in plan]            # the merge's order: image-major
-        buckets = {}
-        for k, (_, (_, _, _, net)) in enumerate(flat):
-            buckets.setdefault(net, []).append(k)
-        order = sorted(buckets, key=lambda net: (-net[0] * net[1], buckets[net][0]))   # the largest shape first: one arena plan
-        # the maps are stored bucket by bucket, so a forward's output is one contiguous copy
-        at, total = {}, 0
-        for net in order:
-            for k in buckets[net]:
-                at[k] = total
-                total += 3 * net[0] * net[1]
+        plans = lambda descs: [plan_views(d.W, d.H, self.preset, self.multiple, self.max_side) for d in descs]
         with torch.no_grad(), torch.cuda.device(self.device):
-            dev = buf.to(self.device, non_blocking=True)
-            maps = torch.empty(total, dtype=torch.float32, device=self.device)
-            for net in order:
-                ks = buckets[net]
-                for b0 in range(0, len(ks), self.batch_size):
-                    part = ks[b0:b0 + self.batch_size]
-                    x = pp.views_to_input_gpu(dev, [pp.window_desc(descs[flat[k][0]], flat[k][1][0]) for k in part],
-                                              [flat[k][1][1] for k in part], net, "normal")
-                    n = len(part) * 3 * net[0] * net[1]
-                    maps[at[part[0]]:at[part[0]] + n].view(len(part), 3, *net).copy_(self.model(x))
-            views = [pp.TtaView(4 * at[k], net[0], net[1], i, box[1], box[0], box[3] - box[1], box[2] - box[0], int(flip))
-                     for k, (i, (box, flip, _, net)) in enumerate(flat)]
-            return pp.merge_normal_views_gpu(maps, views, [(d.H, d.W) for d in descs[:len(images)]], self.merger,
-                                             self.normalize_views, output)
+            maps, views, sizes = _forward_views(self.model, images, plans, self.batch_size, self.device, 3, "normal")
+            return pp.merge_normal_views_gpu(maps, views, sizes, self.merger, self.normalize_views, output)
 
     def __call__(self, images, output: str = "u8"):
         """images: PIL images or uint8 HW[C] arrays -> list of device tensors at each image's own size: [H,W,3] uint8, or
@@ -134,3 +174,67 @@ class NormalsTTA:
         for c0 in range(0, len(images), self.chunk_images):
             res += self._chunk(images[c0:c0 + self.chunk_images], output)
         return res
+
+
+class DepthTTA:
+    """model: a DPT depth network (hybrid or large) on the GPU, x [B,3,h,w] in [-1, 1] -> [B,h,w], for any h, w that are
+    multiples of `multiple` up to `max_side` and B <= batch_size.  align: "lstsq" fits every view to the image's anchor view
+    before the merge (the module's definitions); None merges the views as they are, for comparison."""
+
+    def __init__(self, model, preset="whole", merger: str = "median", align="lstsq", batch_size: int = 32, multiple: int = 32,
+                 max_side: int = 1024, chunk_images: int = 8):
+        if merger not in ("median", "mean"):
+            raise ValueError('merger must be "median" or "mean"')
+        if align not in ("lstsq", None):
+            raise ValueError('align must be "lstsq" or None')
+        if batch_size < 1 or chunk_images < 1:
+            raise ValueError("batch_size and chunk_images must be >= 1")
+        from .model import DPTDepthModel
+        if not isinstance(model, DPTDepthModel) or model.num_channels != 1:
+            raise ValueError("DepthTTA takes a DPT depth model (build_model('depth', ...), hybrid or large)")
+        plan_depth_views(64, 64, preset, multiple, max_side)   # an unknown preset raises here
+        self.model, self.preset, self.merger, self.align = model, preset, merger, align
+        self.batch_size, self.multiple, self.max_side, self.chunk_images = int(batch_size), int(multiple), int(max_side), int(chunk_images)
+        self.device = next(model.parameters()).device
+        if self.device.type != "cuda":
+            raise RuntimeError("DepthTTA needs the model on an AMD GPU: the forward, the alignment and the merge are HIP kernels only")
+
+    def _chunk(self, images, output, return_coeffs):
+        images = [_as_image(im) for im in images]
+        anchors = []
+
+        def plans(descs):
+            planned = [plan_depth_views(d.W, d.H, self.preset, self.multiple, self.max_side) for d in descs]
+            first = 0
+            for plan, anchor in planned:
+                anchors.append(first + anchor)
+                first += len(plan)
+            return [plan for plan, _ in planned]
+
+        with torch.no_grad(), torch.cuda.device(self.device):
+            maps, views, sizes = _forward_views(self.model, images, plans, self.batch_size, self.device, 1, "depth")
+            coeffs = ws = None
+            if self.align is not None:
+                coeffs, ws = pp.align_depth_views_gpu(maps, views, anchors, sizes)
+            res = pp.merge_depth_views_gpu(maps, views, sizes, coeffs, ws, self.merger, output)
+        if not return_coeffs:
+            return res, None
+        if coeffs is None:
+            return res, [None] * len(images)
+        counts = [sum(1 for v in views if v.image == i) for i in range(len(images))]
+        return res, list(coeffs.split(counts))
+
+    def __call__(self, images, output: str = "rgba", return_coeffs: bool = False):
+        """images: PIL images or uint8 HW[C] arrays -> list of device tensors at each image's own size: [H,W,4] uint8 (viridis
+        over the map's own range), or [H,W] fp32 (1 - depth, as resize_outputs_gpu(..., "depth_f32")) with output="f32".
+        return_coeffs=True: -> (that list, per image the [views, 2] fp32 (scale, shift) of its views in plan_depth_views'
+        order; None per image with align=None).  chunk_images images share one upload, one alignment and one merge call."""
+        if output not in ("rgba", "f32"):
+            raise ValueError('output must be "rgba" or "f32"')
+        images = list(images)
+        res, coeffs = [], []
+        for c0 in range(0, len(images), self.chunk_images):
+            r, c = self._chunk(images[c0:c0 + self.chunk_images], output, return_coeffs)
+            res += r
+            coeffs += c or []
+        return (res, coeffs) if return_coeffs else res
