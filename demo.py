@@ -14,7 +14,10 @@ paper_code/oasis_eval_tta.py:324-339, aspect = the aspect-preserving size of mod
 makes the resized normals unit length again, oasis_eval_tta.py:339), --tta NAME [--tta_merger median|mean] (--task normal: test-time
 augmentation, omnidata_amd/tta.py: the views of preset flip / whole / crops / oasis -- oasis_eval_tta.py:487-534, 40 views -- merged per pixel;
 files as with --full_frame; --task depth --tta NAME --tta_align lstsq: the same for depth, every view fitted to a whole-image
-anchor view by least squares before the merge, omnidata_amd/tta.py DepthTTA, DPT backbones only).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
+anchor view by least squares before the merge, omnidata_amd/tta.py DepthTTA, DPT backbones only), --tiled [--tile_size 384
+--tile_scale 1.0 --tile_overlap 0.25] (tiled high-resolution inference, omnidata_amd/tiled.py: overlapping tiles at the chosen pixel
+scale, blended with feathered weights; depth tiles are aligned to a whole-image anchor; files as with --full_frame; excludes
+--full_frame and --tta).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
 """
 import argparse
 import glob
@@ -51,6 +54,12 @@ def main(argv=None):
     parser.add_argument("--tta_align", default=None, choices=["lstsq"],
                         help="--task depth --tta: fit every view to the whole-image anchor view (least-squares scale and shift) "
                              "before the merge; required for depth")
+    parser.add_argument("--tiled", action="store_true",
+                        help="tiled high-resolution inference (omnidata_amd/tiled.py): overlapping tiles, feathered blend, the map "
+                             "at the image's own size; depth tiles are aligned to a whole-image anchor")
+    parser.add_argument("--tile_size", type=int, default=384, help="--tiled: the network's short side for a tile")
+    parser.add_argument("--tile_scale", type=float, default=1.0, help="--tiled: image pixels per network pixel along a tile's side")
+    parser.add_argument("--tile_overlap", type=float, default=0.25, help="--tiled: the blend ramp as a fraction of the window, 0 .. 0.5")
     args = parser.parse_args(argv)
 
     if args.task not in ("normal", "depth"):
@@ -67,6 +76,15 @@ def main(argv=None):
         sys.exit()
     if args.tta_align is not None and (args.tta is None or args.task != "depth"):
         print("--tta_align needs --task depth and --tta")
+        sys.exit()
+    if args.tiled and (args.tta is not None or args.full_frame is not None):
+        print("--tiled excludes --full_frame and --tta")
+        sys.exit()
+    if args.tiled and not (0 <= args.tile_overlap <= 0.5 and args.tile_size >= 1 and args.tile_scale > 0):
+        print("--tiled needs --tile_size >= 1, --tile_scale > 0 and --tile_overlap in [0, 0.5]")
+        sys.exit()
+    if args.backbone == "unet" and args.tiled and args.task == "depth":
+        print("--backbone unet --task depth has no --tiled: the alignment is defined for the DPT depth models")
         sys.exit()
     if args.backbone == "unet" and args.tta is not None and args.task == "depth":
         print("--backbone unet --task depth has no --tta: the alignment is defined for the DPT depth models")
@@ -111,7 +129,7 @@ def main(argv=None):
         model = build_model(args.task, weights=weights, random_weights=args.random_weights, dtype=args.dtype,
                             max_batch=max(args.batch_size, 1), backbone=args.backbone)
     model.to(device)
-    if args.batch_size > 1 or args.full_frame is not None or args.tta is not None:
+    if args.batch_size > 1 or args.full_frame is not None or args.tta is not None or args.tiled:
         from omnidata_amd.batch_infer import BatchPredictor
         p = Path(args.img_path)
         if not (p.is_file() or p.is_dir()):
@@ -120,9 +138,14 @@ def main(argv=None):
         files = [args.img_path] if p.is_file() else glob.glob(args.img_path + "/*")
         # the version-1 UNet takes sides that are multiples of 64 up to 512 (the model oasis_eval_tta.py evaluates)
         tta_options = dict(multiple=64, max_side=512) if unet and args.tta is not None else None
+        tiled = None
+        if args.tiled:
+            tiled = dict(tile=args.tile_size, scale=args.tile_scale, overlap=args.tile_overlap)
+            if unet:
+                tiled.update(multiple=64, max_side=512)
         BatchPredictor(model, args.task, batch_size=max(args.batch_size, 1), full_frame=args.full_frame,
                        renormalize=args.renormalize, tta=args.tta, tta_merger=args.tta_merger,
-                       tta_options=tta_options, tta_align=args.tta_align).predict_to_dir(files, args.output_path, verbose=True)
+                       tta_options=tta_options, tta_align=args.tta_align, tiled=tiled).predict_to_dir(files, args.output_path, verbose=True)
         return
 
     def save_outputs(img_path, output_file_name):

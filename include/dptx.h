@@ -470,6 +470,58 @@ int dptx_tta_align_depth(const void* views_dev, const dptx_tta_view* views, int3
 int dptx_tta_merge_depth(const void* views_dev, const dptx_tta_view* views, int32_t n_views, const float* coeffs_dev,
                          const dptx_image_desc* outs, int32_t B, int32_t mode, void* out_dev, const void* ws, void* stream);
 
+/* ---- Tiled inference: overlapping tiles of one size, blended with feathered weights (no handle; DEVICE pointers unless stated) ----
+ * An image of any size up to 16384 a side is cut into ny x nx windows of ch x cw pixels, every window goes through the network at
+ * one network size h x w, and the maps are blended into a map of the image's own size.  The reference has no tiled script; this
+ * block pins the protocol (omnidata_amd/tiled.py states the planner).  Conventions as above: stream-ordered, the caller's workspace
+ * only, no allocation, no host synchronisation (graph-capturable), DPTX_E_INVALID before anything is launched; `grids` and `outs`
+ * are HOST arrays (one entry per image) read before the call returns; no atomics, fixed orders, bitwise reproducible; an image's
+ * result does not depend on the batch.  One blend launch per image, the grid by value in the kernel's arguments.
+ *
+ *   1. Grid: the starts y0[0 .. ny), x0[0 .. nx) ascend strictly, the first is 0, the last window ends at H / W, and neighbouring
+ *      windows leave no gap (s[i + 1] <= s[i] + c).  Tile (iy, ix) is the window [y0[iy], y0[iy] + ch) x [x0[ix], x0[ix] + cw);
+ *      its map m [C][h][w] fp32 (C = 3 normals, 1 depth) lies at views_dev + offset + (iy * nx + ix) * C * h * w * 4.
+ *   2. Tile value: that of an unflipped view of the TTA merges.  Normals: n = 2m - 1, normalised at the network's resolution
+ *      unless DPTX_TTA_RAW_VIEWS; depth: d = clamp(m, 0, 1).  Then the value of F.interpolate(., (ch, cw), mode='bilinear',
+ *      align_corners=False) at the pixel's place in the window; coordinates and blend order as dptx_tta_merge_normals.
+ *   3. Weight at local coordinate t in [0, c) of an axis with ramp r, start s and length L, in fp32:
+ *        left  = (s == 0 || r == 0)     ? 1 : fminf(1, (t + 0.5f) / r)
+ *        right = (s + c == L || r == 0) ? 1 : fminf(1, ((c - 1 - t) + 0.5f) / r)
+ *      w_axis = left * right, w = w_y * w_x: an edge on the image border is not ramped, w > 0 everywhere in a window, and the sum of
+ *      the weights at a pixel is >= 1.
+ *   4. Blend over the tiles that cover the pixel, iy ascending, then ix ascending, every step an fp32 multiply, then an add:
+ *      normals  acc_c += w * v_c; then F.normalize (eps 1e-12), (n + 1) / 2, clamp and quantisation of DPTX_RESIZE_NORMAL_U8 /
+ *               DPTX_RESIZE_NORMAL_F32 (mode = one of them, | DPTX_TTA_RAW_VIEWS; nothing else);
+ *      depth    acc += w * (scale_k * r_k + shift_k) (k = iy * nx + ix), wsum += w; then acc / wsum, clamp(0, 1) and 1 - x as
+ *               DPTX_RESIZE_DEPTH_F32 (the only mode).  coeffs_dev = NULL blends the tiles unaligned, for comparison.
+ *   5. Alignment (depth): the anchor -- the whole image's map [1][ah][aw] at views_dev + anchor_offset -- is used for the
+ *      alignment only, it is not blended.  Every tile is fitted to it by step 3 of dptx_tta_align_depth, unchanged (the same
+ *      device code: fp64 sums per 64 x 16 tile of the window, the degenerate rule, one rounding to fp32): a tile's coefficients
+ *      equal, bit for bit, what dptx_tta_align_depth gives for the same window and anchor.
+ *   6. Inputs are assumed finite; non-finite ones neither fault nor hang and affect only the image they belong to.
+ * coeffs_dev: [tiles of image 0 | of image 1 | ...][2] fp32 (scale, shift), an image's tiles in grid order.  The workspace of
+ * dptx_tile_align_depth (dptx_tile_depth_workspace_bytes, host-only; 8-byte aligned): every anchor resized to [H][W] fp32 and the
+ * records of one chunk of at most 63 tiles.  Range: 1 <= B <= 4096; 1 <= ny, nx <= 64; 1 <= h, w, ah, aw <= 4096; offsets >= 0
+ * and multiples of 4, as views_dev; ramps >= 0; outs as for dptx_tta_merge_normals / dptx_tta_merge_depth.  A grid that breaks
+ * rule 1, and for dptx_tile_align_depth an image without an anchor, is DPTX_E_INVALID. */
+#define DPTX_TILE_MAX_AXIS 64
+typedef struct dptx_tile_grid {
+  int64_t offset;          /* bytes to tile (0,0)'s [C][h][w] fp32 map; tile (iy,ix) at + (iy*nx+ix)*C*h*w*4 */
+  int64_t anchor_offset;   /* depth: bytes to the anchor's [1][ah][aw] map; -1 = none */
+  int32_t h, w, ch, cw;    /* every tile's network map and window size */
+  int32_t ny, nx;          /* 1..64 each */
+  int32_t ramp_y, ramp_x;  /* >= 0 */
+  int32_t ah, aw;
+  int32_t y0[64], x0[64];  /* ascending, first 0, last + c == H / W, no gap */
+} dptx_tile_grid;          /* one per image */
+int dptx_tile_blend_normals(const void* views_dev, const dptx_tile_grid* grids, const dptx_image_desc* outs, int32_t B, int32_t mode,
+                            void* out_dev, void* stream);
+int dptx_tile_depth_workspace_bytes(const dptx_tile_grid* grids, const dptx_image_desc* outs, int32_t B, int64_t* bytes);
+int dptx_tile_align_depth(const void* views_dev, const dptx_tile_grid* grids, const dptx_image_desc* outs, int32_t B,
+                          float* coeffs_dev, void* ws, int64_t ws_bytes, void* stream);
+int dptx_tile_blend_depth(const void* views_dev, const dptx_tile_grid* grids, const float* coeffs_dev, const dptx_image_desc* outs,
+                          int32_t B, int32_t mode, void* out_dev, void* stream);
+
 /* ---- 3D refocus augmentation (omnidata_tools/torch/data/refocus_augmentation.py; no handle; DEVICE pointers) ----
  * All three are stream-ordered on `stream` and use only the caller's workspace: no allocation, no host synchronisation, no
  * host read of the radii (graph-capturable).  Shapes: B >= 1, C >= 1, 1 <= H, W <= 8192, H*W <= 2^24, n_quantiles >= 1;

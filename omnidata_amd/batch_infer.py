@@ -14,6 +14,10 @@ tta=<preset> (surface normals only) runs the test-time augmentation of paper_cod
 (omnidata_amd/tta.py: every image through the preset's views, merged per pixel): maps of the image's own size, files as in the
 full-frame modes.  With task="depth" it needs tta_align="lstsq" (tta.DepthTTA: every view is fitted to a whole-image anchor
 view by least squares before the merge) and writes <stem>_depth.png as RGBA at the image's own size.
+
+tiled=True | {tile, scale, overlap, ...} runs tiled high-resolution inference instead (omnidata_amd/tiled.py: overlapping tiles of
+the image at the chosen pixel scale, blended with feathered weights; depth tiles are first aligned to a whole-image anchor): maps
+of the image's own size, files as in the full-frame modes.  It excludes full_frame and tta.
 """
 from __future__ import annotations
 
@@ -75,7 +79,7 @@ def plan_full_frame(sizes, mode: str, image_size: int = 384, batch_size: int = 3
 
 class BatchPredictor:
     def __init__(self, model, task: str, batch_size: int = 32, workers: int = 8, image_size: int = 384, full_frame=None,
-                 renormalize: bool = False, tta=None, tta_merger: str = "median", tta_options=None, tta_align=None):
+                 renormalize: bool = False, tta=None, tta_merger: str = "median", tta_options=None, tta_align=None, tiled=None):
         if task not in ("normal", "depth"):
             raise ValueError("task should be one of the following: normal, depth")
         if batch_size < 1:
@@ -93,6 +97,12 @@ class BatchPredictor:
         if tta is not None and task == "depth" and tta_align is None:
             raise ValueError('tta for depth needs tta_align="lstsq": the views of a scale-and-shift-ambiguous map cannot be '
                              "merged without the alignment step")
+        if tiled is False:
+            tiled = None
+        if tiled is not None and (tta is not None or full_frame is not None):
+            raise ValueError("tiled excludes full_frame and tta")
+        if tiled is not None and tiled is not True and not isinstance(tiled, dict):
+            raise ValueError("tiled must be None, True or a dict of TiledNormals' / TiledDepth's options")
         self.full_frame, self.renormalize = full_frame, bool(renormalize)
         self.capped = []   # full_frame="aspect": input indices of the last run whose network size was cut back to the supported range
         self.model, self.task, self.batch_size, self.image_size = model, task, int(batch_size), int(image_size)
@@ -107,6 +117,10 @@ class BatchPredictor:
         elif tta is not None:   # tta_options: NormalsTTA's multiple / max_side / chunk_images / normalize_views
             from .tta import NormalsTTA
             self.tta = NormalsTTA(model, tta, tta_merger, batch_size=self.batch_size, **(tta_options or {}))
+        elif tiled is not None:   # the tiled classes are called as the TTA ones are: chunk_images inputs -> maps at their own sizes
+            from .tiled import TiledDepth, TiledNormals
+            options = dict(batch_size=self.batch_size, **({} if tiled is True else tiled))
+            self.tta = (TiledDepth if task == "depth" else TiledNormals)(model, **options)
 
     # ---- GPU side of one batch: decoded images -> final pixels, still on the device
     def _run(self, images) -> torch.Tensor:
@@ -229,7 +243,7 @@ class BatchPredictor:
 
     def predict(self, images_or_paths):
         """Yields one device tensor per input, in input order (normal: [S,S,3] uint8, depth: [512,512,4] uint8 RGBA; with
-        full_frame or tta the image's own size: [H,W,3] uint8, depth [H,W,4] uint8 RGBA).  Nothing is read back."""
+        full_frame, tta or tiled the image's own size: [H,W,3] uint8, depth [H,W,4] uint8 RGBA).  Nothing is read back."""
         items = list(images_or_paths)
         if self.full_frame is not None or self.tta is not None:
             yield from self._predict_full(items)

@@ -23,18 +23,6 @@ namespace {
 
 constexpr int M_U8 = DPTX_RESIZE_NORMAL_U8, M_F32 = DPTX_RESIZE_NORMAL_F32;
 
-// 2m - 1, then F.normalize over the channels (eps 1e-12)
-__device__ __forceinline__ void decode(const float* __restrict__ p, int plane, int at, int raw, float n[3]) {
-  for (int c = 0; c < 3; ++c) n[c] = 2.f * p[c * plane + at] - 1.f;
-  if (!raw) {
-    float ss = n[0] * n[0];
-    ss += n[1] * n[1];
-    ss += n[2] * n[2];
-    const float d = fmaxf(sqrtf(ss), 1e-12f);
-    for (int c = 0; c < 3; ++c) n[c] = n[c] / d;
-  }
-}
-
 template <int M, int MODE>
 __global__ __launch_bounds__(256) void tta_merge_kernel(const float* __restrict__ views, ViewArgs args, int nv, MergeOut o, int raw,
                                                         uint8_t* __restrict__ out) {

@@ -1,6 +1,6 @@
 // tta_common.h -- what the two merges of test-time augmentation share (tta.hip: surface normals; tta_depth.hip: depth): the output
 // tile, the view descriptors that travel by value in the kernel arguments, the in-register selection of the M smallest values,
-// and the host-side checks of a call's views and outputs.  Contraction is off here as in resample_batch.h, whose taps both use.
+// the decode of a normal (tta.hip and the blend of tiles.hip) and the host-side checks of a call's views and outputs.  Contraction is off here as in resample_batch.h, whose taps both use.
 #pragma once
 #include "resample_batch.h"
 
@@ -48,6 +48,18 @@ struct Lowest {  // the M smallest values so far, ascending
     return r;
   }
 };
+
+// a normal at `at` of a view's [3][plane] map: 2m - 1, then F.normalize over the channels (eps 1e-12) unless raw
+__device__ __forceinline__ void decode(const float* __restrict__ p, int plane, int at, int raw, float n[3]) {
+  for (int c = 0; c < 3; ++c) n[c] = 2.f * p[c * plane + at] - 1.f;
+  if (!raw) {
+    float ss = n[0] * n[0];
+    ss += n[1] * n[1];
+    ss += n[2] * n[2];
+    const float d = fmaxf(sqrtf(ss), 1e-12f);
+    for (int c = 0; c < 3; ++c) n[c] = n[c] / d;
+  }
+}
 
 // bpp: bytes per pixel of the output, 3 (uint8 triples at any byte) or 4 (dword stores)
 inline bool out_ok(const dptx_image_desc& d, int bpp) {

@@ -100,6 +100,10 @@ ABI = [
     ("dptx_tta_depth_workspace_bytes", C.c_int, [_vp, _i32, _vp, _i32, _i64p]),
     ("dptx_tta_align_depth", C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, C.c_int64, _vp]),
     ("dptx_tta_merge_depth", C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    ("dptx_tile_blend_normals", C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    ("dptx_tile_depth_workspace_bytes", C.c_int, [_vp, _vp, _i32, _i64p]),
+    ("dptx_tile_align_depth", C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_tile_blend_depth", C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     ("dptx_postprocess_resize_workspace_bytes", C.c_int, [_i32, _i32, _i64p]),
     ("dptx_postprocess_resize_batch", C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
     ("dptx_refocus_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64p]),

@@ -594,3 +594,125 @@ def merge_depth_views_gpu(maps: torch.Tensor, views, sizes, coeffs=None, ws=None
     if output == "rgba":
         res = [depths_to_rgba_gpu(m[None])[0] for m in res]
     return res
+
+
+# ------------------------------------------------------------------ tiled inference (tiles.hip; omnidata_amd/tiled.py states the protocol)
+TILE_MAX_AXIS = 64           # include/dptx.h DPTX_TILE_MAX_AXIS: tiles per axis
+
+
+class TileGrid(_C.Structure):
+    """include/dptx.h dptx_tile_grid: one per image.  make() fills it from Python lists."""
+    _fields_ = [("offset", _C.c_int64), ("anchor_offset", _C.c_int64), ("h", _C.c_int32), ("w", _C.c_int32), ("ch", _C.c_int32),
+                ("cw", _C.c_int32), ("ny", _C.c_int32), ("nx", _C.c_int32), ("ramp_y", _C.c_int32), ("ramp_x", _C.c_int32),
+                ("ah", _C.c_int32), ("aw", _C.c_int32), ("y0", _C.c_int32 * 64), ("x0", _C.c_int32 * 64)]
+
+    @classmethod
+    def make(cls, offset, net_hw, window_hw, ys, xs, ramps=(0, 0), anchor_offset=-1, anchor_hw=(0, 0)):
+        """offset / anchor_offset: bytes into maps; net_hw (h, w); window_hw (ch, cw); ys / xs: the starts; ramps (ramp_y, ramp_x)."""
+        ys, xs = [int(v) for v in ys], [int(v) for v in xs]
+        if not (1 <= len(ys) <= TILE_MAX_AXIS and 1 <= len(xs) <= TILE_MAX_AXIS):
+            raise ValueError(f"a grid has 1..{TILE_MAX_AXIS} tiles per axis, not {len(ys)} x {len(xs)}")
+        g = cls(int(offset), int(anchor_offset), int(net_hw[0]), int(net_hw[1]), int(window_hw[0]), int(window_hw[1]), len(ys), len(xs),
+                int(ramps[0]), int(ramps[1]), int(anchor_hw[0]), int(anchor_hw[1]))
+        g.y0[:len(ys)] = ys
+        g.x0[:len(xs)] = xs
+        return g
+
+    @property
+    def tiles(self) -> int:
+        return self.ny * self.nx
+
+
+def _check_tile_maps(maps, grids, sizes, channels, anchors=False):
+    from ._native import check_cuda
+    check_cuda("maps", maps)
+    if maps.dtype != torch.float32 or not maps.is_contiguous():
+        raise ValueError("maps must be a contiguous fp32 tensor")
+    grids = list(grids)
+    sizes = [(int(H), int(W)) for H, W in sizes]
+    if len(grids) != len(sizes):
+        raise ValueError(f"{len(sizes)} images but {len(grids)} grids")
+    for g in grids:
+        if g.offset < 0 or g.offset + 4 * channels * g.h * g.w * g.ny * g.nx > maps.numel() * 4:
+            raise ValueError("a grid's tiles lie outside maps")
+        if anchors and (g.anchor_offset < 0 or g.anchor_offset + 4 * g.ah * g.aw > maps.numel() * 4):
+            raise ValueError("a grid's anchor lies outside maps")
+    return grids, sizes
+
+
+def blend_normal_tiles_gpu(maps: torch.Tensor, grids, sizes, normalize_views: bool = True, output: str = "u8"):
+    """The blend of tiled inference for surface normals (dptx_tile_blend_normals), one call: maps is ONE fp32 cuda tensor that holds
+    every tile's [3,h,w] map, an image's tiles contiguous in grid order from grids[i].offset (bytes); grids: one TileGrid per
+    image; sizes [(H, W)] per image.  Every tile is decoded (2m - 1), normalised at its own resolution (normalize_views), resized
+    into its window and weighted with the feathered ramp of include/dptx.h; the weighted sum is normalised again and encoded.
+    -> list of device tensors (views of one packed buffer): [H,W,3] uint8 (output "u8") or [3,H,W] fp32 ("f32")."""
+    from ._native import call
+    grids, sizes = _check_tile_maps(maps, grids, sizes, 3)
+    if output not in ("u8", "f32"):
+        raise ValueError('output must be "u8" or "f32"')
+    if not sizes:
+        return []
+    mode = "normal_u8" if output == "u8" else "normal_f32"
+    descs, total = output_layout(sizes, mode)
+    code = RESIZE_MODES[mode] | (0 if normalize_views else TTA_RAW_VIEWS)
+    out = torch.empty(max(total, 16), dtype=torch.uint8, device=maps.device)
+    arr = (TileGrid * len(grids))(*grids)
+    with torch.cuda.device(maps.device):
+        call("dptx_tile_blend_normals", maps.data_ptr(), _C.addressof(arr), _C.addressof(descs), len(sizes), code, out.data_ptr(),
+             torch.cuda.current_stream().cuda_stream)
+    res = []
+    for d, (H, W) in zip(descs, sizes):
+        if output == "u8":
+            res.append(out[d.offset:d.offset + H * W * 3].view(H, W, 3))
+        else:
+            res.append(out[d.offset:d.offset + 12 * H * W].view(torch.float32).view(3, H, W))
+    return res
+
+
+def align_depth_tiles_gpu(maps: torch.Tensor, grids, sizes):
+    """The alignment step of tiled depth inference (dptx_tile_align_depth), one call: every tile of every grid is fitted to its
+    image's anchor -- the whole image's [1,ah,aw] map at grids[i].anchor_offset -- by the least squares of align_depth_views_gpu
+    (the same device code, the same bits).  -> coeffs [tiles of all images, 2] cuda fp32 (scale, shift), image-major, an image's
+    tiles in grid order."""
+    from ._native import call
+    grids, sizes = _check_tile_maps(maps, grids, sizes, 1, anchors=True)
+    if not sizes:
+        raise ValueError("no image")
+    descs, _ = output_layout(sizes, "depth_f32")
+    arr = (TileGrid * len(grids))(*grids)
+    nbytes = _C.c_int64()
+    call("dptx_tile_depth_workspace_bytes", _C.addressof(arr), _C.addressof(descs), len(sizes), _C.byref(nbytes))
+    ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=maps.device)
+    coeffs = torch.empty(sum(g.tiles for g in grids), 2, dtype=torch.float32, device=maps.device)
+    with torch.cuda.device(maps.device):
+        call("dptx_tile_align_depth", maps.data_ptr(), _C.addressof(arr), _C.addressof(descs), len(sizes), coeffs.data_ptr(),
+             ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    return coeffs
+
+
+def blend_depth_tiles_gpu(maps: torch.Tensor, grids, sizes, coeffs=None, output: str = "f32"):
+    """The blend of tiled depth inference (dptx_tile_blend_depth), one call: every tile is clamped to [0, 1] at its own resolution,
+    resized into its window, mapped by its coefficients (scale * r + shift; coeffs as align_depth_tiles_gpu returned them, None =
+    unaligned, for comparison) and weighted with the feathered ramp; sum / weight sum, clamp(0, 1), 1 - x.  The anchors are not
+    blended.  -> list of device tensors: [H,W] fp32 (output "f32", views of one packed buffer) or [H,W,4] uint8 ("rgba": viridis
+    over the map's own range, as the full-frame depth path writes)."""
+    from ._native import call, check_cuda
+    grids, sizes = _check_tile_maps(maps, grids, sizes, 1)
+    if output not in ("f32", "rgba"):
+        raise ValueError('output must be "f32" or "rgba"')
+    if not sizes:
+        return []
+    if coeffs is not None:
+        check_cuda("coeffs", coeffs)
+        if coeffs.dtype != torch.float32 or not coeffs.is_contiguous() or tuple(coeffs.shape) != (sum(g.tiles for g in grids), 2):
+            raise ValueError("coeffs must be a contiguous fp32 tensor [tiles, 2]")
+    descs, total = output_layout(sizes, "depth_f32")
+    out = torch.empty(max(total, 16), dtype=torch.uint8, device=maps.device)
+    arr = (TileGrid * len(grids))(*grids)
+    with torch.cuda.device(maps.device):
+        call("dptx_tile_blend_depth", maps.data_ptr(), _C.addressof(arr), coeffs.data_ptr() if coeffs is not None else None,
+             _C.addressof(descs), len(sizes), RESIZE_MODES["depth_f32"], out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    res = [out[d.offset:d.offset + 4 * H * W].view(torch.float32).view(H, W) for d, (H, W) in zip(descs, sizes)]
+    if output == "rgba":
+        res = [depths_to_rgba_gpu(m[None])[0] for m in res]
+    return res
