@@ -290,3 +290,164 @@ def attention_planes(x, mode):
     dt, pl = ATT_PLANES[mode]
     hi = x.float().to(dt)
     return hi, ((x.float() - hi.float()).to(dt) if pl == 2 else None)
+
+
+# ------------------------------------------------------------------ GEMMs and convolutions, judged element by element
+# One error number per tensor (rel_err against max |ref|) lets a store that truncates instead of rounding pass (2^-7 |y| is
+# 3.9e-3 of the largest element, under the 6e-3 bar), and lets every row 100x smaller than the largest be wholly wrong.  The
+# helpers below give operands whose rows and columns carry scales of their own, an fp64 reference together with the magnitude
+# sum S that an accumulation error is relative to, and the bar on every single element.  Pure torch, any device.
+
+GEMM_MODES = ATT_MODES
+GEMM_PLANES = ATT_PLANES
+GEMM_U = ATT_U
+# fp32 floor: the largest |y32 - y| / S over (300, 64, 64), (515, 256, 768), (260, 128, 3072), (200, 256, 6912) x {bf16, fp16}
+# operands of scaled_gemm_operands (seed 0), y32 = A W^T + bias + R evaluated in plain fp32 on a CPU, y and S from gemm_ref64.
+# The largest was fp16 at (300, 64, 64): 1.65e-7 with these operands, 1.8e-7 with another draw of the same family -- the
+# constant is the larger; every K from 64 to 6912 lay between 5e-8 and that.  Measured against the reference, never against
+# a kernel; tests/test_gemm_bound_host.py re-measures it (profiles/gemm_elements.md).
+GEMM_F32_FLOOR_MEASURED = 1.8e-7
+GEMM_F32_FLOOR_FACTOR = 4.0   # the MFMA's accumulation order differs from a CPU's (attention uses the same margin)
+GEMM_HOST_SHAPES = ((300, 64, 64), (515, 256, 768), (260, 128, 3072), (200, 256, 6912))
+
+
+def _row_exp(n):
+    """e_m = (7 m mod 13) - 6 for m < n: over [-6, 6], adjacent values differ by 7 or 6."""
+    return ((7 * torch.arange(n)) % 13 - 6).double()
+
+
+def _col_exp(n):
+    """f_n = (5 n mod 7) - 3 for n < n: over [-3, 3], adjacent values differ by 5 or 2."""
+    return ((5 * torch.arange(n)) % 7 - 3).double()
+
+
+def scaled_gemm_operands(M, N, K, seed=0):
+    """A [M, K], W [N, K], bias [N], R [M, N] in fp64 (CPU), deterministic in `seed`: the caller rounds them to the type or
+    splits them into planes (PlaneArena.put).
+      A[m, :] = 2^e_m N(0, 1), e_m = (7 m mod 13) - 6;  W[n, :] = K^-1/2 2^f_n N(0, 1), f_n = (5 n mod 7) - 3;
+      bias[n] = 2^f_n N(0, 1);  R[m, n] = 2^(e_m + f_n) N(0, 1).
+    Adjacent rows and adjacent columns differ in scale by 2^2 at least.  max |A W^T + bias + R| < 60000 (asserted; ~2.8e3)."""
+    g = torch.Generator().manual_seed(2000 + seed)
+    se, sf = torch.exp2(_row_exp(M)), torch.exp2(_col_exp(N))
+    A = torch.randn(M, K, generator=g, dtype=torch.float64) * se[:, None]
+    W = torch.randn(N, K, generator=g, dtype=torch.float64) * sf[:, None] * K ** -0.5
+    bias = torch.randn(N, generator=g, dtype=torch.float64) * sf
+    R = torch.randn(M, N, generator=g, dtype=torch.float64) * se[:, None] * sf[None, :]
+    assert float((A @ W.t() + bias + R).abs().max()) < 60000.0
+    return A, W, bias, R
+
+
+def scaled_conv_operands(B, H, W, Cin, Cout, k, seed=0, Ho=None, Wo=None):
+    """X [B, H, W, Cin] NHWC, Wt [Cout, k, k, Cin], bias [Cout], R [B, Ho, Wo, Cout] (Ho, Wo default to H, W) in fp64 (CPU).
+    The scale of X[b, y, x, :] follows the flat pixel index p over the whole batch, 2^((7 p mod 13) - 6); weight rows and the
+    bias follow f_n with K = k k Cin; R follows (flat output pixel) x channel.  |values| < 2^6 * 6 sigma: inside fp16."""
+    g = torch.Generator().manual_seed(3000 + seed)
+    Ho, Wo = H if Ho is None else Ho, W if Wo is None else Wo
+    sf = torch.exp2(_col_exp(Cout))
+    X = torch.randn(B, H, W, Cin, generator=g, dtype=torch.float64) * torch.exp2(_row_exp(B * H * W)).view(B, H, W, 1)
+    Wt = torch.randn(Cout, k, k, Cin, generator=g, dtype=torch.float64) * sf.view(-1, 1, 1, 1) * (k * k * Cin) ** -0.5
+    bias = torch.randn(Cout, generator=g, dtype=torch.float64) * sf
+    R = torch.randn(B, Ho, Wo, Cout, generator=g, dtype=torch.float64) * torch.exp2(_row_exp(B * Ho * Wo)).view(B, Ho, Wo, 1) * sf
+    return X, Wt, bias, R
+
+
+def gemm_operand_planes(x, mode):
+    """(hi, lo) 16-bit planes of values x as PlaneArena.put splits them (through fp32); lo is None for the one-plane modes."""
+    return attention_planes(x, mode)
+
+
+def epilogue_ref64(acc, Sacc, bias, R, act):
+    """y = act(acc + bias) + R and S = Sacc + |bias| + |R| (fp64); act 0 none, 1 ReLU, 2 erf-GELU."""
+    y, S = acc, Sacc
+    if bias is not None:
+        y, S = y + bias.double(), S + bias.double().abs()
+    if act == 1:
+        y = torch.relu(y)
+    elif act == 2:
+        y = torch.nn.functional.gelu(y)
+    if R is not None:
+        y, S = y + R.double(), S + R.double().abs()
+    return y, S
+
+
+def gemm_ref64(A, W, bias=None, R=None, act=0):
+    """fp64 (y, S) of the values the kernel reads (hi + lo for the plane modes, the hi plane where only that is read):
+    y = act(A W^T + bias) + R, the final value; S = sum_k |a_k| |w_k| + |bias| + |R|, what a rounding of any term of the sum is
+    relative to."""
+    A, W = A.double(), W.double()
+    return epilogue_ref64(A @ W.t(), A.abs() @ W.abs().t(), bias, R, act)
+
+
+def conv_acc64(X, Wt, stride=1, pad_t=0, pad_l=0, Ho=None, Wo=None, a_relu=0):
+    """(conv(x', w), conv(|x'|, |w|)) in fp64, NHWC: X [B, H, W, Cin], Wt [Cout, k, k, Cin], zero padding pad_t rows above and
+    pad_l columns left, below and right whatever (Ho, Wo) leave over, x' = relu(x) when a_relu.  One matrix product per tap:
+    no backend's convolution is involved."""
+    X, Wt = X.double(), Wt.double()
+    if a_relu:
+        X = torch.relu(X)
+    B, H, W_, Cin = X.shape
+    Cout, k = Wt.shape[0], Wt.shape[1]
+    Ho = (H + 2 * pad_t - k) // stride + 1 if Ho is None else Ho
+    Wo = (W_ + 2 * pad_l - k) // stride + 1 if Wo is None else Wo
+    pb = max((Ho - 1) * stride + k - H - pad_t, 0)
+    pr = max((Wo - 1) * stride + k - W_ - pad_l, 0)
+    Xp = torch.nn.functional.pad(X, [0, 0, pad_l, pr, pad_t, pb])
+    assert Xp.shape[1] >= (Ho - 1) * stride + k and Xp.shape[2] >= (Wo - 1) * stride + k
+    acc = torch.zeros(B, Ho, Wo, Cout, dtype=torch.float64, device=X.device)
+    Sacc = torch.zeros_like(acc)
+    for ky in range(k):
+        for kx in range(k):
+            win = Xp[:, ky:ky + (Ho - 1) * stride + 1:stride, kx:kx + (Wo - 1) * stride + 1:stride, :]
+            w = Wt[:, ky, kx, :].t()
+            acc += win @ w
+            Sacc += win.abs() @ w.abs()
+    return acc, Sacc
+
+
+def conv_ref64(X, Wt, bias=None, R=None, stride=1, pad_t=0, pad_l=0, Ho=None, Wo=None, a_relu=0, act=0):
+    """fp64 (y, S) of an NHWC convolution of the values the kernel reads (conv_acc64 has the geometry):
+    y = act(conv(x', w) + bias) + R [B, Ho, Wo, Cout], S = conv(|x'|, |w|) + |bias| + |R|."""
+    return epilogue_ref64(*conv_acc64(X, Wt, stride, pad_t, pad_l, Ho, Wo, a_relu), bias, R, act)
+
+
+def gemm_elem_bound(mode, y, S, act, c_fp32=False, planes=None):
+    """Elementwise bar on |got - y| of a GEMM / convolution output; u = 2^-8 (bf16) / 2^-11 (fp16) the unit roundoff and
+    F = GEMM_F32_FLOOR_FACTOR x GEMM_F32_FLOOR_MEASURED = 7.2e-7 the fp32 floor (accumulation order, bias and residual adds).
+
+      one 16-bit plane       u |y| + F S      the stored value is the nearest 16-bit number
+      fp32 (c_fp32)          F S              (u^2 + F) S in the plane modes: their product drops lo * lo, at most u^2 |a| |w|
+                                              per term, whatever the output's type; nothing is split
+      hi / lo pair           (3 u^2 + F) S    the dropped lo * lo products, the split of the output, one spare
+      any fp16 plane         + 2^-25          a plane value below 2^-14 is subnormal
+      act == 2               F S -> 1.13 F S + 2e-6    1.13 = max |gelu'|; 2e-6 = twice the absolute error that
+                                                       tests/test_gelu_formula.py pins for the device formula
+    ReLU is 1-Lipschitz and changes nothing.  planes: how many planes the OUTPUT has where that is not the mode's own count
+    (the epi2 forms write a pair from a one-plane product; c_hi_only writes one plane from a two-plane kernel)."""
+    dt, pl = GEMM_PLANES[mode]
+    pl = pl if planes is None else planes
+    u = GEMM_U[mode]
+    F = GEMM_F32_FLOOR_FACTOR * GEMM_F32_FLOOR_MEASURED
+    floor = 1.13 * F * S + 2e-6 if act == 2 else F * S
+    if c_fp32:
+        return floor + u * u * S if GEMM_PLANES[mode][1] == 2 else floor
+    bound =u * y.abs() + floor if pl == 1 else 3.0 * u * u * S + floor
+    if dt == torch.float16:
+        bound = bound + 2.0 ** -25
+    return bound
+
+
+def elements_outside(got, y, bound):
+    """(worst |got - y| / bound, indices of the first five elements outside the bound -- a NaN is outside)."""
+    err = (got.double() - y).abs()
+    bad = ~(err <= bound)
+    worst = float((err / bound).nan_to_num(nan=float("inf")).max())
+    return worst, torch.nonzero(bad)[:5].tolist()
+
+
+def assert_elements_inside(got, y, bound, what):
+    """Every element of `got` within `bound` of y: prints the worst |err| / bound, and on failure the first offending
+    (row, column) / (image, y, x, channel) indices.  Returns the worst ratio."""
+    worst, bad = elements_outside(got, y, bound)
+    print(f"\n[elements] {what}: worst |err| / bound {worst:.3f}")
+    assert not bad, f"{what}: worst |err| / bound {worst:.3f}, first elements outside {bad}"
+    return worst

@@ -1,5 +1,6 @@
 """Op-level parity of every HIP kernel against a plain PyTorch fp32 reference of the same op on
-the same (already 16-bit-rounded) inputs.  Run on an MI355X: pytest -m gpu."""
+the same (already 16-bit-rounded) inputs.  Run on an MI355X: pytest -m gpu.
+The GEMMs and convolutions are judged element by element against fp64 in tests/test_gpu_gemm_elements.py."""
 import math
 import os
 
