@@ -17,7 +17,9 @@ files as with --full_frame; --task depth --tta NAME --tta_align lstsq: the same 
 anchor view by least squares before the merge, omnidata_amd/tta.py DepthTTA, DPT backbones only), --tiled [--tile_size 384
 --tile_scale 1.0 --tile_overlap 0.25] (tiled high-resolution inference, omnidata_amd/tiled.py: overlapping tiles at the chosen pixel
 scale, blended with feathered weights; depth tiles are aligned to a whole-image anchor; files as with --full_frame; excludes
---full_frame and --tta).  The forward runs on an MI355X through libdptx.so; no CPU fallback.
+--full_frame and --tta), --guided [--guided_radius 2 --guided_sigma_space 1.0 --guided_sigma_range 0.1] (with --full_frame: the map
+goes to the image's own size through a joint bilateral filter guided by the image itself instead of the plain bilinear / bicubic
+resize, so object boundaries land where the image has them; one forward per image, include/dptx.h "Guided upsampling").  The forward runs on an MI355X through libdptx.so; no CPU fallback.
 """
 import argparse
 import glob
@@ -60,6 +62,12 @@ def main(argv=None):
     parser.add_argument("--tile_size", type=int, default=384, help="--tiled: the network's short side for a tile")
     parser.add_argument("--tile_scale", type=float, default=1.0, help="--tiled: image pixels per network pixel along a tile's side")
     parser.add_argument("--tile_overlap", type=float, default=0.25, help="--tiled: the blend ramp as a fraction of the window, 0 .. 0.5")
+    parser.add_argument("--guided", action="store_true",
+                        help="--full_frame: guided upsampling to the image's own size (joint bilateral filter on the image) "
+                             "instead of the bilinear / bicubic resize")
+    parser.add_argument("--guided_radius", type=int, default=2, help="--guided: (2 * radius)^2 low-resolution taps per pixel, 1 .. 3")
+    parser.add_argument("--guided_sigma_space", type=float, default=1.0, help="--guided: spatial sigma in low-resolution pixels")
+    parser.add_argument("--guided_sigma_range", type=float, default=0.1, help="--guided: colour sigma in [0, 1] units")
     args = parser.parse_args(argv)
 
     if args.task not in ("normal", "depth"):
@@ -82,6 +90,12 @@ def main(argv=None):
         sys.exit()
     if args.tiled and not (0 <= args.tile_overlap <= 0.5 and args.tile_size >= 1 and args.tile_scale > 0):
         print("--tiled needs --tile_size >= 1, --tile_scale > 0 and --tile_overlap in [0, 0.5]")
+        sys.exit()
+    if args.guided and (args.full_frame is None or args.tta is not None or args.tiled):
+        print("--guided needs --full_frame and excludes --tta and --tiled")
+        sys.exit()
+    if args.guided and not (1 <= args.guided_radius <= 3 and args.guided_sigma_space > 0 and args.guided_sigma_range > 0):
+        print("--guided needs --guided_radius in 1 .. 3, --guided_sigma_space > 0 and --guided_sigma_range > 0")
         sys.exit()
     if args.backbone == "unet" and args.tiled and args.task == "depth":
         print("--backbone unet --task depth has no --tiled: the alignment is defined for the DPT depth models")
@@ -143,9 +157,12 @@ def main(argv=None):
             tiled = dict(tile=args.tile_size, scale=args.tile_scale, overlap=args.tile_overlap)
             if unet:
                 tiled.update(multiple=64, max_side=512)
+        guided = None
+        if args.guided:
+            guided = dict(radius=args.guided_radius, sigma_space=args.guided_sigma_space, sigma_range=args.guided_sigma_range)
         BatchPredictor(model, args.task, batch_size=max(args.batch_size, 1), full_frame=args.full_frame,
                        renormalize=args.renormalize, tta=args.tta, tta_merger=args.tta_merger,
-                       tta_options=tta_options, tta_align=args.tta_align, tiled=tiled).predict_to_dir(files, args.output_path, verbose=True)
+                       tta_options=tta_options, tta_align=args.tta_align, tiled=tiled, guided=guided).predict_to_dir(files, args.output_path, verbose=True)
         return
 
     def save_outputs(img_path, output_file_name):

@@ -395,6 +395,49 @@ int dptx_postprocess_resize_batch(const void* y_dev, int32_t B, int32_t C, int32
                                   int32_t mode, void* out_dev, const void* lut_dev, void* workspace, int64_t workspace_bytes,
                                   void* stream);
 
+/* ---- Guided upsampling: dptx_postprocess_resize_batch with edges where the image has them (DEVICE pointers unless stated) ----
+ * Joint bilateral upsampling (Kopf et al. 2007): every output pixel is a weighted mean of the low-resolution map values around
+ * it; the weights fall off with the distance and with the colour difference between the full-resolution image at the pixel and
+ * the low-resolution image at the tap.  Conventions as above: stream-ordered, the caller's workspace only, no allocation, no host
+ * synchronisation (graph-capturable), DPTX_E_INVALID before anything is launched; `guides`, `outs` and `params` are HOST data
+ * read before the call returns; no atomics, bitwise reproducible; an image's result does not depend on the batch.
+ *
+ * Inputs, per image i of a batch that shares the network shape h x w:
+ *   S     y_dev[i]: [C][h][w] fp32, already clamped to [0, 1] by the caller; C = 3 for the NORMAL modes, 1 for the DEPTH modes;
+ *   G_lo  guide_lo_dev[i]: [3][h][w] fp32 in [0, 1], the image as the network saw it;
+ *   G_hi  the image's own uint8 pixels at pixels_dev + guides[i].offset (C in {1, 3}, any row stride), g = u8 / 255 in fp32; a
+ *         grey image uses its one channel three times.  guides[i].H, W equal outs[i].H, W;
+ *   radius R in {1, 2, 3}, sigma_space > 0 in low-resolution pixels, sigma_range > 0 in [0, 1] colour units.  The host computes
+ *   ks = 1 / (2 sigma_space^2) and kr = 1 / (2 sigma_range^2) in double and rounds each once to fp32 (both must come out positive and finite).
+ * Output pixel (Y, X) of an H x W output; all arithmetic fp32, every operation rounded on its own (no contraction):
+ *   1. sy = (h / H) * (Y + 0.5) - 0.5 and sx likewise: ATen's align_corners=False coordinate with scale = in / out in fp32, not
+ *      clamped; by = floor(sy), bx = floor(sx).
+ *   2. Taps qy in {by - R + 1, ..., by + R}, qx in {bx - R + 1, ..., bx + R}; a tap outside [0, h) x [0, w) is skipped, not
+ *      replicated.  At least one tap is always inside.
+ *   3. e_q = ks * ((qy - sy)^2 + (qx - sx)^2) + kr * sum_c (G_hi[c](Y, X) - G_lo[c](qy, qx))^2, c = 0, 1, 2 in order.
+ *   4. e_min = the minimum over the valid taps; w_q = exp(-(e_q - e_min)): the largest weight is exactly 1 and the denominator
+ *      lies in [1, 4 R^2].
+ *   5. v_c = (sum_q w_q * S_c(q)) / sum_q w_q, both sums from 0 over the valid taps in (qy, qx) order.
+ *   6. The mode's steps, exactly those of dptx_postprocess_resize_batch behind its interpolation: the NORMAL modes optionally
+ *      DPTX_RESIZE_RENORM, then the clamp and the quantisation; DPTX_RESIZE_DEPTH_F32 clamp(0, 1), 1 - x; DPTX_RESIZE_DEPTH_RGBA
+ *      min / max over exactly the DEPTH_F32 values (64 partials per image through the workspace in a fixed order), then the LUT.
+ *   7. Inputs are assumed finite; non-finite ones neither fault nor hang and affect only the image they belong to.  The
+ *      definition is total for any h, w, H, W in range: an output smaller than the map is allowed.
+ * outs, out_dev, lut_dev, the workspace (16384 bytes for DPTX_RESIZE_DEPTH_RGBA, 0 otherwise; host-only) and the ranges are
+ * those of dptx_postprocess_resize_batch; guides as for dptx_preprocess_u8_rect_batch (C in {1, 3}, row_stride_bytes >= W*C).
+ * A guide whose H, W differ from its output's, C not in {1, 3}, a radius outside {1, 2, 3} or a sigma that is not positive
+ * is DPTX_E_INVALID. */
+typedef struct dptx_guided_params {
+  int32_t radius;     /* 1, 2 or 3: (2 * radius)^2 taps */
+  float sigma_space;  /* > 0, low-resolution pixels      */
+  float sigma_range;  /* > 0, colour units of [0, 1]     */
+} dptx_guided_params;
+int dptx_postprocess_guided_workspace_bytes(int32_t B, int32_t mode, int64_t* bytes);
+int dptx_postprocess_guided_batch(const void* y_dev, const void* guide_lo_dev, int32_t B, int32_t C, int32_t h, int32_t w,
+                                  const void* pixels_dev, const dptx_image_desc* guides, const dptx_image_desc* outs,
+                                  const dptx_guided_params* params, int32_t mode, void* out_dev, const void* lut_dev,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Test-time augmentation for surface normals: the merge of an image's views (no handle; DEVICE pointers unless stated) ----
  * The protocol of paper_code/oasis_eval_tta.py:440-448,487-534 (SurfaceNormalsTTAWrapper, MedianMerger): every view -- a window
  * of the image, possibly mirrored, at its own network size -- is mapped back into its window, and the views that cover a pixel

@@ -18,6 +18,11 @@ view by least squares before the merge) and writes <stem>_depth.png as RGBA at t
 tiled=True | {tile, scale, overlap, ...} runs tiled high-resolution inference instead (omnidata_amd/tiled.py: overlapping tiles of
 the image at the chosen pixel scale, blended with feathered weights; depth tiles are first aligned to a whole-image anchor): maps
 of the image's own size, files as in the full-frame modes.  It excludes full_frame and tta.
+
+guided=True | {radius, sigma_space, sigma_range} (with full_frame) replaces the last step, the plain bilinear / bicubic resize
+to the image's own size, by guided upsampling (pp.guided_outputs_gpu, dptx_postprocess_guided_batch): a joint bilateral filter
+whose guides are already on the device -- the uploaded uint8 pixels at full resolution and the network input at the map's.  One
+forward per image, edges where the image has them.  It excludes tta and tiled.
 """
 from __future__ import annotations
 
@@ -79,7 +84,8 @@ def plan_full_frame(sizes, mode: str, image_size: int = 384, batch_size: int = 3
 
 class BatchPredictor:
     def __init__(self, model, task: str, batch_size: int = 32, workers: int = 8, image_size: int = 384, full_frame=None,
-                 renormalize: bool = False, tta=None, tta_merger: str = "median", tta_options=None, tta_align=None, tiled=None):
+                 renormalize: bool = False, tta=None, tta_merger: str = "median", tta_options=None, tta_align=None, tiled=None,
+                 guided=None):
         if task not in ("normal", "depth"):
             raise ValueError("task should be one of the following: normal, depth")
         if batch_size < 1:
@@ -103,6 +109,12 @@ class BatchPredictor:
             raise ValueError("tiled excludes full_frame and tta")
         if tiled is not None and tiled is not True and not isinstance(tiled, dict):
             raise ValueError("tiled must be None, True or a dict of TiledNormals' / TiledDepth's options")
+        if guided is False:
+            guided = None
+        if guided is not None and (full_frame is None or tta is not None or tiled is not None):
+            raise ValueError("guided needs full_frame and excludes tta and tiled")
+        # None: the plain resize; else the keyword arguments of pp.guided_outputs_gpu
+        self.guided = None if guided is None else pp.guided_params({} if guided is True else guided)
         self.full_frame, self.renormalize = full_frame, bool(renormalize)
         self.capped = []   # full_frame="aspect": input indices of the last run whose network size was cut back to the supported range
         self.model, self.task, self.batch_size, self.image_size = model, task, int(batch_size), int(image_size)
@@ -160,6 +172,8 @@ class BatchPredictor:
     # ---- full frame: the whole image in, a map of the image's own size out
     def _run_full(self, images, net_hw):
         """-> list of device tensors, image i at its own size: normal [H,W,3] uint8, depth [H,W,4] uint8 (viridis RGBA)."""
+        if self.guided is not None:
+            return self._run_guided(images, net_hw)
         with torch.no_grad():
             x = pp.images_to_input_rect_gpu(images, self.task, net_hw, self.device)
             y = self.model(x).clamp(min=0, max=1)
@@ -167,6 +181,17 @@ class BatchPredictor:
             if self.task == "depth":
                 return pp.resize_outputs_gpu(y, sizes, "depth_rgba")
             return pp.resize_outputs_gpu(y, sizes, "normal_u8", self.renormalize)
+
+    def _run_guided(self, images, net_hw):
+        """_run_full with guided upsampling as the last step: the guides are the uploaded pixels and the network input (in
+        [0, 1]: the depth models take it normalised to [-1, 1])."""
+        with torch.no_grad():
+            x, pixels, descs = pp.images_to_input_rect_gpu(images, self.task, net_hw, self.device, return_pixels=True)
+            y = self.model(x).clamp(min=0, max=1)
+            guide_lo = x * 0.5 + 0.5 if self.task == "depth" else x
+            sizes = [_size_of(im)[::-1] for im in images]
+            mode = "depth_rgba" if self.task == "depth" else "normal_u8"
+            return pp.guided_outputs_gpu(y, guide_lo, pixels, descs, sizes, mode, self.renormalize, **self.guided)
 
     def _full_chunks(self, items, pool):
         """Yields (input indices, decoded images, outputs) per chunk of plan_full_frame(), in the plan's order; the next chunk is

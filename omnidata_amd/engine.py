@@ -106,6 +106,9 @@ ABI = [
     ("dptx_tile_blend_depth", C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     ("dptx_postprocess_resize_workspace_bytes", C.c_int, [_i32, _i32, _i64p]),
     ("dptx_postprocess_resize_batch", C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_postprocess_guided_workspace_bytes", C.c_int, [_i32, _i32, _i64p]),
+    ("dptx_postprocess_guided_batch", C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, C.c_int64,
+                                                _vp]),
     ("dptx_refocus_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64p]),
     ("dptx_refocus_quantiles", C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
     ("dptx_refocus", C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),

@@ -334,9 +334,15 @@ def rect_supported(img, net_hw) -> bool:
     return 1 <= h <= min(MAX_SIDE, MAX_SCALE * OH) and 1 <= w <= min(MAX_SIDE, MAX_SCALE * OW)
 
 
-def images_to_input_rect_gpu(images, task: str, net_hw, device="cuda:0") -> torch.Tensor:
+def _as_pil(img) -> Image.Image:
+    return img if isinstance(img, Image.Image) else Image.fromarray(np.asarray(img))
+
+
+def images_to_input_rect_gpu(images, task: str, net_hw, device="cuda:0", return_pixels: bool = False):
     """[B,3,OH,OW] fp32 on `device`: image_to_input_rect() of every image (bit-identical), from ONE host->device copy of the raw
-    pixels and one ragged-batch resize on the GPU.  Images the kernel does not take go through PIL into their slot."""
+    pixels and one ragged-batch resize on the GPU.  Images the kernel does not take go through PIL into their slot.
+    return_pixels=True -> (x, pixels_dev, descs): also the uploaded uint8 pixel buffer and the ImageDesc array of ALL B images in
+    input order, for guided_outputs_gpu; an image that takes the PIL path is packed as img.convert("RGB").  x is the same."""
     from ._native import call, workspace
     images = list(images)
     OH, OW = int(net_hw[0]), int(net_hw[1])
@@ -344,11 +350,19 @@ def images_to_input_rect_gpu(images, task: str, net_hw, device="cuda:0") -> torc
     device = torch.device(device)
     x = torch.empty(B, 3, OH, OW, dtype=torch.float32, device=device)
     if B == 0:
-        return x
+        return (x, torch.empty(16, dtype=torch.uint8, device=device), (ImageDesc * 1)()) if return_pixels else x
     fast = [i for i, im in enumerate(images) if rect_supported(im, (OH, OW))]
     slow = sorted(set(range(B)) - set(fast))
-    if fast:
+    dev = all_descs = None
+    if return_pixels:   # one buffer with every image; the resize reads the descriptors of the images it takes
+        buf, all_descs = pack_images([_as_pil(im).convert("RGB") if i in slow else im for i, im in enumerate(images)])
+        descs = (ImageDesc * max(len(fast), 1))(*[all_descs[i] for i in fast])
+        if not fast:
+            with torch.cuda.device(device):
+                dev = buf.to(device, non_blocking=True)
+    elif fast:
         buf, descs = pack_images([images[i] for i in fast])
+    if fast:
         ws = workspace("dptx_preprocess_rect_batch_workspace_bytes", device, (min(len(fast), 4096), OH, OW),
                        f"network size {(OH, OW)}: both sides must be multiples of 32 in [64, 1024]")
         with torch.cuda.device(device):
@@ -363,9 +377,8 @@ def images_to_input_rect_gpu(images, task: str, net_hw, device="cuda:0") -> torc
             if not direct:
                 x[torch.tensor(fast, device=device)] = xf
     for i in slow:
-        im = images[i] if isinstance(images[i], Image.Image) else Image.fromarray(np.asarray(images[i]))
-        x[i:i + 1] = image_to_input_rect(im, task, (OH, OW)).to(device)
-    return x
+        x[i:i + 1] = image_to_input_rect(_as_pil(images[i]), task, (OH, OW)).to(device)
+    return (x, dev, all_descs) if return_pixels else x
 
 
 def output_layout(sizes, mode: str):
@@ -419,6 +432,11 @@ def resize_outputs_gpu(y: torch.Tensor, sizes, mode: str, renormalize: bool = Fa
             n = min(4096, B - b0)
             call("dptx_postprocess_resize_batch", y[b0:].data_ptr(), n, y.shape[1], h, w,
                  _C.addressof(descs) + b0 * _C.sizeof(ImageDesc), code, out.data_ptr(), lut_ptr, ws_ptr, ws_n, stream)
+    return _output_views(out, descs, sizes, mode)
+
+
+def _output_views(out: torch.Tensor, descs, sizes, mode: str):
+    """The outputs inside the packed buffer that output_layout() describes, as tensors."""
     res = []
     for d, (H, W) in zip(descs, sizes):
         if mode == "normal_u8":
@@ -430,6 +448,98 @@ def resize_outputs_gpu(y: torch.Tensor, sizes, mode: str, renormalize: bool = Fa
         else:
             res.append(out[d.offset:d.offset + 4 * H * W].view(H, W, 4))
     return res
+
+
+# ------------------------------------------------------------------ guided upsampling (guided.hip)
+class GuidedParams(_C.Structure):
+    """include/dptx.h dptx_guided_params."""
+    _fields_ = [("radius", _C.c_int32), ("sigma_space", _C.c_float), ("sigma_range", _C.c_float)]
+
+
+def guided_params(options=None) -> dict:
+    """-> {radius, sigma_space, sigma_range} with the defaults (2, 1.0, 0.1) filled in; ValueError for an unknown name, a radius
+    outside {1, 2, 3} or a sigma that is not a positive finite number."""
+    p = dict(radius=2, sigma_space=1.0, sigma_range=0.1)
+    if not isinstance(options or {}, dict) or set(options or {}) - set(p):
+        raise ValueError("guided must be None, True or a dict of radius, sigma_space, sigma_range")
+    p.update(options or {})
+    if isinstance(p["radius"], bool) or p["radius"] not in (1, 2, 3):
+        raise ValueError("guided: radius must be 1, 2 or 3")
+    for name in ("sigma_space", "sigma_range"):
+        v = p[name]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0 < v < math.inf):
+            raise ValueError(f"guided: {name} must be a positive number")
+    return dict(radius=int(p["radius"]), sigma_space=float(p["sigma_space"]), sigma_range=float(p["sigma_range"]))
+
+
+def guided_outputs_gpu(y: torch.Tensor, guide_lo: torch.Tensor, pixels_dev: torch.Tensor, descs, sizes, mode: str,
+                       renormalize: bool = False, radius: int = 2, sigma_space: float = 1.0, sigma_range: float = 0.1):
+    """resize_outputs_gpu with guided (joint bilateral, Kopf et al. 2007) upsampling instead of the plain interpolation: the same
+    arguments y, sizes, mode, renormalize and the same list of views, output i at its own size H x W.
+
+    y [B,3,h,w] (normal_*) or [B,h,w] / [B,1,h,w] (depth_*), already clamped to [0, 1]; guide_lo [B,3,h,w] in [0, 1]: the image as
+    the network saw it (the network input x for normals, x * 0.5 + 0.5 for depth); pixels_dev / descs: the packed uint8 pixels on
+    the device and their ImageDesc (pack_images; images_to_input_rect_gpu(..., return_pixels=True)), image i of size sizes[i], one
+    or three channels (a grey image counts three times), g = u8 / 255.
+
+    Output pixel (Y, X), all in fp32, every operation rounded on its own:
+      sy = (h / H) * (Y + 0.5) - 0.5, sx likewise (ATen's align_corners=False coordinate, not clamped); by, bx = their floors;
+      taps qy in by - R + 1 .. by + R, qx in bx - R + 1 .. bx + R, those outside the map skipped (at least one is inside);
+      e_q = ks * ((qy - sy)^2 + (qx - sx)^2) + kr * sum_c (G_hi[c](Y, X) - G_lo[c](qy, qx))^2 with ks = 1 / (2 sigma_space^2),
+      kr = 1 / (2 sigma_range^2); w_q = exp(-(e_q - min e)), so the largest weight is 1;
+      v_c = sum_q w_q * S_c(q) / sum_q w_q in (qy, qx) order; then the mode's steps of resize_outputs_gpu (renormalize, clamp and
+      quantisation; depth: clamp, 1 - x; depth_rgba: viridis over the map's own range).
+    radius R in {1, 2, 3}, sigma_space in low-resolution pixels, sigma_range in [0, 1] colour units.  include/dptx.h ("Guided
+    upsampling") is the full statement.  One entry-point call per 4096 outputs; bitwise reproducible, independent of the batch."""
+    from ._native import call, check_cuda, workspace
+    check_cuda("y", y)
+    check_cuda("guide_lo", guide_lo)
+    check_cuda("pixels_dev", pixels_dev)
+    if mode not in RESIZE_MODES:
+        raise ValueError(f"mode must be one of {sorted(RESIZE_MODES)}")
+    normal = mode.startswith("normal")
+    if renormalize and not normal:
+        raise ValueError("renormalize applies to surface normals only")
+    params = GuidedParams(**guided_params(dict(radius=radius, sigma_space=sigma_space, sigma_range=sigma_range)))
+    h, w = y.shape[-2:]
+    y = y.detach().float().reshape(-1, 3 if normal else 1, h, w).contiguous()
+    B = y.shape[0]
+    if tuple(guide_lo.shape) != (B, 3, h, w):
+        raise ValueError(f"guide_lo must be [{B}, 3, {h}, {w}], the maps' resolution; got {tuple(guide_lo.shape)}")
+    guide_lo = guide_lo.detach().float().contiguous()
+    if pixels_dev.dtype != torch.uint8 or not pixels_dev.is_contiguous() or guide_lo.device != y.device or pixels_dev.device != y.device:
+        raise ValueError("pixels_dev must be a contiguous uint8 tensor, and the guides must be on the maps' device")
+    sizes = [(int(H), int(W)) for H, W in sizes]
+    if len(sizes) != B or len(descs) < B:
+        raise ValueError(f"{B} maps but {len(sizes)} sizes and {len(descs)} guide descriptors")
+    if B == 0:
+        return []
+    if any(not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE) for H, W in sizes):
+        raise ValueError(f"output sides must be in [1, {MAX_SIDE}]")
+    for i, (H, W) in enumerate(sizes):
+        d = descs[i]
+        if (d.H, d.W) != (H, W) or d.C not in (1, 3) or d.row_stride_bytes < d.W * d.C or d.offset < 0 or \
+                d.offset + (d.H - 1) * d.row_stride_bytes + d.W * d.C > pixels_dev.numel():
+            raise ValueError(f"guide {i}: a {d.H}x{d.W}x{d.C} image at offset {d.offset} does not describe {H}x{W} pixels inside pixels_dev")
+    outs, total = output_layout(sizes, mode)
+    code = RESIZE_MODES[mode] | (RESIZE_RENORM if renormalize else 0)
+    out = torch.empty(max(total, 16), dtype=torch.uint8, device=y.device)
+    lut_ptr = ws_ptr = ws_n = 0
+    if mode == "depth_rgba":
+        key = str(y.device)
+        lut = _lut_cache.get(key)
+        if lut is None:
+            lut = _lut_cache[key] = torch.from_numpy(viridis_lut()).to(y.device)
+        ws = workspace("dptx_postprocess_guided_workspace_bytes", y.device, (min(B, 4096), code), "unsupported mode")
+        lut_ptr, ws_ptr, ws_n = lut.data_ptr(), ws.data_ptr(), ws.numel()
+    with torch.cuda.device(y.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        for b0 in range(0, B, 4096):
+            n = min(4096, B - b0)
+            call("dptx_postprocess_guided_batch", y[b0:].data_ptr(), guide_lo[b0:].data_ptr(), n, y.shape[1], h, w,
+                 pixels_dev.data_ptr(), _C.addressof(descs) + b0 * _C.sizeof(ImageDesc), _C.addressof(outs) + b0 * _C.sizeof(ImageDesc),
+                 _C.addressof(params), code, out.data_ptr(), lut_ptr, ws_ptr, ws_n, stream)
+    return _output_views(out, outs, sizes, mode)
 
 
 # ------------------------------------------------------------------ test-time augmentation (fullframe.hip views entry, tta.hip, tta_depth.hip)
