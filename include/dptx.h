@@ -826,6 +826,9 @@ int dptx_op_conv_planes(int32_t dtype, const void* X, const void* Wt, const floa
  * Wt [64][176] 16-bit with k = (c*7 + ky)*8 + kx (kx = 7 and k >= 168 are zero).  H % 8 == 0, W % 128 == 0. */
 int dptx_op_stem_conv(int32_t dtype, const float* x, const void* Wt, void* y, int32_t B, int32_t H, int32_t W,
                       void* stream);
+/* The same with a caller image of element type io (DPTX_IO_FP32 / _BF16 / _FP16). */
+int dptx_op_stem_conv_io(int32_t dtype, const void* x, int32_t io, const void* Wt, void* y, int32_t B, int32_t H, int32_t W,
+                         void* stream);
 /* qkv[B*S,3*H*64] packed (which, head, dim) -> out[B*S,H*64]; softmax(q k^T / 8) v. */
 int dptx_op_attention(int32_t dtype, const void* qkv, void* out, int32_t B, int32_t S,
                       int32_t heads, void* stream);
@@ -868,7 +871,9 @@ int dptx_debug_arena_checksums(dptx_handle h, void* out_dev, int32_t capacity, v
  * schedule in the two-plane 128x128 kernel -- and of the streaming kernel for the small-K 1x1 convolutions -- 8: never take it,
  * 16: take it for every launch it can serve, not only in the shape classes it was adopted for -- and of the forward's
  * folding of norm3 into a second pass of that kernel -- 32: never (conv3, then the GroupNorm apply pass), 64: wherever the
- * folded form can run, not only in the shape classes it was adopted for.  Results do not depend on them. */
+ * folded form can run, not only in the shape classes it was adopted for -- and of the stem convolution and the x2 up-sampling --
+ * 128: both on their first kernels everywhere, 256: the strip form of the up-sampling wherever it can run, not only in the
+ * (H, C) classes it was adopted for.  Results do not depend on them. */
 int dptx_debug_set_gemm_flags(int32_t flags);
 /* NHWC conv on OCP e4m3 operands (the fp8 dtype's convolution): X8[B,H,W,Cin] and Wt8[Cout][k][k][Cin] are e4m3 bytes
  * (Cin % 128 == 0), fp32 accumulate on the block-scaled fp8 MFMA at unit scale; Y = act(out_scale * conv + bias) (+R) in
@@ -899,6 +904,9 @@ int dptx_op_conv_groupnorm_fused(int32_t dtype, const void* X, const void* Wt, c
 /* bilinear x2, align_corners=True, NHWC 16-bit. */
 int dptx_op_upsample2x(int32_t dtype, const void* X, void* Y, int32_t B, int32_t H, int32_t W,
                        int32_t C, void* stream);
+/* The strip form of that kernel alone (dtype 0 / 1): a thread emits `rows` (4 or 8) output rows from rows / 2 + 2 source rows. */
+int dptx_op_upsample2x_strip(int32_t dtype, const void* X, void* Y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t rows,
+                             void* stream);
 /* Dense GEMM with the consumer epilogue of the LayerNorm fold (what the qkv / fc1 launches run): C[M,N] (16-bit) =
  * act((A[M,K] W[N,K]^T - mu colsum) rstd + bias), with (mu, rstd) of row m combined from the (sum, sum of squares) records
  * ln_stats[m][0 .. ln_nblk) (float2, row stride 8 records; ln_nblk = K / 128 = 6 or 8) and ln_colsum[n] = sum_k W[n][k]. */

@@ -223,6 +223,43 @@ __device__ __forceinline__ float bilerp(float a, float b, float c, float d, floa
   return __fmaf_rn(ly1, t1, __fmul_rn(ly0, t0));
 }
 
+// The same association is separable as written: the inner sums are the horizontal blends of source rows y0 and y1.  A
+// kernel that emits several output rows per thread forms them once per source row (hblend) and every output row as one
+// vertical blend of two of them (vblend) -- bit-identical to bilerp(), 2.3x fewer VALU operations.
+template <int DT>
+__device__ __forceinline__ void unpack8(const u32x4_t v, float* f) {
+  f[0] = T16<DT>::tof((uint16_t)(v.x & 0xffffu)); f[1] = T16<DT>::tof((uint16_t)(v.x >> 16));
+  f[2] = T16<DT>::tof((uint16_t)(v.y & 0xffffu)); f[3] = T16<DT>::tof((uint16_t)(v.y >> 16));
+  f[4] = T16<DT>::tof((uint16_t)(v.z & 0xffffu)); f[5] = T16<DT>::tof((uint16_t)(v.z >> 16));
+  f[6] = T16<DT>::tof((uint16_t)(v.w & 0xffffu)); f[7] = T16<DT>::tof((uint16_t)(v.w >> 16));
+}
+template <int DT>
+__device__ __forceinline__ void hblend(const u32x4_t s0, const u32x4_t s1, float lx0, float lx1, float (&t)[8]) {
+  float a[8], b[8];
+  unpack8<DT>(s0, a);
+  unpack8<DT>(s1, b);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) t[e] = __fmaf_rn(lx1, b[e], __fmul_rn(lx0, a[e]));
+}
+template <int DT, bool PIN = false>
+__device__ __forceinline__ u32x4_t vblend(const float (&t0)[8], const float (&t1)[8], float ly0, float ly1) {
+  float o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    o[e] = __fmaf_rn(ly1, t1[e], __fmul_rn(ly0, t0[e]));
+    // fp16: the fp32-rounded blend is what gets rounded to 16 bits, as in bilerp() + store8f.  Where hipcc folds the fma and
+    // the conversion into v_fma_mixlo_f16 (it did in upsample2x_strip_kernel), the exact sum is rounded once and fp16 ties
+    // come out differently (T16<DT_FP16>::fromf has the same story): PIN keeps the fp32 value in a register of its own
+    if (PIN && DT == DT_FP16) asm("" : "+v"(o[e]));
+  }
+  u32x4_t r;
+  r.x = T16<DT>::pack2(o[0], o[1]);
+  r.y = T16<DT>::pack2(o[2], o[3]);
+  r.z = T16<DT>::pack2(o[4], o[5]);
+  r.w = T16<DT>::pack2(o[6], o[7]);
+  return r;
+}
+
 // erfc via Abramowitz & Stegun 7.1.28, erfc(z) = (1 + a1 z + ... + a6 z^6)^-16 for z >= 0 (|abs err| <= 3e-7; measured
 // 7.1e-7 on gelu over [-12, 12] in fp32, the same league as 7.1.26's 4.7e-7, which round 1-2 used): six fused
 // multiply-adds, four squarings and ONE quarter-rate instruction (v_rcp_f32) -- 7.1.26 needs v_rcp_f32 + v_exp_f32 and as

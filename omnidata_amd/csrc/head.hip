@@ -32,37 +32,8 @@ constexpr int HT_P_BYTES = HT_PR * HT_PC * 256;       // [row][col][16 chunks x 
 constexpr int HT_CONST_FLOATS = 32 + 3 * 32 + 4;      // bias2, w4 (<= 3 channels), bias4
 constexpr size_t HT_SMEM = HT_W_BYTES + HT_P_BYTES + HT_CONST_FLOATS * 4;
 
-template <int DT>
-__device__ __forceinline__ void unpack8(const u32x4_t v, float* f) {
-  f[0] = T16<DT>::tof((uint16_t)(v.x & 0xffffu)); f[1] = T16<DT>::tof((uint16_t)(v.x >> 16));
-  f[2] = T16<DT>::tof((uint16_t)(v.y & 0xffffu)); f[3] = T16<DT>::tof((uint16_t)(v.y >> 16));
-  f[4] = T16<DT>::tof((uint16_t)(v.z & 0xffffu)); f[5] = T16<DT>::tof((uint16_t)(v.z >> 16));
-  f[6] = T16<DT>::tof((uint16_t)(v.w & 0xffffu)); f[7] = T16<DT>::tof((uint16_t)(v.w >> 16));
-}
-
-// ATen's bilinear association ly0*(lx0*a + lx1*b) + ly1*(lx0*c + lx1*d) is separable as written: the inner sums are the
-// horizontal blends of source rows y0 and y1.  They are formed once per source row (hblend), and every window row is
-// one vertical blend of two of them (vblend) -- bit-identical to bilerp() in common.h, 2.3x fewer VALU operations.
-template <int DT>
-__device__ __forceinline__ void hblend(const u32x4_t s0, const u32x4_t s1, float lx0, float lx1, float (&t)[8]) {
-  float a[8], b[8];
-  unpack8<DT>(s0, a);
-  unpack8<DT>(s1, b);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) t[e] = __fmaf_rn(lx1, b[e], __fmul_rn(lx0, a[e]));
-}
-template <int DT, int J>
-__device__ __forceinline__ u32x4_t vblend(const float (&T)[6][8], float ly0, float ly1) {
-  float o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) o[e] = __fmaf_rn(ly1, T[J + 1][e], __fmul_rn(ly0, T[J][e]));
-  u32x4_t r;
-  r.x = T16<DT>::pack2(o[0], o[1]);
-  r.y = T16<DT>::pack2(o[2], o[3]);
-  r.z = T16<DT>::pack2(o[4], o[5]);
-  r.w = T16<DT>::pack2(o[6], o[7]);
-  return r;
-}
+// ATen's bilinear association ly0*(lx0*a + lx1*b) + ly1*(lx0*c + lx1*d) is separable as written: the source rows' horizontal
+// blends are formed once per source row (common.h hblend), and every window row is one vertical blend of two of them (vblend).
 
 template <int DT>
 __global__ __launch_bounds__(HT_THREADS) void head_tail_kernel(const uint16_t* __restrict__ H0, const uint16_t* __restrict__ W2,
@@ -157,11 +128,11 @@ __global__ __launch_bounds__(HT_THREADS) void head_tail_kernel(const uint16_t* _
           const int y0 = (int)sy;
           const float ly1 = sy - (float)y0, ly0 = 1.f - ly1;
           switch (y0 - ybase) {  // uniform over the block; slot j+1 holds row min(y0+1, Hs-1) = ATen's y1
-            case 0: o = vblend<DT, 0>(T, ly0, ly1); break;
-            case 1: o = vblend<DT, 1>(T, ly0, ly1); break;
-            case 2: o = vblend<DT, 2>(T, ly0, ly1); break;
-            case 3: o = vblend<DT, 3>(T, ly0, ly1); break;
-            default: o = vblend<DT, 4>(T, ly0, ly1); break;
+            case 0: o = vblend<DT>(T[0], T[1], ly0, ly1); break;
+            case 1: o = vblend<DT>(T[1], T[2], ly0, ly1); break;
+            case 2: o = vblend<DT>(T[2], T[3], ly0, ly1); break;
+            case 3: o = vblend<DT>(T[3], T[4], ly0, ly1); break;
+            default: o = vblend<DT>(T[4], T[5], ly0, ly1); break;
           }
         }
         *(u32x4_t*)(dst + r * (HT_PC * 256)) = o;

@@ -85,6 +85,7 @@ struct GemmParams {
   int debug_flags;   // debug (dptx_debug_set_gemm_flags): 1 = staged epilogue everywhere, 2 = one block per tile, 4 = lockstep two-plane 128x128 kernel,
                      // 8 = never take the streaming 1x1 kernel, 16 = take it wherever it can run (not only in the adopted classes),
                      // 32 / 64 = never / wherever eligible: the GroupNorm-epilogue schedule of the streaming kernel (read by the callers)
+                     // (128 / 256 are read by launch_stem_conv / launch_upsample2x through gemm_debug_flags())
   float a_rpi_rcp, wout_rcp;  // 1 / a_rpi, 1 / Wout (filled in by launch_gemm: row -> (image, y, x) without integer division)
   // conv1x1.hip, GroupNorm-epilogue form (launch_conv1x1_stream form C1_GN): the per-(image, channel) affines of
   // launch_gn_finalize, gn_tab[img][4][N] = (a, d, ra, rd); the epilogue stores act( x a + d + (R1 ? (gn_tab_rgn ? r ra + rd : r) : 0) )
@@ -107,7 +108,9 @@ void gemm_set_trace(long long* dev_buf);
 // debug / tests: 1 = no register-direct epilogue, 2 = no persistent launch, 4 = no two-plane ping-pong kernel, 8 = never take
 // the streaming 1x1 kernel, 16 = take it for every launch it can serve, also outside the classes it was adopted for, 32 = never
 // fold a GroupNorm into a second pass of the streaming kernel (conv1x1_gn_*: the schedule conv -> gn_apply), 64 = fold it
-// wherever that form can run, adopted or not (same results either way)
+// wherever that form can run, adopted or not (same results either way), 128 = the stem convolution and the x2 up-sampling on
+// their first kernels (stem_conv_kernel, upsample2x_kernel) everywhere, 256 = the strip form of the up-sampling wherever it can
+// run, not only in the classes it was adopted for (same results either way)
 void gemm_set_debug_flags(int flags);
 int gemm_debug_flags();
 // conv1x1.hip: the streaming kernel for dense / strided 1x1 convolutions with K = Cin in {64, 128, 256}, N % 64 == 0, one 16-bit
@@ -163,7 +166,8 @@ hipError_t launch_gn_relu_maxpool(int mode, const void* X, void* Y, const float*
                                   const float* partial, int B, int H, int W, int C, float eps, Planes pl, hipStream_t stream);
 
 // fused stem conv 7x7 s2 TF-SAME: x NCHW fp32 [B,3,H,W] -> y NHWC 16-bit [B,H/2,W/2,64]; Wt [64][176], k = (c*7+ky)*8 + kx
-// io: element type of x (common.h IO_*: fp32 / bf16 / fp16)
+// io: element type of x (common.h IO_*: fp32 / bf16 / fp16).  bf16 / fp16 modes run stem_conv_kernel_wp (wave-private 16-bit
+// staging, four blocks per CU; the same bits) unless debug flag 128 is set or x / Wt / y are not 16-byte aligned
 hipError_t launch_stem_conv(int mode, const void* x, int io, const void* Wt, void* y, int B, int H, int W, Planes pl,
                             hipStream_t stream);
 
@@ -171,6 +175,9 @@ hipError_t launch_stem_conv(int mode, const void* x, int io, const void* Wt, voi
 // Y8 (optional): e4m3 copy of the output times q_scale, 1 byte per element, for an fp8 convolution downstream
 hipError_t launch_upsample2x(int mode, const void* X, void* Y, int B, int H, int W, int C, Planes pl, hipStream_t stream,
                              void* Y8 = nullptr, float q_scale = 1.0f, bool out_hi_only = false);
+// the strip form alone (bf16 / fp16, no e4m3 copy): R = 4 or 8 output rows per thread.  launch_upsample2x takes it in the (H, C)
+// classes where it measured faster (debug flag 256: wherever it can run, 128: nowhere); the bits are upsample2x_kernel's
+hipError_t launch_upsample2x_strip(int mode, const void* X, void* Y, int B, int H, int W, int C, int R, hipStream_t stream);
 // fp8 calibration: atomicMax(*amax_bits, bits of max |x| (relu: max(x, 0)) over n 16-bit elements); *amax_bits starts at 0
 hipError_t launch_amax(int mode, const void* X, size_t n, int relu, unsigned* amax_bits, hipStream_t stream);
 

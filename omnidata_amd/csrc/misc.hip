@@ -62,10 +62,128 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const uint16_t* __restr
   }
 }
 
+// The separable form for the one-plane dtypes (no e4m3 copy): a thread owns 8 channels of one output column over a STRIP of
+// R output rows.  ry = (H-1)/(2H-1) < 1/2, so the strip's rows oy0 .. oy0+R-1 have y0 - (int)(ry oy0) <= R/2 and their
+// y1 = min(y0 + 1, H - 1) lies one further: R/2 + 2 source rows starting at ybase = (int)(ry oy0), slot j holding row
+// min(ybase + j, H - 1) -- head_tail_kernel's six rows per ten window rows.  (upsample_strip_rows_ok() replays the fp32
+// index arithmetic of every output row of the launch's H on the host before the form is taken.)  Each slot's two source
+// vectors are loaded once and blended horizontally once (common.h hblend); an output row is one vertical blend of two slots
+// (vblend) -- bilerp()'s roundings.  The per-row sy, y0, ly1 arithmetic is ATen's, as upsample2x_kernel is compiled.
+// grid (ceil(Wo*C/8 / 256), B * ceil(Ho / R)): lanes run along (column, chunk), so a wave stores 1 KB contiguous per output
+// row; image and strip come from blockIdx.y (one scalar division per block); the last strip of an image may be short.
+template <int DT, int R>
+__global__ __launch_bounds__(256) void upsample2x_strip_kernel(const uint16_t* __restrict__ X, uint16_t* __restrict__ Y, int H, int W,
+                                                               int C, int cshift, int nstrips) {
+  constexpr int NS = R / 2 + 2;
+  const int Ho = 2 * H, Wo = 2 * W, cvec = C >> 3;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= Wo * cvec) return;
+  const int v = idx & (cvec - 1), ox = idx >> cshift;
+  const int b = blockIdx.y / nstrips, oy0 = (blockIdx.y - b * nstrips) * R;
+  const float ry = (float)(H - 1) / (float)(Ho - 1);  // Ho >= 2
+  const float rx = (float)(W - 1) / (float)(Wo - 1);
+  // l1 = src - i0 is spelled as the fma hipcc contracts it to in upsample2x_kernel (ratio * dst is not rounded before the
+  // subtraction; i0 comes from the rounded product): left to -ffp-contract, this kernel got the fma in some rows only
+  const float sx = __fmul_rn(rx, (float)ox);
+  const int x0 = (int)sx, x1 = x0 + (x0 < W - 1 ? 1 : 0);
+  const float lx1 = __fmaf_rn(rx, (float)ox, -(float)x0), lx0 = 1.f - lx1;
+  const int ybase = (int)__fmul_rn(ry, (float)oy0);
+  const uint16_t* img = X + (long long)b * H * W * C + v * 8;
+  u32x4_t S[NS][2];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    const int row = min(ybase + j, H - 1);
+    S[j][0] = *(const u32x4_t*)(img + (row * W + x0) * C);
+    S[j][1] = *(const u32x4_t*)(img + (row * W + x1) * C);
+  }
+  float T[NS][8];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) hblend<DT>(S[j][0], S[j][1], lx0, lx1, T[j]);
+  uint16_t* out = Y + (((long long)b * Ho + oy0) * Wo + ox) * C + v * 8;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int oy = oy0 + r;
+    if (oy >= Ho) break;  // uniform over the block
+    const int y0 = (int)__fmul_rn(ry, (float)oy);
+    const float ly1 = __fmaf_rn(ry, (float)oy, -(float)y0), ly0 = 1.f - ly1;
+    const int d = __builtin_amdgcn_readfirstlane(y0 - ybase);  // uniform over the block; 0 .. min(r, R / 2)
+    u32x4_t o;
+    if (r == 0 || d == 0) o = vblend<DT, true>(T[0], T[1], ly0, ly1);
+    else if (r == 1 || d == 1) o = vblend<DT, true>(T[1], T[2], ly0, ly1);
+    else if (R == 4 || r == 2 || d == 2) o = vblend<DT, true>(T[2], T[3], ly0, ly1);
+    else if (r == 3 || d == 3) o = vblend<DT, true>(T[NS > 4 ? 3 : 0], T[NS > 4 ? 4 : 1], ly0, ly1);
+    else o = vblend<DT, true>(T[NS > 5 ? 4 : 0], T[NS > 5 ? 5 : 1], ly0, ly1);
+    *(u32x4_t*)(out + (long long)r * Wo * C) = o;
+  }
+}
+
+// the strip form's precondition, replayed with the kernel's own fp32 arithmetic for every output row of an H-row source:
+// y0 - ybase in [0, min(r, R/2)] (the slots the kernel selects from)
+static bool upsample_strip_rows_ok(int H, int R) {
+  static std::mutex mu;
+  static std::set<std::pair<int, int>> good, bad;
+  std::lock_guard<std::mutex> lock(mu);
+  const std::pair<int, int> key(H, R);
+  if (good.count(key)) return true;
+  if (bad.count(key)) return false;
+  const int Ho = 2 * H;
+  const float ry = (float)(H - 1) / (float)(Ho - 1);
+  bool ok = true;
+  for (int oy0 = 0; oy0 < Ho && ok; oy0 += R) {
+    const int ybase = (int)(ry * (float)oy0);
+    for (int r = 0; r < R && oy0 + r < Ho; ++r) {
+      const int d = (int)(ry * (float)(oy0 + r)) - ybase;
+      if (d < 0 || d > std::min(r, R / 2)) ok = false;
+    }
+  }
+  (ok ? good : bad).insert(key);
+  return ok;
+}
+
+// R output rows per thread of the strip form for an (H, C) launch, 0 = upsample2x_kernel.  Classes and strip heights are
+// those that measured faster at the op level at B = 32 and B = 16 (profiles/stem_upsample.md); debug flag 256 takes the
+// strip form (R = 4 outside the measured classes) wherever it can run, flag 128 nowhere.
+static int upsample_strip_rows(int H, int W, int C) {
+  const int flags = gemm_debug_flags();
+  if (flags & 128) return 0;
+  int R = 0;
+  // the four decoder launches: 96 x 96 211 -> 139 us and 48 x 48 38.6 -> 34.9 us with strips of 8 (B = 32; 106 -> 79 and
+  // 21.0 -> 18.1 at B = 16); 24 x 24 8.2 -> 6.6 us and 12 x 12 4.4 -> 4.2 us with strips of 4 at B = 16, what a half batch
+  // of the two-stream forward launches (strips of 8 there: 6.9 and 4.5 us)
+  if (C == 256 && H == W && (H == 96 || H == 48)) R = 8;
+  if (C == 256 && H == W && (H == 24 || H == 12)) R = 4;
+  if (R == 0 && (flags & 256)) R = 4;
+  return R;
+}
+
+hipError_t launch_upsample2x_strip(int mode, const void* X, void* Y, int B, int H, int W, int C, int R, hipStream_t stream) {
+  const int cvec = C / 8;
+  if (C % 8 != 0 || (cvec & (cvec - 1)) != 0 || (long long)H * W * C >= (1ll << 31) || H < 1 || W < 1 || B < 1)
+    return hipErrorInvalidValue;
+  if ((mode != MODE_BF16 && mode != MODE_FP16) || (R != 4 && R != 8) || !upsample_strip_rows_ok(H, R)) return hipErrorInvalidValue;
+  if ((uintptr_t)X % 16 != 0 || (uintptr_t)Y % 16 != 0) return hipErrorInvalidValue;
+  int cshift = 0;
+  while ((1 << cshift) < cvec) ++cshift;
+  const int nstrips = (2 * H + R - 1) / R;
+  dim3 grid((2 * W * cvec + 255) / 256, B * nstrips);
+#define DPTX_UP_STRIP(DT_, R_)                                                                                              \
+  hipLaunchKernelGGL((upsample2x_strip_kernel<DT_, R_>), grid, dim3(256), 0, stream, (const uint16_t*)X, (uint16_t*)Y, H, W, C, \
+                     cshift, nstrips)
+  if (mode == MODE_BF16) { if (R == 4) DPTX_UP_STRIP(DT_BF16, 4); else DPTX_UP_STRIP(DT_BF16, 8); }
+  else { if (R == 4) DPTX_UP_STRIP(DT_FP16, 4); else DPTX_UP_STRIP(DT_FP16, 8); }
+#undef DPTX_UP_STRIP
+  return hipGetLastError();
+}
+
 hipError_t launch_upsample2x(int mode, const void* X, void* Y, int B, int H, int W, int C, Planes pl, hipStream_t stream,
                              void* Y8, float q_scale, bool out_hi_only) {
   const int cvec = C / 8;
   if (C % 8 != 0 || (cvec & (cvec - 1)) != 0 || (long long)H * W * C >= (1ll << 31)) return hipErrorInvalidValue;
+  if ((mode == MODE_BF16 || mode == MODE_FP16) && Y8 == nullptr && H >= 1 && W >= 1 && B >= 1) {  // launches with an e4m3 copy stay below
+    const int R = upsample_strip_rows(H, W, C);
+    if (R != 0 && upsample_strip_rows_ok(H, R) && (uintptr_t)X % 16 == 0 && (uintptr_t)Y % 16 == 0)
+      return launch_upsample2x_strip(mode, X, Y, B, H, W, C, R, stream);
+  }
   int cshift = 0;
   while ((1 << cshift) < cvec) ++cshift;
   dim3 grid((2 * W * cvec + 255) / 256, B * 2 * H);

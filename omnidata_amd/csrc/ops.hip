@@ -88,6 +88,11 @@ int dptx_op_stem_conv(int32_t dtype, const float* x, const void* Wt, void* y, in
   return rc(launch_stem_conv(dtype, x, DPTX_IO_FP32, Wt, y, B, H, W, g_op_planes, (hipStream_t)stream));
 }
 
+int dptx_op_stem_conv_io(int32_t dtype, const void* x, int32_t io, const void* Wt, void* y, int32_t B, int32_t H, int32_t W, void* stream) {
+  if (io != DPTX_IO_FP32 && io != DPTX_IO_BF16 && io != DPTX_IO_FP16) return rc(hipErrorInvalidValue);
+  return rc(launch_stem_conv(dtype, x, io, Wt, y, B, H, W, g_op_planes, (hipStream_t)stream));
+}
+
 int dptx_op_attention(int32_t dtype, const void* qkv, void* out, int32_t B, int32_t S, int32_t heads, void* stream) {
   return rc(launch_attention(dtype, qkv, out, B, S, heads, g_op_planes, (hipStream_t)stream));
 }
@@ -195,6 +200,11 @@ int dptx_op_conv_groupnorm_fused(int32_t dtype, const void* X, const void* Wt, c
 
 int dptx_op_upsample2x(int32_t dtype, const void* X, void* Y, int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
   return rc(launch_upsample2x(dtype, X, Y, B, H, W, C, g_op_planes, (hipStream_t)stream));
+}
+
+int dptx_op_upsample2x_strip(int32_t dtype, const void* X, void* Y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t rows,
+                             void* stream) {
+  return rc(launch_upsample2x_strip(dtype, X, Y, B, H, W, C, rows, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -141,6 +141,7 @@ ABI = [
     ("dptx_op_conv", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp] + [_i32] * 13 + [_vp]),
     ("dptx_op_conv_planes", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp] + [_i32] * 16 + [_vp]),
     ("dptx_op_stem_conv", C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    ("dptx_op_stem_conv_io", C.c_int, [_i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("dptx_op_attention", C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("dptx_op_layernorm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, C.c_float, _vp]),
     ("dptx_op_groupnorm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp]),
@@ -156,6 +157,7 @@ ABI = [
     ("dptx_op_conv_groupnorm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp] + [_i32] * 12 + [C.c_float, _vp, _vp]),
     ("dptx_op_conv_groupnorm_fused", C.c_int, [_i32] + [_vp] * 9 + [_i32] * 6 + [C.c_float, _vp, _vp, _i32, _vp]),
     ("dptx_op_upsample2x", C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    ("dptx_op_upsample2x_strip", C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_op_gemm_ln", C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, C.c_float, _vp]),
     ("dptx_op_gemm_stream", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("dptx_op_gemm_stream32", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),

@@ -1,7 +1,9 @@
 """Per-shape micro-benchmark of the implicit-GEMM kernel on the DPT-Hybrid layer shapes (B=32).
 Usage (GPU box): python tools/gemm_bench.py [--dtype bf16]
                  python tools/gemm_bench.py --ab-flags 0,8 --gn --reps 5 --only s0.c3,s1.c3   (A/B of two launch forms)
-                 python tools/gemm_bench.py --ab-gn-fold --reps 5 --iters 20 [--batch 16]      (conv3 + norm3: unfused vs folded)"""
+                 python tools/gemm_bench.py --ab-gn-fold --reps 5 --iters 20 [--batch 16]      (conv3 + norm3: unfused vs folded)
+                 python tools/gemm_bench.py --ab-stem --reps 5 --iters 20 [--batch 16]         (stem convolution: first vs second form)
+                 python tools/gemm_bench.py --ab-upsample --reps 5 --iters 20 [--batch 16]     (x2 up-sampling: first form vs strips)"""
 import argparse
 import os
 import sys
@@ -133,6 +135,67 @@ def ab_gn_fold(lib, dt, tdt, st, args, only):
         del X, Wt, R, Yraw, Y
 
 
+def _ab(sides, args):
+    """alternating --reps repetitions of --iters launches per side -> ({side: [us]}, {side: median}, {side: max - min})"""
+    for fn in sides.values():
+        assert fn() == 0
+    t = {n: [] for n in sides}
+    for _ in range(args.reps):
+        for n, fn in sides.items():
+            t[n].append(timeit(fn) * 1e3)
+    return t, {n: sorted(v)[len(v) // 2] for n, v in t.items()}, {n: max(v) - min(v) for n, v in t.items()}
+
+
+def _flagged(lib, flag, fn):
+    def run():
+        lib.dptx_debug_set_gemm_flags(flag)
+        try:
+            return fn()
+        finally:
+            lib.dptx_debug_set_gemm_flags(0)
+    return run
+
+
+def ab_stem(lib, dt, tdt, st, args):
+    """The stem convolution at 384 x 384 from an fp32 image: stem_conv_kernel (debug flag 128) against stem_conv_kernel_wp (the
+    dispatch), alternating; every repetition, the medians, each side's spread and the verdict of the adoption rule (faster by
+    more than the larger spread); bytes the launch has to move (image in + raw map out) over the median = achieved TB/s."""
+    print(f"# stem conv 384 x 384, old (flag 128) vs new, {args.reps} x {args.iters} launches, B = {B}, {args.dtype}; us per launch")
+    x = torch.rand(B, 3, 384, 384, device="cuda")
+    Wt = (torch.randn(64, 176, device="cuda") * 147 ** -0.5).to(tdt)
+    y = torch.empty(B, 192, 192, 64, device="cuda", dtype=tdt)
+    call = lambda: lib.dptx_op_stem_conv(dt, x.data_ptr(), Wt.data_ptr(), y.data_ptr(), B, 384, 384, st)
+    t, med, spr = _ab({"old": _flagged(lib, 128, call), "new": call}, args)
+    mb = (x.numel() * 4 + y.numel() * 2) / 1e6
+    gain = med["old"] - med["new"]
+    print("stem  old " + " ".join(f"{v:6.1f}" for v in t["old"]) + "  | new " + " ".join(f"{v:6.1f}" for v in t["new"]) +
+          f"  | median {med['old']:6.1f} vs {med['new']:6.1f}  gain {gain:+6.1f}  spread {spr['old']:4.1f} / {spr['new']:4.1f}"
+          f"  -> {'faster' if gain > max(spr.values()) else 'not faster'}")
+    print(f"      {mb:.1f} MB in + out: old {mb / med['old']:.2f} TB/s, new {mb / med['new']:.2f} TB/s")
+
+
+def ab_upsample(lib, dt, tdt, st, args):
+    """The four decoder up-samplings (C = 256): upsample2x_kernel (debug flag 128) against the strip form with 4 and with 8
+    output rows per thread, alternating; medians, spreads, the adoption rule per strip height, and bytes written over the
+    median = achieved write rate."""
+    print(f"# x2 up-sampling C = 256, old (flag 128) vs strips of 4 / 8 rows, {args.reps} x {args.iters} launches, B = {B}, {args.dtype}; us per launch")
+    for H in (96, 48, 24, 12):
+        X = torch.randn(B, H, H, 256, device="cuda").to(tdt)
+        Y = torch.empty(B, 2 * H, 2 * H, 256, device="cuda", dtype=tdt)
+        old = lambda: lib.dptx_op_upsample2x(dt, X.data_ptr(), Y.data_ptr(), B, H, H, 256, st)
+        strip = lambda R: (lambda: lib.dptx_op_upsample2x_strip(dt, X.data_ptr(), Y.data_ptr(), B, H, H, 256, R, st))
+        t, med, spr = _ab({"old": _flagged(lib, 128, old), "strip4": strip(4), "strip8": strip(8)}, args)
+        out_mb = Y.numel() * 2 / 1e6
+        line = f"up@{H:<3d} " + "  | ".join(f"{n} " + " ".join(f"{v:6.1f}" for v in t[n]) for n in t) + "  | median " + \
+            " / ".join(f"{med[n]:6.1f}" for n in t) + "  spread " + " / ".join(f"{spr[n]:4.1f}" for n in t)
+        for n in ("strip4", "strip8"):
+            gain = med["old"] - med[n]
+            line += f"  {n} gain {gain:+6.1f} -> {'faster' if gain > max(spr['old'], spr[n]) else 'not faster'}"
+        print(line)
+        print(f"        writes {out_mb:.1f} MB: " + ", ".join(f"{n} {out_mb / med[n]:.2f} TB/s" for n in t))
+        del X, Y
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
@@ -143,6 +206,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="repetitions per side of --ab-flags")
     ap.add_argument("--ab-gn-fold", action="store_true",
                     help="conv3 + norm3 of the three stage classes: conv + apply pass vs statistics + finalize + GroupNorm-epilogue pass")
+    ap.add_argument("--ab-stem", action="store_true", help="stem convolution: stem_conv_kernel (flag 128) vs stem_conv_kernel_wp")
+    ap.add_argument("--ab-upsample", action="store_true", help="x2 up-sampling of the four decoder classes: first form vs strips of 4 / 8 rows")
     ap.add_argument("--gn", action="store_true", help="--ab-flags: GroupNorm records on (conv + apply pass) where the forward has them")
     args = ap.parse_args()
     global B
@@ -155,6 +220,12 @@ def main():
     st = torch.cuda.current_stream().cuda_stream
     if args.ab_gn_fold:
         return ab_gn_fold(lib, dt, tdt, st, args, only)
+    if args.ab_stem or args.ab_upsample:
+        if args.ab_stem:
+            ab_stem(lib, dt, tdt, st, args)
+        if args.ab_upsample:
+            ab_upsample(lib, dt, tdt, st, args)
+        return
     if args.ab_flags:
         return ab_conv(lib, dt, tdt, st, args, only)
     tot_ms, tot_flop = 0.0, 0.0
