@@ -928,6 +928,16 @@ int dptx_op_gemm_stream32(int32_t dtype, const void* A, const void* W, const flo
 int dptx_op_head_tail(int32_t dtype, const void* H0, const void* W2, const float* b2, const float* w4,
                       const float* b4, float* y, int32_t B, int32_t Hs, int32_t Ws, int32_t C,
                       int32_t relu_out, void* stream);
+/* The same with a result of element type io (DPTX_IO_FP32 / _BF16 / _FP16; anything else -> DPTX_E_INVALID): the fp32 value
+ * rounded to nearest, as the forward stores a 16-bit result image. */
+int dptx_op_head_tail_io(int32_t dtype, const void* H0, const void* W2, const float* b2, const float* w4,
+                         const float* b4, void* y, int32_t io, int32_t B, int32_t Hs, int32_t Ws, int32_t C,
+                         int32_t relu_out, void* stream);
+/* The 1x1 projection of the three-launch tail (dpt_depth.py:96-98): X [B*HW][32] 16-bit (a hi/lo pair for BF16X3 / FP16X3,
+ * planes of dptx_op_set_planes) -> y NCHW [B][Cout][HW] of element type io = w X + b, ReLU if relu.  w fp32 [Cout][32],
+ * b fp32 [Cout].  Cout outside 1..4, B < 1, HW < 1, an unknown io or another dtype -> DPTX_E_INVALID. */
+int dptx_op_head_out(int32_t dtype, const void* X, const float* w, const float* b, void* y, int32_t io, int32_t B,
+                     int32_t HW, int32_t Cout, int32_t relu, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * The reference's version-1 UNet (omnidata_tools/torch/modules/unet.py:8-105; checkpoint omnidata_unet_normal_v1.pth),

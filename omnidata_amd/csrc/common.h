@@ -223,6 +223,16 @@ __device__ __forceinline__ float bilerp(float a, float b, float c, float d, floa
   return __fmaf_rn(ly1, t1, __fmul_rn(ly0, t0));
 }
 
+// ATen's source index and weight of one axis, i0 = int(ratio * dst) and l1 = ratio * dst - i0, in the ONE rounding the x2
+// up-sampling kernels (misc.hip) and both head kernels (head.hip) use: i0 from the rounded product, l1 from one fma on the unrounded one (what hipcc's contraction made of
+// `src - i0` in upsample2x_kernel).  Spelled out, because left to -ffp-contract a kernel gets the fma on one axis and the plain
+// subtraction on the other, and the two differ by up to an ulp of src.
+__device__ __forceinline__ int lerp_index(float ratio, int dst, float& l1) {
+  const int i0 = (int)__fmul_rn(ratio, (float)dst);
+  l1 = __fmaf_rn(ratio, (float)dst, -(float)i0);
+  return i0;
+}
+
 // The same association is separable as written: the inner sums are the horizontal blends of source rows y0 and y1.  A
 // kernel that emits several output rows per thread forms them once per source row (hblend) and every output row as one
 // vertical blend of two of them (vblend) -- bit-identical to bilerp(), 2.3x fewer VALU operations.

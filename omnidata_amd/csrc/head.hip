@@ -88,10 +88,10 @@ __global__ __launch_bounds__(HT_THREADS) void head_tail_kernel(const uint16_t* _
     const int b = t / tpi, rem = t - b * tpi, ty = rem / tiles_x, tx = rem - ty * tiles_x;
     const int ox = tx * 32 - 1 + wx;
     const bool vx = col_thread && ox >= 0 && ox < Wo;
-    const float sx = rx * (float)(vx ? ox : 0);
+    const float sx = __fmul_rn(rx, (float)(vx ? ox : 0));
     const int x0 = (int)sx, x1 = x0 + (x0 < Ws - 1 ? 1 : 0);
     const int oyb = max(ty * 8 - 1, 0);
-    const int ybase = (int)(ry * (float)oyb);
+    const int ybase = (int)__fmul_rn(ry, (float)oyb);
     const uint16_t* img = H0 + (long long)b * Hs * Ws * 128 + wch * 8;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
@@ -112,10 +112,13 @@ __global__ __launch_bounds__(HT_THREADS) void head_tail_kernel(const uint16_t* _
     if (col_thread) {
       const int ox = ox0 - 1 + wx;
       const bool vx = ox >= 0 && ox < Wo;
-      const float sx = rx * (float)(vx ? ox : 0);
-      const int x0 = (int)sx;
-      const float lx1 = sx - (float)x0, lx0 = 1.f - lx1;
-      const int ybase = (int)(ry * (float)max(oy0 - 1, 0));
+      // l1 = src - i0 as upsample2x_kernel has it: one fma on the unrounded product, i0 from the rounded one (common.h
+      // lerp_index).  Left to -ffp-contract, head_tail_x3_kernel got the fma for ly1 and a plain subtraction for lx1, and its
+      // window was not the map upsample2x_kernel stores (tests/test_gpu_head_elements.py test_head_window_probe)
+      float lx1;
+      (void)lerp_index(rx, vx ? ox : 0, lx1);   // the weight only: the source columns x0, x1 were taken in fetch()
+      const float lx0 = 1.f - lx1;
+      const int ybase = (int)__fmul_rn(ry, (float)max(oy0 - 1, 0));
       char* dst = P + wx * 256 + ((wch ^ (wx & 15)) << 4);
       float T[6][8];
 #pragma unroll
@@ -124,9 +127,9 @@ __global__ __launch_bounds__(HT_THREADS) void head_tail_kernel(const uint16_t* _
         const int oy = oy0 - 1 + r;
         u32x4_t o = zero4;
         if (vx && oy >= 0 && oy < Ho) {
-          const float sy = ry * (float)oy;
-          const int y0 = (int)sy;
-          const float ly1 = sy - (float)y0, ly0 = 1.f - ly1;
+          float ly1;
+          const int y0 = lerp_index(ry, oy, ly1);
+          const float ly0 = 1.f - ly1;
           switch (y0 - ybase) {  // uniform over the block; slot j+1 holds row min(y0+1, Hs-1) = ATen's y1
             case 0: o = vblend<DT>(T[0], T[1], ly0, ly1); break;
             case 1: o = vblend<DT>(T[1], T[2], ly0, ly1); break;
@@ -306,10 +309,10 @@ __global__ __launch_bounds__(HX_THREADS) void head_tail_x3_kernel(const uint16_t
       if (item < 2 * 136) {
         const int ox = ox0 - 1 + wx;
         const bool vx = ox >= 0 && ox < Wo;
-        const float sx = rx * (float)(vx ? ox : 0);
-        const int x0 = (int)sx, x1 = x0 + (x0 < Ws - 1 ? 1 : 0);
-        const float lx1 = sx - (float)x0, lx0 = 1.f - lx1;
-        const int ybase = (int)(ry * (float)max(oy0 - 1 + 5 * rh, 0));
+        float lx1;
+        const int x0 = lerp_index(rx, vx ? ox : 0, lx1), x1 = x0 + (x0 < Ws - 1 ? 1 : 0);
+        const float lx0 = 1.f - lx1;
+        const int ybase = (int)__fmul_rn(ry, (float)max(oy0 - 1 + 5 * rh, 0));
         const uint16_t* img = H0 + (long long)b * Hs * Ws * 128 + quarter * 32 + wch * 8;
         SrcVecs S;
 #pragma unroll
@@ -331,9 +334,9 @@ __global__ __launch_bounds__(HX_THREADS) void head_tail_x3_kernel(const uint16_t
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] = 0.f;
           if (vx && oy >= 0 && oy < Ho) {
-            const float sy = ry * (float)oy;
-            const int y0 = (int)sy;
-            const float ly1 = sy - (float)y0, ly0 = 1.f - ly1;
+            float ly1;
+            const int y0 = lerp_index(ry, oy, ly1);
+            const float ly0 = 1.f - ly1;
             const int j0 = y0 - ybase;  // 0..2; slot j0 + 1 holds row min(y0 + 1, Hs - 1) = ATen's y1
             if (j0 == 0) {
 #pragma unroll

@@ -39,10 +39,9 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const uint16_t* __restr
   const int b = blockIdx.y / Ho, oy = blockIdx.y - b * Ho;
   const float ry = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
   const float rx = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
-  const float sy = ry * (float)oy, sx = rx * (float)ox;
-  const int y0 = (int)sy, x0 = (int)sx;
+  float ly1, lx1;
+  const int y0 = lerp_index(ry, oy, ly1), x0 = lerp_index(rx, ox, lx1);
   const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-  const float ly1 = sy - (float)y0, lx1 = sx - (float)x0;
   const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
   const uint16_t* img = X + (long long)b * H * W * C + v * 8;
   float a[8], bb[8], c[8], d[8], o[8];
@@ -82,11 +81,11 @@ __global__ __launch_bounds__(256) void upsample2x_strip_kernel(const uint16_t* _
   const int b = blockIdx.y / nstrips, oy0 = (blockIdx.y - b * nstrips) * R;
   const float ry = (float)(H - 1) / (float)(Ho - 1);  // Ho >= 2
   const float rx = (float)(W - 1) / (float)(Wo - 1);
-  // l1 = src - i0 is spelled as the fma hipcc contracts it to in upsample2x_kernel (ratio * dst is not rounded before the
-  // subtraction; i0 comes from the rounded product): left to -ffp-contract, this kernel got the fma in some rows only
-  const float sx = __fmul_rn(rx, (float)ox);
-  const int x0 = (int)sx, x1 = x0 + (x0 < W - 1 ? 1 : 0);
-  const float lx1 = __fmaf_rn(rx, (float)ox, -(float)x0), lx0 = 1.f - lx1;
+  // l1 = src - i0 as upsample2x_kernel has it (common.h lerp_index: ratio * dst is not rounded before the subtraction; i0
+  // comes from the rounded product): left to -ffp-contract, this kernel got the fma in some rows only
+  float lx1;
+  const int x0 = lerp_index(rx, ox, lx1), x1 = x0 + (x0 < W - 1 ? 1 : 0);
+  const float lx0 = 1.f - lx1;
   const int ybase = (int)__fmul_rn(ry, (float)oy0);
   const uint16_t* img = X + (long long)b * H * W * C + v * 8;
   u32x4_t S[NS][2];
@@ -104,8 +103,9 @@ __global__ __launch_bounds__(256) void upsample2x_strip_kernel(const uint16_t* _
   for (int r = 0; r < R; ++r) {
     const int oy = oy0 + r;
     if (oy >= Ho) break;  // uniform over the block
-    const int y0 = (int)__fmul_rn(ry, (float)oy);
-    const float ly1 = __fmaf_rn(ry, (float)oy, -(float)y0), ly0 = 1.f - ly1;
+    float ly1;
+    const int y0 = lerp_index(ry, oy, ly1);
+    const float ly0 = 1.f - ly1;
     const int d = __builtin_amdgcn_readfirstlane(y0 - ybase);  // uniform over the block; 0 .. min(r, R / 2)
     u32x4_t o;
     if (r == 0 || d == 0) o = vblend<DT, true>(T[0], T[1], ly0, ly1);
@@ -286,9 +286,12 @@ __global__ __launch_bounds__(256) void head_out_kernel(const uint16_t* __restric
     for (int q = 0; q < 4; ++q) load8f<DT, PL>(X + i * 32 + q * 8, plane, f + 8 * q);
     const long long b = i / HW, p = i - b * HW;
     for (int c = 0; c < Cout; ++c) {
-      float acc = bias[c];
+      // four chains of eight terms (k mod 4), then a tree: eleven roundings on the longest path where one chain of 33 left the
+      // fp32 floor of the other kernels on a few of 4 M pixels (tests/test_gpu_head_elements.py test_head_out_elements)
+      float a[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int k = 0; k < 32; ++k) acc += w[c * 32 + k] * f[k];
+      for (int k = 0; k < 32; ++k) a[k & 3] = __fmaf_rn(w[c * 32 + k], f[k], a[k & 3]);
+      float acc = ((a[0] + a[1]) + (a[2] + a[3])) + bias[c];
       if (relu) acc = fmaxf(acc, 0.f);
       io_store(y, (b * Cout + c) * HW + p, acc, io);
     }

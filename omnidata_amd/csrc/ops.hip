@@ -65,6 +65,22 @@ int dptx_op_head_tail(int32_t dtype, const void* H0, const void* W2, const float
   return rc(launch_head_tail(dtype, H0, W2, b2, w4, b4, y, DPTX_IO_FP32, B, Hs, Ws, C, relu_out, (hipStream_t)stream, g_op_planes));
 }
 
+int dptx_op_head_tail_io(int32_t dtype, const void* H0, const void* W2, const float* b2, const float* w4, const float* b4, void* y,
+                         int32_t io, int32_t B, int32_t Hs, int32_t Ws, int32_t C, int32_t relu_out, void* stream) {
+  if (io != DPTX_IO_FP32 && io != DPTX_IO_BF16 && io != DPTX_IO_FP16) return DPTX_E_INVALID;
+  return rc(launch_head_tail(dtype, H0, W2, b2, w4, b4, y, io, B, Hs, Ws, C, relu_out, (hipStream_t)stream, g_op_planes));
+}
+
+// the 1x1 projection of the unfused tail (misc.hip head_out_kernel): what bf16x3, and every size the fused form refuses, run
+int dptx_op_head_out(int32_t dtype, const void* X, const float* w, const float* b, void* y, int32_t io, int32_t B, int32_t HW,
+                     int32_t Cout, int32_t relu, void* stream) {
+  if (io != DPTX_IO_FP32 && io != DPTX_IO_BF16 && io != DPTX_IO_FP16) return DPTX_E_INVALID;
+  if (Cout < 1 || Cout > 4 || B < 1 || HW < 1) return DPTX_E_INVALID;
+  if (dtype != DPTX_DTYPE_BF16 && dtype != DPTX_DTYPE_FP16 && dtype != DPTX_DTYPE_BF16X3 && dtype != DPTX_DTYPE_FP16X3)
+    return DPTX_E_INVALID;
+  return rc(launch_head_out(dtype, X, w, b, y, io, B, HW, Cout, relu, g_op_planes, (hipStream_t)stream));
+}
+
 int dptx_op_conv(int32_t dtype, const void* X, const void* Wt, const float* bias, const void* R, void* Y, int32_t B, int32_t H,
                  int32_t W, int32_t Cin, int32_t Cout, int32_t ksize, int32_t stride, int32_t pad_t, int32_t pad_l, int32_t Ho,
                  int32_t Wo, int32_t a_relu, int32_t act, void* stream) {

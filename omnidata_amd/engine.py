@@ -162,6 +162,8 @@ ABI = [
     ("dptx_op_gemm_stream", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("dptx_op_gemm_stream32", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("dptx_op_head_tail", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("dptx_op_head_tail_io", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("dptx_op_head_out", C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     # the version-1 UNet (omnidata_amd/unet.py): a handle type of its own, and the op-level entry points of its kernels
     ("dptx_unet_default_config", None, [_vp]),
     ("dptx_unet_create", C.c_int, [C.POINTER(_vp), _vp]),

@@ -451,3 +451,169 @@ def assert_elements_inside(got, y, bound, what):
     print(f"\n[elements] {what}: worst |err| / bound {worst:.3f}")
     assert not bad, f"{what}: worst |err| / bound {worst:.3f}, first elements outside {bad}"
     return worst
+
+
+# ------------------------------------------------------------------ the kernels that interpolate, judged element by element
+# The x2 up-sampling (csrc/misc.hip) and the fused head tail (csrc/head.hip) against fp64.  rel_err lets a wrong value in a
+# small channel, a wrong halo column at a tile seam and a flipped 16-bit rounding in the window pass; the helpers below give
+# operands with a scale of their own in every pixel and channel, fp64 references with the magnitude sums a bound is relative
+# to, and the bars on every single element.  Pure torch, any device.  tests/test_head_bound_host.py shows on a CPU which
+# mistakes the bars reject; profiles/head_elements.md has the figures.
+
+UP_VARIANTS = ("y:sub x:sub", "y:sub x:fma", "y:fma x:sub", "y:fma x:fma")
+# fp32 floor of the blend in units of 2^-24 Sb: the largest |F.interpolate(fp32) - upsample_ref64| / (2^-24 Sb) on a CPU over
+# UP_HOST_CASES x the four modes' operands (scaled_head_operands, seed 0), each case against the variant that fits it best
+# (on a CPU always "y:sub x:sub").  The sixteen figures lay between 2.87 and 4.43, the largest bf16x3 at (1, 96, 96, 128) -- the
+# roundings of 1 - l1 on either axis, of six products and of three sums.  Measured against the reference, never against a
+# kernel; tests/test_head_bound_host.py re-measures it (profiles/head_elements.md).
+UP_F32_FLOOR_MEASURED = 4.5
+UP_HOST_CASES = ((1, 4, 16, 128), (2, 12, 16, 128), (3, 20, 48, 128), (1, 96, 96, 128))
+HEAD_HOST_SHAPES = ((1, 4, 16, 1, 1), (2, 4, 32, 3, 0), (2, 12, 16, 2, 1), (3, 20, 48, 3, 1))
+
+
+def scaled_head_operands(B, Hs, Ws, C, seed=0, Cin=128):
+    """H0 [B, Hs, Ws, Cin], W2 [32, 3, 3, Cin], b2 [32], w4 [C, 32], b4 [C] in fp64 (CPU), deterministic in `seed`.
+      H0[b, y, x, c] = 2^((7 p mod 13) - 6) 2^((5 c mod 7) - 3) N(0, 1), p the flat pixel index over the batch: the family of
+      scaled_conv_operands with a scale per channel on top;  W2[n], b2[n] carry 2^((5 n mod 7) - 3) as there (K = 9 Cin);
+      w4[c, :] = (8, 1, 1/8, 1)[c] 32^-1/2 N(0, 1) and b4[c] = (8, 1, 1/8, 1)[c] N(0, 1): a small output channel is judged by
+      its own size.  |H0| < 2^9 * 6: inside fp16."""
+    g = torch.Generator().manual_seed(4000 + seed)
+    H0 = (torch.randn(B, Hs, Ws, Cin, generator=g, dtype=torch.float64) * torch.exp2(_row_exp(B * Hs * Ws)).view(B, Hs, Ws, 1)
+          * torch.exp2(_col_exp(Cin)))
+    sf = torch.exp2(_col_exp(32))
+    W2 = torch.randn(32, 3, 3, Cin, generator=g, dtype=torch.float64) * sf.view(-1, 1, 1, 1) * (9 * Cin) ** -0.5
+    b2 = torch.randn(32, generator=g, dtype=torch.float64) * sf
+    rs = torch.tensor([8.0, 1.0, 0.125, 1.0], dtype=torch.float64)[:C]
+    w4 = torch.randn(C, 32, generator=g, dtype=torch.float64) * rs[:, None] * 32 ** -0.5
+    b4 = torch.randn(C, generator=g, dtype=torch.float64) * rs
+    return H0, W2, b2, w4, b4
+
+
+def up_axis32(n_in, variant_fma, device="cpu"):
+    """(i0, i1, l0, l1) of one axis of the x2 align-corners up-sampling in ATen's fp32 formulation: ratio = (in - 1) / (out - 1),
+    src = ratio dst, i0 = int(src), i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1, everything rounded to fp32.  l1 has two
+    legitimate values: fl32(fl32(ratio dst) - i0) (variant_fma False: the subtraction itself is exact) and fl32(ratio dst - i0)
+    with the product not rounded (True: what a compiler's fma contraction gives; exact to form in fp64, where the product of
+    two fp32 numbers and its difference to a small integer are representable).  i0 comes from the rounded product either way."""
+    n_out = 2 * n_in
+    ratio = (torch.tensor(float(n_in - 1), dtype=torch.float32) / torch.tensor(float(n_out - 1), dtype=torch.float32))
+    dst = torch.arange(n_out, dtype=torch.float32)
+    src = ratio * dst                                        # fp32, rounded
+    i0 = src.to(torch.int64)
+    i1 = i0 + (i0 < n_in - 1).to(torch.int64)
+    if variant_fma:
+        l1 = (ratio.double() * dst.double() - i0.double()).float()
+    else:
+        l1 = src - i0.float()
+    l0 = 1.0 - l1                                            # fp32, rounded
+    return i0.to(device), i1.to(device), l0.to(device), l1.to(device)
+
+
+def upsample_ref64(X, variant):
+    """(y, Sb) in fp64 of the x2 bilinear align-corners up-sampling of the values X [B, H, W, C] the kernel reads (hi + lo for
+    the plane modes): indices and weights in fp32 (up_axis32; variant 0..3 = UP_VARIANTS picks how l1 is rounded on the two
+    axes), the blend ly0 (lx0 a + lx1 b) + ly1 (lx0 c + lx1 d) in fp64.  Sb is the same blend of |values| with |weights|: what
+    a rounding of any weight, product or partial sum is relative to."""
+    X = X.double()
+    y0, y1, ly0, ly1 = up_axis32(X.shape[1], bool(variant & 2), X.device)
+    x0, x1, lx0, lx1 = up_axis32(X.shape[2], bool(variant & 1), X.device)
+    ly0, ly1 = ly0.double().view(1, -1, 1, 1), ly1.double().view(1, -1, 1, 1)
+    lx0, lx1 = lx0.double().view(1, 1, -1, 1), lx1.double().view(1, 1, -1, 1)
+    r0, r1 = X[:, y0], X[:, y1]
+    a, b, c, d = r0[:, :, x0], r0[:, :, x1], r1[:, :, x0], r1[:, :, x1]
+    y = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d)
+    Sb = ly0.abs() * (lx0.abs() * a.abs() + lx1.abs() * b.abs()) + ly1.abs() * (lx0.abs() * c.abs() + lx1.abs() * d.abs())
+    return y, Sb
+
+
+def up_elem_bound(mode, y, Sb):
+    """Elementwise bar on |got - y| of the up-sampling; u the unit roundoff of the plane type and c = GEMM_F32_FLOOR_FACTOR x
+    UP_F32_FLOOR_MEASURED = 18 the fp32 floor of the blend in units of 2^-24 Sb (measured on a CPU, see the constant).
+
+      one 16-bit plane    u |y| + c 2^-24 Sb       the stored value is the nearest 16-bit number to the fp32 blend
+      hi / lo pair        (3 u^2 + c 2^-24) Sb     the split of the output (u^2 |y| <= u^2 Sb), two spare
+      any fp16 plane      + 2^-25                  a plane value below 2^-14 is subnormal
+    A launch passes when ALL its elements are inside the bar for ONE of the four variants of upsample_ref64: a kernel uses one
+    arithmetic throughout."""
+    dt, pl = GEMM_PLANES[mode]
+    u = GEMM_U[mode]
+    floor = GEMM_F32_FLOOR_FACTOR * UP_F32_FLOOR_MEASURED * 2.0 ** -24 * Sb
+    bound = u * y.abs() + floor if pl == 1 else 3.0 * u * u * Sb + floor
+    if dt == torch.float16:
+        bound = bound + 2.0 ** -25
+    return bound
+
+
+def upsample_variants_inside(got, X, mode):
+    """{variant index: worst |err| / bound} of `got` against upsample_ref64(X, variant) / up_elem_bound for the four variants,
+    and the set of variants for which every element is inside."""
+    worst, inside = {}, set()
+    for v in range(4):
+        y, Sb = upsample_ref64(X, v)
+        w, bad = elements_outside(got, y, up_elem_bound(mode, y, Sb))
+        worst[v] = w
+        if not bad:
+            inside.add(v)
+    return worst, inside
+
+
+def head_tail_ref64(U, W2, b2, w4, b4, relu):
+    """fp64 reference of the head chain behind the up-sampling, from the up-sampled values U [B, Ho, Wo, 128] (NHWC):
+      h = relu(conv3x3(U, W2, pad 1) + b2)    S_h = conv(|U|, |W2|) + |b2|    (conv_acc64: one matrix product per tap)
+      y = w4 h + b4, relu(y) when `relu`
+    Returns (y, Sw, Hw, Hh) in the kernel's NCHW layout [B, C, Ho, Wo]: Sw = sum_n |w4| S_h, what a rounding inside the
+    convolution's sum is relative to once projected; Hw = sum_n |w4| |h| + |b4|, the same for the projection; Hh = sum_n |w4| |h|
+    alone, what a rounding of the stored h is relative to."""
+    W2, b2, w4, b4 = W2.double(), b2.double(), w4.double(), b4.double()
+    acc, Sacc = conv_acc64(U, W2, 1, 1, 1)
+    h = torch.relu(acc + b2)
+    Sh = Sacc + b2.abs()
+    y = h @ w4.t() + b4
+    if relu:
+        y = torch.relu(y)
+    Sw = Sh @ w4.abs().t()
+    Hh = h.abs() @ w4.abs().t()
+    Hw = Hh + b4.abs()
+    return y.permute(0, 3, 1, 2), Sw.permute(0, 3, 1, 2), Hw.permute(0, 3, 1, 2), Hh.permute(0, 3, 1, 2)
+
+
+def head_elem_bound(mode, y, Sw, Hw, io=None, h_planes=0, Hh=None):
+    """Elementwise bar on |got - y| of the head tail; F = GEMM_F32_FLOOR_FACTOR x GEMM_F32_FLOOR_MEASURED = 7.2e-7, u the unit
+    roundoff of the plane type, (y, Sw, Hw, Hh) from head_tail_ref64.
+
+      F (Sw + Hw)                 fp32: the convolution's accumulation and bias (relative to S_h, carried through |w4|; ReLU is
+                                  1-Lipschitz) and the 32-term projection with its bias (relative to sum |w4| |h| + |b4|)
+      + u^2 Sw                    plane modes: every product drops lo * lo, at most u^2 |U| |W2| per term
+      + u_io |y|                  a 16-bit result (io = "bf16" / "fp16")
+    The unfused chain stores h before the projection reads it (h_planes = 1 or 2), which the bias b4 has no part in:
+      + u Hh                      one plane: sum |w4| u |h|
+      + 3 u^2 Hh                  a pair: the split of h"""
+    u = GEMM_U[mode]
+    F = GEMM_F32_FLOOR_FACTOR * GEMM_F32_FLOOR_MEASURED
+    bound = F * (Sw + Hw)
+    if GEMM_PLANES[mode][1] == 2:
+        bound = bound + u * u * Sw
+    if h_planes == 1:
+        bound = bound + u * Hh
+    elif h_planes == 2:
+        bound = bound + 3.0 * u * u * Hh
+    if io in ("bf16", "fp16"):
+        bound = bound + GEMM_U[io] * y.abs()
+    return bound
+
+
+def head_out_ref64(X, Xlo, w, b, relu):
+    """(y, S) in fp64 of the 1x1 projection of x = X (+ Xlo, the lo plane, unless None) [B, HW, 32] -> NCHW [B, Cout, HW]:
+    y = w x + b (ReLU when `relu`), S = sum |w| |x| + |b|.  Row blocks of 2^20 pixels: the largest test has 4.2 M of them."""
+    w, b = w.double(), b.double()
+    B, HW, _ = X.shape
+    y = torch.empty(B, w.shape[0], HW, dtype=torch.float64, device=X.device)
+    S = torch.empty_like(y)
+    for i in range(0, HW, 1 << 20):
+        x = X[:, i:i + (1 << 20)].double()
+        if Xlo is not None:
+            x = x + Xlo[:, i:i + (1 << 20)].double()
+        v = x @ w.t() + b
+        y[:, :, i:i + (1 << 20)] = (torch.relu(v) if relu else v).transpose(1, 2)
+        S[:, :, i:i + (1 << 20)] = (x.abs() @ w.abs().t() + b.abs()).transpose(1, 2)
+    return y, S
