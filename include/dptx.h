@@ -939,6 +939,41 @@ int dptx_op_head_tail_io(int32_t dtype, const void* H0, const void* W2, const fl
 int dptx_op_head_out(int32_t dtype, const void* X, const float* w, const float* b, void* y, int32_t io, int32_t B,
                      int32_t HW, int32_t Cout, int32_t relu, void* stream);
 
+/* The glue kernels of the forward, one launch each (tests/test_gpu_glue.py).  dtype is BF16 / FP16 / BF16X3 / FP16X3; a 16-bit
+ * tensor is a hi/lo pair in the two-plane dtypes (planes of dptx_op_set_planes).  A null pointer, another dtype and every
+ * argument named below as refused -> DPTX_E_INVALID, before anything is launched or written. */
+/* The 16x16 patches of DPT-Large's patch embedding: x NCHW [B,3,H,W] of element type io -> P [B*(H/16)*(W/16)][768] 16-bit
+ * with k = (c*16 + ky)*16 + kx, each element rounded to nearest (split for a pair).  Refused: an unknown io, B < 1, H or W
+ * below 16 or no multiple of 16. */
+int dptx_op_patchify16(int32_t dtype, const void* x, int32_t io, void* P, int32_t B, int32_t H, int32_t W, void* stream);
+/* The re-layout behind a ConvTranspose2d with kernel == stride as a GEMM: G [B*h*w][(dy*k + dx)*C + c] ->
+ * Y [B][h*k][w*k][C] (NHWC) with Y[b][y*k + dy][x*k + dx][c] = G[(b, y, x)][(dy*k + dx)*C + c]; both planes of a pair are
+ * copied bit for bit.  Refused: B, h, w < 1, k outside 1..16, C < 8 or no multiple of 8, G == Y. */
+int dptx_op_depth_to_space(int32_t dtype, const void* G, void* Y, int32_t B, int32_t h, int32_t w, int32_t k, int32_t C,
+                           void* stream);
+/* _resize_pos_embed (vit.py:102-116): src fp32 [1 + g_old*g_old][C] -> dst fp32 [1 + gh*gw][C]; row 0 (cls) is copied, the
+ * grid rows are F.interpolate(mode="bilinear", align_corners=False) in ATen's fp32 index arithmetic.  Refused: g_old, gh, gw
+ * or C < 1, (gh*gw + 1)*C or g_old*g_old*C at or above 2^31. */
+int dptx_op_pos_resize(const float* src, float* dst, int32_t g_old, int32_t gh, int32_t gw, int32_t C, void* stream);
+/* The cls half of ProjectReadout: out[b*N + n] (fp32) = sum_k x[b*x_stride + k] W[n*ldw + w_off + k] + bias[n] (bias may be
+ * NULL).  x is fp32, or 16-bit of the dtype's type when x16 != 0 (BF16 / FP16 only); W is 16-bit, hi + lo in the two-plane
+ * dtypes (weight plane of dptx_op_set_planes).  Refused: B, N < 1, K < 4, K / w_off / ldw / x_stride no multiple of 4,
+ * w_off < 0, ldw < w_off + K, x_stride < K, x16 with a two-plane dtype. */
+int dptx_op_readout_cls(int32_t dtype, const void* x, int64_t x_stride, const void* W, int32_t ldw, int32_t w_off,
+                        const float* bias, float* out, int32_t B, int32_t N, int32_t K, int32_t x16, void* stream);
+/* dst[i] (16-bit) = src[i] (fp32) rounded to nearest, hi = rn(x), lo = rn(x - hi) for a pair.  Refused: n < 8, n % 8 != 0. */
+int dptx_op_cast_f32(int32_t dtype, const float* src, void* dst, int64_t n, void* stream);
+/* dst[i] (fp32) = src[i] (16-bit), fl32(hi + lo) for a pair: the export of a debug tap.  Refused: n < 8, n % 8 != 0
+ * (the rule of dptx_op_cast_f32, whose inverse it is). */
+int dptx_op_to_f32(int32_t dtype, const void* src, float* dst, int64_t n, void* stream);
+/* *amax_bits = max(*amax_bits, bits of max_i |X[i]|) (relu != 0: of max_i max(X[i], 0)) over the n 16-bit values of ONE plane
+ * (the two-plane dtypes name the plane type only): the fp8 calibration's reduction; a non-negative float orders like its
+ * bits.  Refused: n < 8, n % 8 != 0. */
+int dptx_op_amax(int32_t dtype, const void* X, int64_t n, int32_t relu, uint32_t* amax_bits, void* stream);
+/* *flag |= 1 if any of the n 16-bit values of ONE plane is an Inf or a NaN: the forward's range check.  Refused: n < 8,
+ * n % 8 != 0. */
+int dptx_op_nonfinite_scan(int32_t dtype, const void* X, int64_t n, uint32_t* flag, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * The reference's version-1 UNet (omnidata_tools/torch/modules/unet.py:8-105; checkpoint omnidata_unet_normal_v1.pth),
  * inference forward: downsample = 6, in_channels = 3, out_channels 1..4, GroupNorm(8) + ReLU behind every 3x3

@@ -507,8 +507,12 @@ hipError_t launch_depth_to_space(int mode, const void* G, void* Y, int B, int h,
 // ------------------------------------------------------------------------------ tap export
 template <int DT, int PL>
 __global__ void to_f32_kernel(const uint16_t* __restrict__ src, float* __restrict__ dst, size_t n, long long plane) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    dst[i] = T16<DT>::tof(src[i]) + (PL == 2 ? T16<DT>::tof(src[i + plane]) : 0.f);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    // one plane: the conversion alone (`+ 0.f` made +0 of a stored -0: tests/test_gpu_glue.py test_to_f32)
+    float v = T16<DT>::tof(src[i]);
+    if (PL == 2) v += T16<DT>::tof(src[i + plane]);
+    dst[i] = v;
+  }
 }
 hipError_t launch_to_f32(int mode, const void* src, float* dst, size_t n, Planes pl, hipStream_t stream) {
   const int grid = (int)min((n + 255) / 256, (size_t)8192);

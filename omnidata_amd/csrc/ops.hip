@@ -223,4 +223,63 @@ int dptx_op_upsample2x_strip(int32_t dtype, const void* X, void* Y, int32_t B, i
   return rc(launch_upsample2x_strip(dtype, X, Y, B, H, W, C, rows, (hipStream_t)stream));
 }
 
+// ---- the glue kernels of misc.hip, one launch each (tests/test_gpu_glue.py).  Every argument the launcher or the kernel would
+// mishandle -- a size its 32-bit index arithmetic overflows on, a count that leaves an empty grid, a stride that breaks the
+// alignment of its vector loads -- is refused here, before any launch.
+static bool op_dtype16(int32_t dtype) {
+  return dtype == DPTX_DTYPE_BF16 || dtype == DPTX_DTYPE_FP16 || dtype == DPTX_DTYPE_BF16X3 || dtype == DPTX_DTYPE_FP16X3;
+}
+static bool op_io(int32_t io) { return io == DPTX_IO_FP32 || io == DPTX_IO_BF16 || io == DPTX_IO_FP16; }
+
+int dptx_op_patchify16(int32_t dtype, const void* x, int32_t io, void* P, int32_t B, int32_t H, int32_t W, void* stream) {
+  if (!op_dtype16(dtype) || !op_io(io) || x == nullptr || P == nullptr) return DPTX_E_INVALID;
+  if (B < 1 || H < 16 || W < 16 || H % 16 != 0 || W % 16 != 0) return DPTX_E_INVALID;
+  return rc(launch_patchify16(dtype, x, io, P, B, H, W, g_op_planes, (hipStream_t)stream));
+}
+
+int dptx_op_depth_to_space(int32_t dtype, const void* G, void* Y, int32_t B, int32_t h, int32_t w, int32_t k, int32_t C,
+                           void* stream) {
+  if (!op_dtype16(dtype) || G == nullptr || Y == nullptr || G == Y) return DPTX_E_INVALID;
+  if (B < 1 || h < 1 || w < 1 || k < 1 || k > 16 || C < 8 || C % 8 != 0) return DPTX_E_INVALID;
+  if ((long long)h * k >= (1ll << 31) || (long long)w * k >= (1ll << 31)) return DPTX_E_INVALID;  // y*k + dy, x*k + dx are ints
+  return rc(launch_depth_to_space(dtype, G, Y, B, h, w, k, C, g_op_planes, (hipStream_t)stream));
+}
+
+int dptx_op_pos_resize(const float* src, float* dst, int32_t g_old, int32_t gh, int32_t gw, int32_t C, void* stream) {
+  if (src == nullptr || dst == nullptr || g_old < 1 || gh < 1 || gw < 1 || C < 1) return DPTX_E_INVALID;
+  // the kernel's element index, and its source offset (y * g_old + x) * C, are ints
+  if (((long long)gh * gw + 1) * C + 255 >= (1ll << 31) || (long long)g_old * g_old * C >= (1ll << 31)) return DPTX_E_INVALID;
+  return rc(launch_pos_resize(src, dst, g_old, gh, gw, C, (hipStream_t)stream));
+}
+
+int dptx_op_readout_cls(int32_t dtype, const void* x, int64_t x_stride, const void* W, int32_t ldw, int32_t w_off,
+                        const float* bias, float* out, int32_t B, int32_t N, int32_t K, int32_t x16, void* stream) {
+  if (!op_dtype16(dtype) || x == nullptr || W == nullptr || out == nullptr) return DPTX_E_INVALID;
+  if (B < 1 || N < 1 || K < 4 || K % 4 != 0 || w_off < 0 || w_off % 4 != 0 || ldw % 4 != 0 || ldw < w_off + K) return DPTX_E_INVALID;
+  if (x_stride < K || x_stride % 4 != 0 || (long long)B * N + 3 >= (1ll << 31)) return DPTX_E_INVALID;
+  if (x16 != 0 && mode_is_x3(dtype)) return DPTX_E_INVALID;  // the two-plane modes keep the fp32 stream: no lo plane of x is read
+  return rc(launch_readout_cls(dtype, (const float*)x, x_stride, W, ldw, w_off, bias, out, B, N, K, g_op_planes,
+                               (hipStream_t)stream, x16 != 0));
+}
+
+int dptx_op_cast_f32(int32_t dtype, const float* src, void* dst, int64_t n, void* stream) {
+  if (!op_dtype16(dtype) || src == nullptr || dst == nullptr || n < 8 || n % 8 != 0) return DPTX_E_INVALID;
+  return rc(launch_cast_f32(dtype, src, dst, (size_t)n, g_op_planes, (hipStream_t)stream));
+}
+
+int dptx_op_to_f32(int32_t dtype, const void* src, float* dst, int64_t n, void* stream) {
+  if (!op_dtype16(dtype) || src == nullptr || dst == nullptr || n < 8 || n % 8 != 0) return DPTX_E_INVALID;  // cast_f32's rule
+  return rc(launch_to_f32(dtype, src, dst, (size_t)n, g_op_planes, (hipStream_t)stream));
+}
+
+int dptx_op_amax(int32_t dtype, const void* X, int64_t n, int32_t relu, uint32_t* amax_bits, void* stream) {
+  if (!op_dtype16(dtype) || X == nullptr || amax_bits == nullptr || n < 8 || n % 8 != 0) return DPTX_E_INVALID;
+  return rc(launch_amax(dtype, X, (size_t)n, relu != 0, amax_bits, (hipStream_t)stream));
+}
+
+int dptx_op_nonfinite_scan(int32_t dtype, const void* X, int64_t n, uint32_t* flag, void* stream) {
+  if (!op_dtype16(dtype) || X == nullptr || flag == nullptr || n < 8 || n % 8 != 0) return DPTX_E_INVALID;
+  return rc(launch_nonfinite_scan(dtype, X, (size_t)n, flag, (hipStream_t)stream));
+}
+
 }  // extern "C"

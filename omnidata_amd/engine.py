@@ -164,6 +164,14 @@ ABI = [
     ("dptx_op_head_tail", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_op_head_tail_io", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_op_head_out", C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("dptx_op_patchify16", C.c_int, [_i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+    ("dptx_op_depth_to_space", C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("dptx_op_pos_resize", C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    ("dptx_op_readout_cls", C.c_int, [_i32, _vp, C.c_int64, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    ("dptx_op_cast_f32", C.c_int, [_i32, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_op_to_f32", C.c_int, [_i32, _vp, _vp, C.c_int64, _vp]),
+    ("dptx_op_amax", C.c_int, [_i32, _vp, C.c_int64, _i32, _vp, _vp]),
+    ("dptx_op_nonfinite_scan", C.c_int, [_i32, _vp, C.c_int64, _vp, _vp]),
     # the version-1 UNet (omnidata_amd/unet.py): a handle type of its own, and the op-level entry points of its kernels
     ("dptx_unet_default_config", None, [_vp]),
     ("dptx_unet_create", C.c_int, [C.POINTER(_vp), _vp]),

@@ -410,7 +410,7 @@ def conv_ref64(X, Wt, bias=None, R=None, stride=1, pad_t=0, pad_l=0, Ho=None, Wo
     return epilogue_ref64(*conv_acc64(X, Wt, stride, pad_t, pad_l, Ho, Wo, a_relu), bias, R, act)
 
 
-def gemm_elem_bound(mode, y, S, act, c_fp32=False, planes=None):
+def gemm_elem_bound(mode, y, S, act, c_fp32=False, planes=None, floor_measured=None):
     """Elementwise bar on |got - y| of a GEMM / convolution output; u = 2^-8 (bf16) / 2^-11 (fp16) the unit roundoff and
     F = GEMM_F32_FLOOR_FACTOR x GEMM_F32_FLOOR_MEASURED = 7.2e-7 the fp32 floor (accumulation order, bias and residual adds).
 
@@ -422,11 +422,12 @@ def gemm_elem_bound(mode, y, S, act, c_fp32=False, planes=None):
       act == 2               F S -> 1.13 F S + 2e-6    1.13 = max |gelu'|; 2e-6 = twice the absolute error that
                                                        tests/test_gelu_formula.py pins for the device formula
     ReLU is 1-Lipschitz and changes nothing.  planes: how many planes the OUTPUT has where that is not the mode's own count
-    (the epi2 forms write a pair from a one-plane product; c_hi_only writes one plane from a two-plane kernel)."""
+    (the epi2 forms write a pair from a one-plane product; c_hi_only writes one plane from a two-plane kernel).
+    floor_measured: the measured fp32 floor where the kernel has one of its own (the stem: STEM_F32_FLOOR_MEASURED)."""
     dt, pl = GEMM_PLANES[mode]
     pl = pl if planes is None else planes
     u = GEMM_U[mode]
-    F = GEMM_F32_FLOOR_FACTOR * GEMM_F32_FLOOR_MEASURED
+    F = GEMM_F32_FLOOR_FACTOR * (GEMM_F32_FLOOR_MEASURED if floor_measured is None else floor_measured)
     floor = 1.13 * F * S + 2e-6 if act == 2 else F * S
     if c_fp32:
         return floor + u * u * S if GEMM_PLANES[mode][1] == 2 else floor
@@ -617,3 +618,305 @@ def head_out_ref64(X, Xlo, w, b, relu):
         y[:, :, i:i + (1 << 20)] = (torch.relu(v) if relu else v).transpose(1, 2)
         S[:, :, i:i + (1 << 20)] = (x.abs() @ w.abs().t() + b.abs()).transpose(1, 2)
     return y, S
+
+
+# ------------------------------------------------------------------ the stem and the glue kernels, judged element by element
+# The stem convolution (csrc/stem.hip), GroupNorm (+ ReLU + max-pool) (csrc/norm.hip) and the position-embedding resize
+# (csrc/misc.hip) against fp64.  One number per tensor, or per (image, group), lets a truncating store, a dropped window tap, a
+# wrong value in a small channel or at a dim pixel pass; the helpers below give operands with a scale of their own per pixel
+# and channel, fp64 references with the magnitude sums a bound is relative to, and the bars on every single element.  Pure
+# torch, any device.  tests/test_stem_bound_host.py measures the floors and shows on a CPU which mistakes the bars reject;
+# profiles/stem_elements.md has the figures.
+
+STEM_SHAPES = ((1, 8, 8), (3, 16, 40), (1, 8, 256), (1, 16, 136), (2, 24, 264))                     # (B, H, W)
+STEM_IO = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+POOL_SHAPES = ((1, 2, 2, 64), (2, 4, 6, 64), (3, 16, 24, 64), (1, 34, 30, 64), (2, 32, 48, 64), (1, 96, 96, 64),
+               (2, 8, 8, 128))                                                                       # (B, H, W, C)
+GN_ELEM_CASES = ((2, 100, 64, 1, False), (1, 33, 512, 1, False), (3, 300, 256, 0, True), (2, 40, 1024, 1, True),
+                 (2, 2304, 128, 1, True))                                                            # (B, HW, C, relu, residual)
+POS_GRIDS = ((12, 32), (1, 1), (40, 24), (64, 48), (23, 25))                                         # (gh, gw)
+# fp32 floor of the stem: the largest |y32 - y| / S over STEM_SHAPES x the four modes x the three image types (stem_operands,
+# seed 0), y32 the fp32 model of tests/test_stem_bound_host.py that accumulates in the kernel's order -- eleven k-steps of 16
+# (two (c, ky) rows of 8 taps) in ascending order, one fp32 addition per MFMA -- with nothing rounded behind the operands, y and
+# S from stem_ref64.  K is 147 and the accumulator takes eleven (33 in the plane modes) rounded additions of partial sums of
+# either sign, which reads above the dense GEMM's 1.8e-7.  Measured against the reference, never against the kernel;
+# test_stem_floor_is_what_the_bound_uses re-measures it.
+STEM_F32_FLOOR_MEASURED = 3.2e-7
+# fp32 floor of GroupNorm (+ ReLU + max-pool) in units of 2^-24 T: the largest |y32 - y| / (2^-24 T) over POOL_SHAPES and
+# GN_ELEM_CASES x the four modes, y32 the fp32 model of tests/test_stem_bound_host.py -- fp32 (sum, sum of squares) per
+# gn_chunks record, fp64 across the records, mean and rstd rounded to fp32, a = rstd gamma rounded, d = fma(-a, mean, beta),
+# fma(x, a, d) --, y and T from gn_pool_ref64 / gn_ref64.  Measured against the reference, never against the kernel;
+# test_gn_floor_is_what_the_bound_uses re-measures it.
+GN_F32_FLOOR_MEASURED = 9.1
+# fp32 error of a source coordinate of pos_resize_kernel, s = max((dst + 0.5) r - 0.5, 0) with r = fl(24 / g): three roundings.
+# r carries 2^-24 relatively, which (dst + 0.5) r < 32 turns into 2^-19 at most; the product below 32 is rounded by half an
+# ulp, 2^-20 at most; so is the difference (exact above 0.5).  2^-19 + 2^-20 + 2^-20 = 2^-18.  l1 = s - i0 is exact.
+POS_COORD_ERR = 2.0 ** -18
+
+
+def plane_value(p):
+    """fp64 value of a (hi, lo) pair of gemm_operand_planes; lo may be None."""
+    return p[0].double() if p[1] is None else p[0].double() + p[1].double()
+
+
+def stem_operands(B, H, W, seed=0):
+    """(x [B, 3, H, W] NCHW, wp [64, 176], X [B, H, W, 3] NHWC, Wt [64, 7, 7, 3] OHWI) in fp64 (CPU), deterministic in `seed`:
+    scaled_conv_operands(B, H, W, 3, 64, 7, seed) -- every pixel carries 2^((7 p mod 13) - 6) and a sign per value, every
+    output channel 2^((5 n mod 7) - 3).  x and X, wp and Wt hold the same values: x and wp are what the kernel takes (wp packed
+    with k = (c 7 + ky) 8 + kx, zero in tap kx = 7 and in k >= 168), X and Wt what conv_ref64 takes."""
+    X, Wt, _, _ = scaled_conv_operands(B, H, W, 3, 64, 7, seed)
+    wp = torch.zeros(64, 176, dtype=torch.float64)
+    wp[:, :168].view(64, 3, 7, 8)[..., :7] = Wt.permute(0, 3, 1, 2)
+    return X.permute(0, 3, 1, 2).contiguous(), wp, X, Wt
+
+
+def stem_image_planes(x, mode, io):
+    """(hi, lo) planes of the image as the kernel forms them: the caller's values rounded to the image type `io` first, then
+    rounded to the mode's plane type, or split hi = dt(x), lo = dt(x - hi) in the plane modes."""
+    return gemm_operand_planes(x.float().to(STEM_IO[io]).float(), mode)
+
+
+def stem_ref64(X, Wt, mode, io="fp32"):
+    """fp64 (y, S) [B, H/2, W/2, 64] of the stem convolution of the values the MFMAs read: conv_ref64(x', w', stride 2, one
+    matrix product per tap) with TF-SAME padding (2 above and left, 3 below and right), x' = the image X [B, H, W, 3] rounded
+    to `io` and then to the plane type (hi + lo in the plane modes), w' = the weight Wt [64, 7, 7, 3] rounded or split the
+    same way."""
+    H, W = X.shape[1], X.shape[2]
+    xv = plane_value(stem_image_planes(X, mode, io))
+    wv = plane_value(gemm_operand_planes(Wt, mode))
+    return conv_ref64(xv, wv, stride=2, pad_t=2, pad_l=2, Ho=H // 2, Wo=W // 2)
+
+
+def stem_elem_bound(mode, y, S):
+    """gemm_elem_bound with the stem's own fp32 floor F = GEMM_F32_FLOOR_FACTOR x STEM_F32_FLOOR_MEASURED:
+    u |y| + F S (one plane), (3 u^2 + F) S (a pair), + 2^-25 with an fp16 plane."""
+    return gemm_elem_bound(mode, y, S, 0, floor_measured=STEM_F32_FLOOR_MEASURED)
+
+
+def pool_operands(B, H, W, C, seed=0):
+    """X [B, H W, C] fp64 (CPU): nhwc_with_group_stats times 2^((3 p mod 5) - 2), p the flat pixel index over the batch, so
+    that the taps of one pooling window differ in size (adjacent pixels by 2^3 or 2^2) and a dropped or misplaced tap moves
+    the maximum.  |values| < 2^5 * 6: inside fp16."""
+    X = nhwc_with_group_stats(B, H * W, C, seed=seed)
+    f = torch.exp2(((3 * torch.arange(B * H * W)) % 5 - 2).double()).view(B, H * W, 1)
+    return X * f
+
+
+def gn_params(C, seed=0):
+    """(gamma [C], beta [C]) fp32 (CPU) of either sign, deterministic in `seed`."""
+    g = torch.Generator().manual_seed(5000 + seed)
+    return torch.randn(C, generator=g), torch.randn(C, generator=g)
+
+
+def gn_affine64(X, gamma, beta, eps, groups=32):
+    """(a, d, mean) [B, 1, C] fp64 of GroupNorm(groups) of X [B, HW, C]: the biased statistics of every (image, group) in fp64,
+    a = gamma rstd, d = beta - mean a, so that gn(x) = x a + d."""
+    X = X.double()
+    B, HW, C = X.shape
+    cpg = C // groups
+    xg = X.reshape(B, HW, groups, cpg)
+    mean = xg.mean((1, 3))
+    var = ((xg - mean.view(B, 1, groups, 1)) ** 2).mean((1, 3))
+    rstd = 1.0 / torch.sqrt(var + eps)
+    a = gamma.double().view(1, C) * rstd.repeat_interleave(cpg, 1)
+    m = mean.repeat_interleave(cpg, 1)
+    d = beta.double().view(1, C) - m * a
+    return a.view(B, 1, C), d.view(B, 1, C), m.view(B, 1, C)
+
+
+def window_max(v, H, W, y_from=0, size=3):
+    """max over the window {2 o + y_from .. 2 o + y_from + size - 1}^2 within the image of v [B, H, W, C] -> [B, (H + 1) / 2,
+    (W + 1) / 2, C]; taps outside the image count as -inf (MaxPool2dSame(3, 2) of an even size: y_from 0, size 3)."""
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    lead = -min(y_from, 0)
+    vp = torch.nn.functional.pad(v, [0, 0, lead, 2 * Wo + size + 1, lead, 2 * Ho + size + 1], value=float("-inf"))
+    out = None
+    for dy in range(size):
+        for dx in range(size):
+            y0, x0 = dy + y_from + lead, dx + y_from + lead
+            s = vp[:, y0:y0 + 2 * Ho - 1:2, x0:x0 + 2 * Wo - 1:2]
+            out = s if out is None else torch.maximum(out, s)
+    return out
+
+
+def gn_ref64(X, gamma, beta, R=None, relu=0, eps=1e-5):
+    """fp64 (y, T) [B, HW, C] of GroupNorm(32) (+ residual R, + ReLU) of the stored values X [B, HW, C] (hi + lo in the plane
+    modes): y = relu(x a + d + R), T = |x| |a| + |mean| |a| + |beta| + |R|, what a rounding of the statistics, of the affine or
+    of the sum is relative to."""
+    X = X.double()
+    a, d, m = gn_affine64(X, gamma, beta, eps)
+    y = X * a + d
+    T = X.abs() * a.abs() + m.abs() * a.abs() + beta.double().abs().view(1, 1, -1)
+    if R is not None:
+        y, T = y + R.double(), T + R.double().abs()
+    return (torch.relu(y) if relu else y), T
+
+
+def gn_pool_ref64(X, gamma, beta, H, W, eps=1e-5):
+    """fp64 (y, T) [B, H/2, W/2, C] of the stem's GroupNorm(32) + ReLU + MaxPool2dSame(3, 2) of the stored values X [B, H W, C]:
+    v = x a + d with the fp64 statistics of every (image, group); y = max(0, max of v over the window {2 oy .. 2 oy + 2} x
+    {2 ox .. 2 ox + 2} within the image); T = max over the same window of |x| |a| + |mean| |a| + |beta|."""
+    X = X.double()
+    B, _, C = X.shape
+    v, T = gn_ref64(X, gamma, beta, None, 0, eps)
+    y = torch.relu(window_max(v.view(B, H, W, C), H, W))
+    return y, window_max(T.view(B, H, W, C), H, W)
+
+
+def gn_elem_bound(mode, y, T):
+    """Elementwise bar on |got - y| of GroupNorm (+ ReLU + max-pool); u the unit roundoff of the plane type, (y, T) from
+    gn_ref64 / gn_pool_ref64 and c = GEMM_F32_FLOOR_FACTOR x GN_F32_FLOOR_MEASURED the fp32 floor in units of 2^-24 T.
+
+      one 16-bit plane    u |y| + c 2^-24 T        the stored value is the nearest 16-bit number to the fp32 result
+      hi / lo pair        (3 u^2 + c 2^-24) T      the split of the output, two spare
+      any fp16 plane      + 2^-25                  a plane value below 2^-14 is subnormal
+    ReLU and the maximum are 1-Lipschitz and monotone and change nothing."""
+    dt, pl = GEMM_PLANES[mode]
+    u = GEMM_U[mode]
+    floor = GEMM_F32_FLOOR_FACTOR * GN_F32_FLOOR_MEASURED * 2.0 ** -24 * T
+    bound = u * y.abs() + floor if pl == 1 else 3.0 * u * u * T + floor
+    if dt == torch.float16:
+        bound = bound + 2.0 ** -25
+    return bound
+
+
+def scaled_pos_embed(C, seed=0, g_old=24):
+    """pos_embed [1 + g_old^2, C] as fp32 values in fp64 (CPU): 2^((7 p mod 13) - 6) 2^((5 c mod 7) - 3) N(0, 1), p the row --
+    the family of scaled_head_operands: every source pixel and every channel has a scale of its own."""
+    g = torch.Generator().manual_seed(6000 + seed)
+    n = 1 + g_old * g_old
+    x = torch.randn(n, C, generator=g, dtype=torch.float64) * torch.exp2(_row_exp(n)).view(n, 1) * torch.exp2(_col_exp(C))
+    return x.float().double()
+
+
+def pos_axis64(g_old, g):
+    """(i0, i1, l0, l1) of one axis of the half-pixel (align_corners=False) resize g_old -> g: the source coordinate is the
+    exact rational s = max(((2 dst + 1) g_old - g) / (2 g), 0) (integers up to the one division), i0 = floor(s)."""
+    dst = torch.arange(g, dtype=torch.float64)
+    s = (((2.0 * dst + 1.0) * g_old - g) / (2.0 * g)).clamp_min(0.0)
+    i0 = s.floor().to(torch.int64).clamp_max(g_old - 1)
+    i1 = i0 + (i0 < g_old - 1).to(torch.int64)
+    l1 = s - i0.double()
+    return i0, i1, 1.0 - l1, l1
+
+
+def pos_resize_ref64(src, g_old, gh, gw):
+    """fp64 (y, Sb, L) [1 + gh gw, C] of _resize_pos_embed of src [1 + g_old^2, C]: row 0 is the cls row (Sb = |y|, L = 0); the
+    grid rows are the bilinear blend ly0 (lx0 a + lx1 b) + ly1 (lx0 c + lx1 d) at pos_axis64's coordinates, Sb the same blend
+    of |values|, and L the largest |a| + |b| + |c| + |d| over the 3 x 3 source cells around the cell (y0, x0): the interpolant
+    is continuous and piecewise linear, so a coordinate that is off by e, even into a neighbouring cell, moves the value by at
+    most e L."""
+    src = src.double()
+    C = src.shape[1]
+    G = src[1:].view(g_old, g_old, C)
+    y0, y1, ly0, ly1 = pos_axis64(g_old, gh)
+    x0, x1, lx0, lx1 = pos_axis64(g_old, gw)
+    ly0, ly1 = ly0.view(-1, 1, 1), ly1.view(-1, 1, 1)
+    lx0, lx1 = lx0.view(1, -1, 1), lx1.view(1, -1, 1)
+    a, b, c, d = G[y0][:, x0], G[y0][:, x1], G[y1][:, x0], G[y1][:, x1]
+    y = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d)
+    Sb = ly0 * (lx0 * a.abs() + lx1 * b.abs()) + ly1 * (lx0 * c.abs() + lx1 * d.abs())
+    nxt = torch.arange(g_old).add(1).clamp_max(g_old - 1)
+    A = G.abs()
+    cell = A + A[:, nxt] + A[nxt] + A[nxt][:, nxt]                                     # corner sum of the cell at (y, x)
+    cp = torch.nn.functional.pad(cell, [0, 0, 1, 1, 1, 1], value=0.0)
+    Lc = None
+    for dy in range(3):
+        for dx in range(3):
+            s = cp[dy:dy + g_old, dx:dx + g_old]
+            Lc = s if Lc is None else torch.maximum(Lc, s)
+    L = Lc[y0][:, x0]
+    z = torch.zeros(1, C, dtype=torch.float64)
+    return (torch.cat([src[:1], y.reshape(-1, C)]), torch.cat([src[:1].abs(), Sb.reshape(-1, C)]), torch.cat([z, L.reshape(-1, C)]))
+
+
+def pos_elem_bound(Sb, L):
+    """Elementwise bar on |got - y| of the position-embedding resize: c 2^-24 Sb + e_s L with c = GEMM_F32_FLOOR_FACTOR x
+    UP_F32_FLOOR_MEASURED = 18, the measured floor of the x2 up-sampling's blend (the same six products and three sums), and
+    e_s = POS_COORD_ERR = 2^-18 the fp32 error of a source coordinate."""
+    return GEMM_F32_FLOOR_FACTOR * UP_F32_FLOOR_MEASURED * 2.0 ** -24 * Sb + POS_COORD_ERR * L
+
+
+# ------------------------------------------------------------------ outputs behind guards
+SENTINEL = 0xFFC1 - 0x10000  # int16 view of 0xFFC1: a NaN in bf16 and in fp16, which no kernel under test stores
+
+
+class debug_flags:
+    """with debug_flags(v): the launches inside run under dptx_debug_set_gemm_flags(v); 0 afterwards"""
+
+    def __init__(self, value):
+        self.value = value
+
+    def __enter__(self):
+        assert load_library().dptx_debug_set_gemm_flags(self.value) == 0
+
+    def __exit__(self, *exc):
+        load_library().dptx_debug_set_gemm_flags(0)
+
+
+class Target:
+    """An output of n 16-bit elements (a hi / lo pair in the plane modes) pre-filled with a NaN, `guard` elements of the same
+    NaN in front of it and behind it, and the inputs of one launch.  One plane: buffers of their own.  A pair: everything in
+    one PlaneArena whose both planes are NaN wherever no input lies -- after the launch, whatever is not the output must
+    hold the bits it held before."""
+
+    def __init__(self, mode, n, guard, input_elems=0):
+        self.mode, self.n, self.guard = mode, n, guard
+        self.dt, self.pl = GEMM_PLANES[mode]
+        if self.pl == 2:
+            self.arena = PlaneArena(input_elems + n + 2 * guard + 4096, "cuda:0", self.dt)
+            self.arena.buf.view(torch.int16).fill_(SENTINEL)
+        else:
+            self.arena = None
+
+    def put(self, t):
+        """an input: the values t rounded to the plane type, or split into the arena's planes"""
+        return self.arena.put(t) if self.pl == 2 else t.float().to(self.dt).to("cuda:0").contiguous()
+
+    def out(self):
+        if self.pl == 2:
+            self.arena.empty(self.guard)
+            self.y = self.arena.empty(self.n)
+            self.arena.empty(self.guard)
+            self.before = self.arena.buf.clone()
+        else:
+            self.buf = torch.full((self.n + 2 * self.guard,), SENTINEL, device="cuda:0", dtype=torch.int16)
+            self.y = self.buf[self.guard:self.guard + self.n].view(self.dt)
+        return self.y
+
+    def check(self):
+        """nothing but the output was written"""
+        torch.cuda.synchronize()
+        if self.pl == 2:
+            o = (self.y.data_ptr() - self.arena.buf.data_ptr()) // 2
+            keep = torch.ones(self.arena.total, dtype=torch.bool, device="cuda:0")
+            keep[o:o + self.n] = False
+            a, b = self.arena.buf.view(torch.int16), self.before.view(torch.int16)
+            assert torch.equal(a[:, keep], b[:, keep]), "written outside the output"
+        else:
+            g = self.guard
+            assert bool((self.buf[:g] == SENTINEL).all()) and bool((self.buf[g + self.n:] == SENTINEL).all()), "written outside the output"
+
+    def planes(self):
+        """(hi, lo) planes of the output on the device, lo None for one plane, after check()"""
+        self.check()
+        return self.y, (self.arena.lo(self.y) if self.pl == 2 else None)
+
+    def value(self):
+        """fp64 value of the output (hi + lo) on the CPU, after check()"""
+        self.check()
+        return (self.arena.value(self.y) if self.pl == 2 else self.y.double()).cpu()
+
+    def close(self):
+        if self.arena is not None:
+            self.arena.release()
+
+
+def guarded_f32(n, guard):
+    """(whole buffer, view of the n payload elements) of fp32 NaNs: `guard` of them in front of and behind the payload"""
+    buf = torch.full((n + 2 * guard,), float("nan"), device="cuda:0")
+    return buf, buf[guard:guard + n]
+
+
+def f32_guards_intact(buf, n, guard):
+    return bool(torch.isnan(buf[:guard]).all()) and bool(torch.isnan(buf[guard + n:]).all())

@@ -310,7 +310,8 @@ def test_upsample2x_align_corners(dtype, B, H, C):
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 @pytest.mark.parametrize("B,H,W", [(2, 384, 384), (1, 64, 128), (3, 96, 256), (2, 256, 320), (1, 96, 160), (1, 64, 96)])
 def test_fused_stem_conv(dtype, B, H, W):
-    """7x7 stride-2 TF-SAME conv straight from the NCHW fp32 image (no im2col)."""
+    """7x7 stride-2 TF-SAME conv straight from the NCHW fp32 image (no im2col).  One number per tensor on positive images of one
+    scale: tests/test_gpu_stem_elements.py judges every element of this kernel, in all four modes, against fp64."""
     lib = load_library()
     x = torch.rand(B, 3, H, W, device=DEV)
     w = torch.randn(64, 3, 7, 7, device=DEV) * 147 ** -0.5
@@ -485,7 +486,8 @@ def maxpool_same_ref(y):
 @pytest.mark.parametrize("B,H,W", [(1, 192, 192), (3, 32, 48), (2, 144, 224), (3, 64, 96)])
 def test_gn_relu_maxpool_per_group_statistics(dtype, B, H, W):
     """The stem's GroupNorm + ReLU + MaxPool2dSame(3, 2) (gn_relu_maxpool_kernel) at the 384 stem (192 x 192 x 64), flex stems
-    and B = 3, every (image, group) on its own statistics, against timm's module order in fp64, per (image, group)."""
+    and B = 3, every (image, group) on its own statistics, against timm's module order in fp64, per (image, group).  Every
+    single element, with window taps of different sizes, is judged in tests/test_gpu_stem_elements.py."""
     lib = load_library()
     C = 64
     X = nhwc_with_group_stats(B, H * W, C, seed=70 + H).to(TDT[dtype]).to(DEV).view(B, H, W, C)

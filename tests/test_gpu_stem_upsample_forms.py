@@ -88,7 +88,8 @@ def test_stem_new_form_equals_old_bitwise(dtype, io, case):
 @pytest.mark.parametrize("io", ["fp32", "bf16", "fp16"])
 @pytest.mark.parametrize("case", STEM_CASES)
 def test_stem_new_form_against_fp32(dtype, io, case):
-    """the reference and the bound of tests/test_gpu_ops.py::test_fused_stem_conv"""
+    """the reference and the bound of tests/test_gpu_ops.py::test_fused_stem_conv: one number per tensor.  Both forms are judged
+    element by element, on signed and scaled operands, in tests/test_gpu_stem_elements.py."""
     x, w, _ = stem_operands(dtype, io, case)
     ref = F.conv2d(F.pad(x.float().to(TDT[dtype]).float(), [2, 3, 2, 3]), w.float(), None, 2).permute(0, 2, 3, 1)
     y = run_stem(dtype, io, case, 0)
