@@ -797,6 +797,49 @@ int dptx_eval_depth(const float* pred, const float* target /*[B,1,H,W]*/, const 
 /* Per-pixel angles for tests and debugging (:43): ang [B][H][W] fp64, degrees, the mask not applied.  No workspace. */
 int dptx_eval_normal_pixels(const float* pred, const float* target, int32_t B, int32_t H, int32_t W, double* ang, void* stream);
 
+/* ---- scale-and-shift-aligned depth evaluation (no handle; DEVICE pointers) ----
+ * The depth network's output is defined up to a scale and a shift per image, so a depth checkpoint is judged on the
+ * prediction FITTED to the ground truth per image.  One call: the fit of every image, then every metric of the fitted
+ * prediction.  Same contract as the two sections it composes (MiDaS statistics, evaluation metrics): stream-ordered on
+ * `stream`, on the caller's workspace only, no allocation, no host synchronisation, no float atomics, bitwise reproducible,
+ * a per-image row the same alone and inside any batch.  Shapes as dptx_eval_depth.  A null pointer (`aligned` excepted),
+ * an unknown `align` or `flags` bit, a min_depth that is not positive and finite, a workspace that is too small or another
+ * shape -> DPTX_E_INVALID, before anything is launched.
+ * Coefficients, per image, from the stages of dptx_midas_stats (the same bits):
+ *   DPTX_EVAL_ALIGN_LSTSQ   scale, shift of compute_scale_and_shift(pred, target, mask) (midas_loss.py:10-30; DPTX_MIDAS_ALIGN),
+ *                           (0, 0) where det == 0;  aligned = scale p, then + shift;
+ *   DPTX_EVAL_ALIGN_MEDIAN  t_p, t_g, s_p, s_g of masked_shift_and_scale (:33-56; DPTX_MIDAS_SSI);  aligned =
+ *                           (p - t_p) / (s_p + 1e-6f), then (s_g + 1e-6f) times that, then + t_g.
+ * fp32, every step rounded on its own; with DPTX_EVAL_ALIGNED_CLAMP then clamped to [0, 1] (paper_code/test_depth.py:207; a NaN
+ * stays a NaN).  coeffs [B][2] fp32 = scale, shift; for MEDIAN the equivalent pair ((s_g + 1e-6f) / (s_p + 1e-6f), t_g - that
+ * t_p), for reporting only.  aligned (nullable) [B][1][H][W] receives the aligned value of every pixel, masked or not.
+ * out [B + 1][DPTX_EVAL_ALIGNED_FIELDS] fp64: rows 0 .. B - 1 the images, row B the whole batch (the reference's get_metrics
+ * on the stacked aligned batch), all from one pass.
+ *   Fields 0-7: the row of dptx_eval_depth for the aligned tensor, bit for bit (rows 0 .. B - 1: with DPTX_EVAL_PER_IMAGE; row
+ *   B: without): the same per-pixel fp64 arithmetic, block partition and summation order.
+ *   Fields 8-14, over the valid pixels only (selected by the mask, not multiplied by it), in fp64 with a_e = max(aligned,
+ *   min_depth), t_e = max(target, min_depth): abs_rel = mean |a_e - t_e| / t_e, sq_rel = mean (a_e - t_e)^2 / t_e, rmse =
+ *   sqrt(mean (a_e - t_e)^2), rmse_log = sqrt(mean (ln a_e - ln t_e)^2), delta1..3 = the fraction with max(a_e / t_e,
+ *   t_e / a_e) < 1.25, 1.5625, 1.953125 (a NaN compares false).
+ *   The delta counts are integers (counted per thread, exact in the fp64 rows of partial sums).
+ * A row with an empty mask gets n = 0 and NaN elsewhere, decided on the device.  Every other row is finite for finite inputs
+ * with one exception inherited from dptx_eval_depth: rel_error (field 6) divides by the target, so a VALID pixel with target
+ * == 0 makes it +inf (NaN if the aligned value is 0 there too) in its image's row and in row B; fields 8-14 floor the target
+ * and stay finite.  Inputs are assumed finite; non-finite ones touch only their own image's rows and row B.
+ * Host-only (no GPU needed): the workspace, with A(x) = x rounded up to a multiple of 256, nblk = min(ceil(ceil(H W / 4) /
+ * 256), 1024) (the blocks of dptx_eval_depth) and M = what dptx_midas_workspace_bytes(B, H, W, 1, .) gives:
+ *   *bytes = A(120 B nblk) + A(32 B) + M
+ * (the partial sums, the per-image statistics, the workspace of the statistics' stages).  One stream at a time per
+ * workspace, as above. */
+#define DPTX_EVAL_ALIGN_LSTSQ 1
+#define DPTX_EVAL_ALIGN_MEDIAN 2
+#define DPTX_EVAL_ALIGNED_CLAMP 1   /* flags: clamp the aligned value to [0, 1] */
+#define DPTX_EVAL_ALIGNED_FIELDS 15 /* the 8 of DPTX_EVAL_DEPTH_FIELDS, abs_rel, sq_rel, rmse, rmse_log, delta1, delta2, delta3 */
+int dptx_eval_aligned_workspace_bytes(int32_t B, int32_t H, int32_t W, int64_t* bytes);
+int dptx_eval_depth_aligned(const float* pred, const float* target /*[B,1,H,W]*/, const uint8_t* mask /*[B,H,W]*/, int32_t B,
+                            int32_t H, int32_t W, int32_t align, int32_t flags, float min_depth, double* out /*[B + 1][15]*/,
+                            float* coeffs /*[B][2]*/, float* aligned /*nullable*/, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- op-level entry points (unit tests + micro-benchmarks of the individual kernels) ----
  * dtype: DPTX_DTYPE_*.  All pointers are device pointers; row-major / NHWC. */
 

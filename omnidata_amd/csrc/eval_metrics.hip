@@ -21,12 +21,19 @@
 // Numerics: per-pixel arithmetic in fp64 on the fp32 inputs, no contraction in this unit: every product, sum, sqrt and
 // division is the correctly rounded one, as on the CPU.  Masking follows the reference: every term is computed for every
 // pixel and multiplied by the 0 / 1 mask, so a non-finite term outside the mask poisons its sum as it does there.
+//
+// dptx_eval_depth_aligned (a' below) is the depth form of a prediction that is first fitted to the target per image, by
+// least squares or by median and mean deviation: midas_loss.hip's stats stages (midas_stats.h) leave every image's
+// coefficients in the workspace, one terms pass aligns each pixel in fp32 as it loads it and adds the depth form's eight
+// sums and seven more (AbsRel, SqRel, RMSE, RMSE-log, delta < 1.25^k), and one finalize launch writes the B per-image rows
+// and the batch row.  The aligned tensor is never written unless the caller asks for it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
 #include "../../include/dptx.h"
+#include "midas_stats.h"
 #include "select.h"
 
 #pragma clang fp contract(off)
@@ -210,6 +217,21 @@ __global__ __launch_bounds__(TPB) void ev_normal_kernel(const float* __restrict_
   }
 }
 
+// the eight sums of the depth form for one pixel (p, t: the fp64 of the fp32 values, m: the 0 / 1 mask)
+__device__ __forceinline__ void depth_terms(double p, double t, double m, double* v) {
+  const double diff = fabs(p - t) * m;  // :61
+  v[0] += m;
+  v[1] += diff;
+  v[2] += diff * diff;
+  v[3] += log(1.0 + 64.0 * diff) * m;                              // :64
+  const double dlog = fabs((log(1.0 + 64.0 * p) - log(1.0 + 64.0 * t)) * m);  // :68, :70
+  v[4] += dlog;
+  v[5] += dlog * dlog;
+  v[6] += (diff / t) * m;                                          // :72: 0 / 0 outside the mask where target == 0
+  const double ir = 1.0 / (1.0 + 64.0 * p) - 1.0 / (1.0 + 64.0 * t);  // :74
+  v[7] += (ir * ir) * m;
+}
+
 // partial row of the depth form: the count, sums of |diff| m, its square, log(1 + 64 |diff| m) m, |dlog m|, its square,
 // (|diff| m / t) m, (1 / (1 + 64 p) - 1 / (1 + 64 t))^2 m
 template <bool VEC>
@@ -228,22 +250,122 @@ __global__ __launch_bounds__(TPB) void ev_depth_kernel(const float* __restrict__
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if (!u.in[k]) continue;
-        const double p = (double)u.p[k][0], t = (double)u.t[k][0];
-        const double m = u.m[k] ? 1.0 : 0.0;
-        const double diff = fabs(p - t) * m;  // :61
-        v[0] += m;
-        v[1] += diff;
-        v[2] += diff * diff;
-        v[3] += log(1.0 + 64.0 * diff) * m;                              // :64
-        const double dlog = fabs((log(1.0 + 64.0 * p) - log(1.0 + 64.0 * t)) * m);  // :68, :70
-        v[4] += dlog;
-        v[5] += dlog * dlog;
-        v[6] += (diff / t) * m;                                          // :72: 0 / 0 outside the mask where target == 0
-        const double ir = 1.0 / (1.0 + 64.0 * p) - 1.0 / (1.0 + 64.0 * t);  // :74
-        v[7] += (ir * ir) * m;
+        depth_terms((double)u.p[k][0], (double)u.t[k][0], u.m[k] ? 1.0 : 0.0, v);
       }
     }
     block_sum<NS>(v, red, part + (b * gridDim.x + blockIdx.x) * NS);
+  }
+}
+
+// ---------------------------------------------------------------- a'. the aligned depth form (dptx_eval_depth_aligned)
+// The prediction is first mapped onto the target per image, with the coefficients that midas_loss.hip's stats stages left
+// in the workspace (midas_stats.h: stats [B][DPTX_MIDAS_STATS] = t_p, t_g, s_p, s_g, n, scale, shift, argmedian), in fp32
+// with every step rounded on its own:
+//   LSTSQ   a = scale p, then a + shift                             (compute_scale_and_shift, midas_loss.py:10-30)
+//   MEDIAN  pa = (p - t_p) / (s_p + 1e-6f), pa (s_g + 1e-6f), + t_g (masked_shift_and_scale, :33-56)
+// then clamped to [0, 1] on request (a NaN stays a NaN).  Sums 0..7 are those of the depth form on that value, in the same
+// partition and order; sums 8..14 are the benchmark fields over the VALID pixels only (selected, not multiplied), with
+// a_e = max(a, min_depth), t_e = max(t, min_depth): |a_e - t_e| / t_e, (a_e - t_e)^2 / t_e, (a_e - t_e)^2,
+// (ln a_e - ln t_e)^2 and the counts of max(a_e / t_e, t_e / a_e) < 1.25, 1.25^2, 1.25^3 (a NaN compares false).  A thread
+// counts in integers; its counts (at most 4 per unit it takes, far below 2^32) enter the block's partial row as fp64, where
+// sums of integers below 2^53 are exact: the row's count is the integer it would be in any order.
+constexpr int NA = DPTX_EVAL_ALIGNED_FIELDS;  // sums per partial row of the aligned form
+constexpr float ALIGN_EPS = 1e-6f;
+static_assert(NA == 15 && DPTX_MIDAS_STATS == 8, "aligned fields");
+
+struct Coef {
+  float scale, shift;    // LSTSQ
+  float tp, tg, dp, dg;  // MEDIAN: the medians and s + 1e-6f
+};
+
+__device__ __forceinline__ Coef load_coef(const float* __restrict__ st /*[DPTX_MIDAS_STATS]*/) {
+  Coef c;
+  c.tp = st[0], c.tg = st[1];
+  c.dp = st[2] + ALIGN_EPS, c.dg = st[3] + ALIGN_EPS;
+  c.scale = st[5], c.shift = st[6];
+  return c;
+}
+
+template <bool MEDIAN>
+__device__ __forceinline__ float align_value(float p, const Coef& c, bool clamp) {
+  float a;
+  if constexpr (MEDIAN) {
+    const float pa = (p - c.tp) / c.dp;
+    a = pa * c.dg;
+    a = a + c.tg;
+  } else {
+    a = c.scale * p;
+    a = a + c.shift;
+  }
+  if (clamp) a = a < 0.0f ? 0.0f : (a > 1.0f ? 1.0f : a);  // torch.clamp: NaN stays NaN
+  return a;
+}
+
+template <bool VEC, bool MEDIAN>
+__global__ __launch_bounds__(TPB) void ev_aligned_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                         const uint8_t* __restrict__ mask, int B, int64_t HW, int64_t units,
+                                                         int64_t per_block, const float* __restrict__ stats, int clamp,
+                                                         double min_depth, float* __restrict__ coeffs /*[B][2]*/,
+                                                         float* __restrict__ aligned_out /*nullable*/,
+                                                         double* __restrict__ part /*[B][nblk][NA]*/) {
+  __shared__ double red[4 * NA];
+  const int64_t lo = (int64_t)blockIdx.x * per_block, hi = lo + per_block < units ? lo + per_block : units;
+  for (int64_t b = blockIdx.y; b < B; b += gridDim.y) {
+    const Coef c = load_coef(stats + b * DPTX_MIDAS_STATS);  // block-uniform
+    if (blockIdx.x == 0 && threadIdx.x == 0) {               // the reported pair; MEDIAN: the equivalent scale and shift
+      float cs = c.scale, ch = c.shift;
+      if constexpr (MEDIAN) {
+        cs = c.dg / c.dp;
+        const float q = cs * c.tp;
+        ch = c.tg - q;
+      }
+      coeffs[2 * b] = cs;
+      coeffs[2 * b + 1] = ch;
+    }
+    double v[NA];
+#pragma unroll
+    for (int s = 0; s < NA; ++s) v[s] = 0.0;
+    uint32_t within[3] = {0, 0, 0};
+    for (int64_t i = lo + threadIdx.x; i < hi; i += TPB) {
+      Unit<1> u;
+      load_unit<1, VEC>(pred, target, mask, b, 4 * i, HW, u);
+      float al[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        al[k] = 0.0f;
+        if (!u.in[k]) continue;
+        al[k] = align_value<MEDIAN>(u.p[k][0], c, clamp != 0);
+        const double a = (double)al[k], t = (double)u.t[k][0];
+        depth_terms(a, t, u.m[k] ? 1.0 : 0.0, v);
+        if (u.m[k]) {
+          const double ae = a < min_depth ? min_depth : a, te = t < min_depth ? min_depth : t;  // NaN stays NaN
+          const double d = ae - te, dd = d * d;
+          v[8] += fabs(d) / te;
+          v[9] += dd / te;
+          v[10] += dd;
+          const double lg = log(ae) - log(te);
+          v[11] += lg * lg;
+          const double r1 = ae / te, r2 = te / ae;
+          const double r = r1 > r2 ? r1 : r2;  // a_e, t_e > 0: one ratio is NaN only where the other is too
+          within[0] += r < 1.25 ? 1u : 0u;
+          within[1] += r < 1.5625 ? 1u : 0u;
+          within[2] += r < 1.953125 ? 1u : 0u;
+        }
+      }
+      if (aligned_out) {
+        float* ap = aligned_out + b * HW + 4 * i;
+        if constexpr (VEC) {
+          *(float4*)ap = make_float4(al[0], al[1], al[2], al[3]);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (u.in[k]) ap[k] = al[k];
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) v[12 + s] = (double)within[s];
+    block_sum<NA>(v, red, part + (b * gridDim.x + blockIdx.x) * NA);
   }
 }
 
@@ -341,16 +463,17 @@ __global__ __launch_bounds__(TPB) void ev_select_kernel(const uint64_t* __restri
 }
 
 // ---------------------------------------------------------------- c. finalize
-// the partials [first, first + count) in index order -> sums[NS], valid in every thread with t < NS
+// the partials [first, first + count) of N sums each in index order -> sums[N], valid in every thread with t < N
+template <int N = NS>
 __device__ __forceinline__ void sum_partials(const double* __restrict__ part, int64_t first, int64_t count, double* red,
-                                             double* sums /*LDS [NS]*/) {
-  double s[NS];
+                                             double* sums /*LDS [N]*/) {
+  double s[N];
 #pragma unroll
-  for (int k = 0; k < NS; ++k) s[k] = 0.0;
+  for (int k = 0; k < N; ++k) s[k] = 0.0;
   for (int64_t j = threadIdx.x; j < count; j += TPB)
 #pragma unroll
-    for (int k = 0; k < NS; ++k) s[k] += part[(first + j) * NS + k];
-  block_sum<NS>(s, red, sums);
+    for (int k = 0; k < N; ++k) s[k] += part[(first + j) * N + k];
+  block_sum<N>(s, red, sums);
 }
 
 __global__ __launch_bounds__(TPB) void ev_normal_finalize_kernel(const double* __restrict__ part, int64_t nblk, int B, int64_t HW,
@@ -385,29 +508,75 @@ __global__ __launch_bounds__(TPB) void ev_normal_finalize_kernel(const double* _
   }
 }
 
+// the eight fields of the depth form from a row's sums
+__device__ __forceinline__ void depth_fields(const double* sums, double numel, double* o) {
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const double N = sums[0], inv_valid = numel / N;
+  o[0] = N;
+  const bool some = N > 0.0;
+  o[1] = some ? sums[1] / numel * inv_valid * 100.0 : nan;          // :77, :85
+  o[2] = some ? sums[2] / numel * inv_valid * 100.0 : nan;          // :78-79, :84
+  o[3] = some ? sums[3] / numel * inv_valid : nan;                  // :66
+  o[4] = some ? sums[4] / numel * inv_valid : nan;                  // :68
+  o[5] = some ? sums[5] / N - (sums[4] * sums[4]) / (N * N) : nan;  // :71
+  o[6] = some ? sums[6] / numel * inv_valid : nan;                  // :72
+  o[7] = some ? sums[7] / numel * inv_valid : nan;                  // :74
+}
+
 __global__ __launch_bounds__(TPB) void ev_depth_finalize_kernel(const double* __restrict__ part, int64_t nblk, int B, int64_t HW,
                                                                 int per_image, int64_t rows, double* __restrict__ out) {
   __shared__ double red[4 * NS];
   __shared__ double sums[NS];
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const double numel = (double)(per_image ? HW : (int64_t)B * HW);
   for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
     sum_partials(part, per_image ? row * nblk : 0, per_image ? nblk : (int64_t)B * nblk, red, sums);
     if (threadIdx.x == 0) {
-      const double N = sums[0], inv_valid = numel / N;
-      double* o = out + row * DPTX_EVAL_DEPTH_FIELDS;
-      o[0] = N;
-      const bool some = N > 0.0;
-      o[1] = some ? sums[1] / numel * inv_valid * 100.0 : nan;          // :77, :85
-      o[2] = some ? sums[2] / numel * inv_valid * 100.0 : nan;          // :78-79, :84
-      o[3] = some ? sums[3] / numel * inv_valid : nan;                  // :66
-      o[4] = some ? sums[4] / numel * inv_valid : nan;                  // :68
-      o[5] = some ? sums[5] / N - (sums[4] * sums[4]) / (N * N) : nan;  // :71
-      o[6] = some ? sums[6] / numel * inv_valid : nan;                  // :72
-      o[7] = some ? sums[7] / numel * inv_valid : nan;                  // :74
+      depth_fields(sums, numel, out + row * DPTX_EVAL_DEPTH_FIELDS);
     }
     __syncthreads();
   }
+}
+
+// rows 0 .. B - 1: the images (the partials of image `row`); row B: the whole batch (all partials), as the depth form's
+// two kinds of call
+__global__ __launch_bounds__(TPB) void ev_aligned_finalize_kernel(const double* __restrict__ part, int64_t nblk, int B, int64_t HW,
+                                                                  double* __restrict__ out /*[B + 1][NA]*/) {
+  __shared__ double red[4 * NA];
+  __shared__ double sums[NA];
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  for (int64_t row = blockIdx.x; row <= B; row += gridDim.x) {
+    const bool image = row < B;
+    sum_partials<NA>(part, image ? row * nblk : 0, image ? nblk : (int64_t)B * nblk, red, sums);
+    if (threadIdx.x == 0) {
+      double* o = out + row * NA;
+      depth_fields(sums, (double)(image ? HW : (int64_t)B * HW), o);
+      const double N = sums[0];
+      const bool some = N > 0.0;
+      o[8] = some ? sums[8] / N : nan;
+      o[9] = some ? sums[9] / N : nan;
+      o[10] = some ? sqrt(sums[10] / N) : nan;
+      o[11] = some ? sqrt(sums[11] / N) : nan;
+      o[12] = some ? sums[12] / N : nan;
+      o[13] = some ? sums[13] / N : nan;
+      o[14] = some ? sums[14] / N : nan;
+    }
+    __syncthreads();
+  }
+}
+
+// include/dptx.h dptx_eval_aligned_workspace_bytes documents these sizes
+struct AlignedLayout {
+  Layout ev;  // the block partition of the depth form
+  int64_t off_stats, off_midas, bytes;
+};
+
+bool aligned_layout(int32_t B, int32_t H, int32_t W, AlignedLayout& al) {
+  int64_t midas = 0;
+  if (!layout(B, H, W, al.ev) || !midas_stats_workspace(B, H, W, &midas)) return false;
+  al.off_stats = align256((int64_t)B * al.ev.nblk * NA * 8);                   // partials fp64 [B][nblk][NA]
+  al.off_midas = al.off_stats + align256((int64_t)B * DPTX_MIDAS_STATS * 4);  // stats fp32 [B][DPTX_MIDAS_STATS]
+  al.bytes = al.off_midas + midas;                                            // the workspace of the stats stages
+  return true;
 }
 
 // ---------------------------------------------------------------- per-pixel angles
@@ -484,6 +653,45 @@ int dptx_eval_depth(const float* pred, const float* target, const uint8_t* mask,
   const int64_t rows = per_image ? B : 1;
   hipLaunchKernelGGL(ev_depth_finalize_kernel, dim3((unsigned)std::min<int64_t>(rows, MAX_GRID_Y)), dim3(TPB), 0, st, part, lo.nblk, (int)B, lo.HW,
                      per_image, rows, out);
+  return launch_ok() ? DPTX_OK : DPTX_E_HIP;
+}
+
+int dptx_eval_aligned_workspace_bytes(int32_t B, int32_t H, int32_t W, int64_t* bytes) {
+  AlignedLayout al;
+  if (!bytes || !aligned_layout(B, H, W, al)) return DPTX_E_INVALID;
+  *bytes = al.bytes;
+  return DPTX_OK;
+}
+
+int dptx_eval_depth_aligned(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W,
+                            int32_t align, int32_t flags, float min_depth, double* out, float* coeffs, float* aligned_out, void* ws,
+                            int64_t ws_bytes, void* stream) {
+  AlignedLayout al;
+  if (!pred || !target || !mask || !out || !coeffs || !ws || !aligned(ws, 8) || !aligned_layout(B, H, W, al) ||
+      ws_bytes < al.bytes || (align != DPTX_EVAL_ALIGN_LSTSQ && align != DPTX_EVAL_ALIGN_MEDIAN) ||
+      (flags & ~DPTX_EVAL_ALIGNED_CLAMP) || !(min_depth > 0.0f) || !std::isfinite(min_depth))
+    return DPTX_E_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  const Layout& lo = al.ev;
+  double* part = (double*)ws;
+  float* stats = (float*)((char*)ws + al.off_stats);
+  const bool median = align == DPTX_EVAL_ALIGN_MEDIAN;
+  // the solve kernel of the stats stages writes the coefficients; the metric pass below reads them in stream order
+  if (!midas_stats_launch(pred, target, mask, B, H, W, median ? DPTX_MIDAS_SSI : DPTX_MIDAS_ALIGN, stats, (char*)ws + al.off_midas, st))
+    return DPTX_E_HIP;
+  const dim3 grid((unsigned)lo.nblk, (unsigned)grid_y(B));
+  const int clamp = (flags & DPTX_EVAL_ALIGNED_CLAMP) ? 1 : 0;
+  const bool vec = vec_ok(lo, pred, target, mask, ws) && (!aligned_out || aligned(aligned_out, 16));
+#define DPTX_EV_ALIGNED(V, M)                                                                                                   \
+  hipLaunchKernelGGL((ev_aligned_kernel<V, M>), grid, dim3(TPB), 0, st, pred, target, mask, (int)B, lo.HW, lo.units, lo.per_block, \
+                     (const float*)stats, clamp, (double)min_depth, coeffs, aligned_out, part)
+  if (vec && median) DPTX_EV_ALIGNED(true, true);
+  else if (vec) DPTX_EV_ALIGNED(true, false);
+  else if (median) DPTX_EV_ALIGNED(false, true);
+  else DPTX_EV_ALIGNED(false, false);
+#undef DPTX_EV_ALIGNED
+  hipLaunchKernelGGL(ev_aligned_finalize_kernel, dim3((unsigned)std::min<int64_t>((int64_t)B + 1, MAX_GRID_Y)), dim3(TPB), 0, st,
+                     (const double*)part, lo.nblk, (int)B, lo.HW, out);
   return launch_ok() ? DPTX_OK : DPTX_E_HIP;
 }
 

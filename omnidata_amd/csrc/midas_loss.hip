@@ -26,6 +26,7 @@
 #include <cstdint>
 
 #include "../../include/dptx.h"
+#include "midas_stats.h"
 #include "select.h"
 
 #pragma clang fp contract(off)
@@ -603,6 +604,26 @@ bool run_stats(const float* pred, const float* targ, const uint8_t* mask, const 
 }
 
 }  // namespace
+
+// midas_stats.h: stages a..c for the other units, the call dptx_midas_stats makes
+namespace dptx {
+
+bool midas_stats_workspace(int32_t B, int32_t H, int32_t W, int64_t* bytes) {
+  Layout lo;
+  if (!layout(B, H, W, 1, lo)) return false;
+  *bytes = lo.total;
+  return true;
+}
+
+bool midas_stats_launch(const float* pred, const float* target, const uint8_t* mask, int32_t B, int32_t H, int32_t W, int32_t terms,
+                        float* stats, void* ws, hipStream_t stream) {
+  Layout lo;
+  Shape s;
+  if (!shape_of(B, H, W, terms, 1, lo, s)) return false;
+  return run_stats(pred, target, mask, s, lo, ws_view(ws, lo), 1, stats, stream);
+}
+
+}  // namespace dptx
 
 extern "C" {
 

@@ -136,6 +136,8 @@ ABI = [
     ("dptx_eval_normal", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
     ("dptx_eval_depth", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
     ("dptx_eval_normal_pixels", C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    ("dptx_eval_aligned_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i64p]),
+    ("dptx_eval_depth_aligned", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
     ("dptx_op_set_planes", C.c_int, [C.c_int64, C.c_int64]),
     ("dptx_op_gemm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_op_conv", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp] + [_i32] * 13 + [_vp]),

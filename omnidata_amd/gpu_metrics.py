@@ -11,6 +11,14 @@ the whole batch, or with per_image one row per image (what the reference's test 
     get_metrics(pred, target, task=None, masks=None)     ->  the reference's shape: dict of floats or None, one copy
     MetricsAccumulator(task)                             ->  mean and std over the images of a dataset
     normal_angles(pred, target)                          ->  [B,H,W] fp64: every pixel's angular error in degrees
+    aligned_depth_metrics(pred, target, mask, align=...) ->  depth metrics of the prediction fitted to the target per image
+    align_depth(pred, target, mask, align)               ->  the fitted prediction and its (scale, shift) per image
+
+The depth network's output is defined up to a scale and a shift per image, so a depth checkpoint is judged after a per-image
+fit to the ground truth: align='lstsq' (compute_scale_and_shift, losses/midas_loss.py:10-30) or align='median'
+(masked_shift_and_scale, :33-56).  dptx_eval_depth_aligned fits, aligns and evaluates in one call and adds the standard
+benchmark fields abs_rel, sq_rel, rmse, rmse_log and delta1..3; get_metrics and MetricsAccumulator take align= and go
+through it, and without it they are the unaligned code path.
 
 Key names are those of omnidata_amd.metrics plus num_valid.  pred / target: [B,3,H,W] (normal) or [B,1,H,W] (depth) in fp32,
 fp16 or bf16; mask: [B, 1 or C, H, W] bool, of which channel 0 is used, as in the reference.  CUDA tensors only: there is no
@@ -35,13 +43,18 @@ import torch
 from ._native import call, check_cuda, workspace
 from .engine import _stream, load_library
 
-__all__ = ["normal_metrics", "depth_metrics", "get_metrics", "normal_angles", "MetricsAccumulator", "NORMAL_FIELDS", "DEPTH_FIELDS"]
+__all__ = ["normal_metrics", "depth_metrics", "get_metrics", "normal_angles", "MetricsAccumulator", "NORMAL_FIELDS", "DEPTH_FIELDS",
+           "aligned_depth_metrics", "align_depth", "ALIGNED_DEPTH_FIELDS"]
 
 PER_IMAGE = 1                                   # include/dptx.h DPTX_EVAL_PER_IMAGE
 # the rows of dptx_eval_normal / dptx_eval_depth (DPTX_EVAL_NORMAL_FIELDS, DPTX_EVAL_DEPTH_FIELDS), in order
 NORMAL_FIELDS = ("num_valid", "ang_error_mean", "ang_error_median", "ang_error_without_masking", "percentage_within_11.25_degrees",
                  "percentage_within_22.5_degrees", "percentage_within_30_degrees", "eval_L1", "eval_mse")
 DEPTH_FIELDS = ("num_valid", "eval_L1", "eval_mse", "log10_diff", "log10", "si_log", "rel_error", "irmse")
+# the rows of dptx_eval_depth_aligned (DPTX_EVAL_ALIGNED_FIELDS)
+ALIGNED_DEPTH_FIELDS = DEPTH_FIELDS + ("abs_rel", "sq_rel", "rmse", "rmse_log", "delta1", "delta2", "delta3")
+_ALIGN = {"lstsq": 1, "median": 2}               # DPTX_EVAL_ALIGN_LSTSQ, DPTX_EVAL_ALIGN_MEDIAN
+ALIGNED_CLAMP = 1                                # DPTX_EVAL_ALIGNED_CLAMP
 _TASKS = {"normal": ("dptx_eval_normal", 3, NORMAL_FIELDS), "depth_zbuffer": ("dptx_eval_depth", 1, DEPTH_FIELDS)}
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 
@@ -125,10 +138,67 @@ def normal_angles(pred, target) -> torch.Tensor:
     return ang
 
 
-def get_metrics(pred, target, task=None, masks=None) -> Optional[Dict[str, float]]:
+def _check_align(task, align, min_depth=1e-3):
+    _task(task)
+    if align not in _ALIGN:
+        raise ValueError(f"align must be one of {sorted(_ALIGN)}, got {align!r}")
+    if task != "depth_zbuffer":
+        raise ValueError(f"align={align!r} needs task='depth_zbuffer': there is no aligned evaluation of task {task!r}")
+    try:   # the C ABI takes a float: judge the value it will see (1e-50 is 0.0f there, 1e39 is inf)
+        md = float(torch.tensor(float(min_depth), dtype=torch.float64).float())
+    except (TypeError, ValueError):
+        md = math.nan
+    if not (math.isfinite(md) and md > 0):
+        raise ValueError(f"min_depth must be positive and finite as an fp32 number, got {min_depth!r}")
+
+
+def _aligned_rows(pred, target, mask, align, clamp, min_depth, want_aligned=False):
+    """-> (rows fp64 [B + 1, 15], coeffs fp32 [B, 2], aligned fp32 [B,1,H,W] or None); stream-ordered, no synchronisation."""
+    _check_align("depth_zbuffer", align, min_depth)
+    p, t, m = _inputs(pred, target, mask, 1)
+    B, _, H, W = p.shape
+    ws = workspace("dptx_eval_aligned_workspace_bytes", p.device, (B, H, W), _unsupported(B, H, W))
+    out = torch.empty(B + 1, len(ALIGNED_DEPTH_FIELDS), dtype=torch.float64, device=p.device)
+    coeffs = torch.empty(B, 2, dtype=torch.float32, device=p.device)
+    al = torch.empty_like(p) if want_aligned else None
+    call("dptx_eval_depth_aligned", p.data_ptr(), t.data_ptr(), m.data_ptr(), B, H, W, _ALIGN[align], ALIGNED_CLAMP if clamp else 0,
+         float(min_depth), out.data_ptr(), coeffs.data_ptr(), al.data_ptr() if want_aligned else None, ws.data_ptr(), ws.numel(),
+         _stream(p.device))
+    return out, coeffs, al
+
+
+def aligned_depth_metrics(pred, target, mask, align: str = "lstsq", clamp: bool = True, min_depth: float = 1e-3,
+                          per_image: bool = False, return_coeffs: bool = False, return_aligned: bool = False):
+    """The depth metrics of the prediction fitted to the target per image (align 'lstsq' or 'median'; with clamp the fitted
+    value is clamped to [0, 1], paper_code/test_depth.py:207), keys ALIGNED_DEPTH_FIELDS, as fp64 CUDA tensors: 0-d for the
+    whole batch (the reference's get_metrics on the stacked fitted batch) or [B] with per_image.  abs_rel .. delta3 are
+    taken over the valid pixels with both depths floored at min_depth.  With return_coeffs / return_aligned the result is a
+    tuple (dict, coeffs [B,2] fp32 = scale, shift, aligned [B,1,H,W] fp32), the absent ones left out.  No synchronisation."""
+    rows, coeffs, al = _aligned_rows(pred, target, mask, align, clamp, min_depth, return_aligned)
+    B = coeffs.shape[0]
+    d = _as_dict(rows[:B] if per_image else rows[B:], ALIGNED_DEPTH_FIELDS, per_image)
+    if not (return_coeffs or return_aligned):
+        return d
+    return (d,) + ((coeffs,) if return_coeffs else ()) + ((al,) if return_aligned else ())
+
+
+def align_depth(pred, target, mask, align: str = "lstsq"):
+    """-> (aligned [B,1,H,W] fp32, coeffs [B,2] fp32 = scale, shift): the prediction fitted to the target per image, not
+    clamped, at every pixel (masked or not)."""
+    _, coeffs, al = _aligned_rows(pred, target, mask, align, False, 1e-3, True)
+    return al, coeffs
+
+
+def get_metrics(pred, target, task=None, masks=None, align=None, clamp: bool = True, min_depth: float = 1e-3) -> Optional[Dict[str, float]]:
     """Reference-shaped entry point (:13): task in {'normal', 'depth_zbuffer'} -> dict of Python floats with the reference's
     keys, or None for an empty mask; one device-to-host copy of the row.  Any other task (the reference's task-less L1 / MSE
-    included) raises ValueError."""
+    included) raises ValueError.  With align ('lstsq' / 'median', depth only) the row is that of aligned_depth_metrics for
+    the whole batch, with its seven further keys."""
+    if align is not None:
+        _check_align(task, align, min_depth)
+        rows, _, _ = _aligned_rows(pred, target, masks, align, clamp, min_depth)
+        row = rows[-1].cpu().tolist()
+        return None if row[0] < 1.0 else dict(zip(ALIGNED_DEPTH_FIELDS[1:], row[1:]))
     _, _, fields = _task(task)
     row = _rows(task, pred, target, masks, False)[0].cpu().tolist()
     if row[0] < 1.0:
@@ -144,15 +214,25 @@ class MetricsAccumulator:
     squares per field, images with an empty mask left out, as the reference skips a None); plain torch ops, no
     synchronisation.  compute() makes one copy and returns {name: (mean, std)}, with num_images the number of images that
     counted.  std is the SAMPLE standard deviation (divisor n - 1, what runstats' Statistics.variance() gives there), from
-    the sums: sqrt(max(sumsq - sum^2 / n, 0) / (n - 1)); NaN for n < 2, and mean NaN for n == 0."""
+    the sums: sqrt(max(sumsq - sum^2 / n, 0) / (n - 1)); NaN for n < 2, and mean NaN for n == 0.
 
-    def __init__(self, task: str):
+    With align ('lstsq' / 'median', task 'depth_zbuffer' only) the rows are the per-image rows of aligned_depth_metrics: every
+    image fitted to its own ground truth, the keys ALIGNED_DEPTH_FIELDS."""
+
+    def __init__(self, task: str, align=None, clamp: bool = True, min_depth: float = 1e-3):
         _, _, self.fields = _task(task)
         self.task = task
+        self.align, self.clamp, self.min_depth = align, clamp, min_depth
+        if align is not None:   # the per-image rows of aligned_depth_metrics
+            _check_align(task, align, min_depth)
+            self.fields = ALIGNED_DEPTH_FIELDS
         self._acc = None   # fp64 [3, fields]: count, sum, sum of squares
 
     def update(self, pred, target, mask) -> None:
-        rows = _rows(self.task, pred, target, mask, True)
+        if self.align is not None:
+            rows = _aligned_rows(pred, target, mask, self.align, self.clamp, self.min_depth)[0][:-1]
+        else:
+            rows = _rows(self.task, pred, target, mask, True)
         if self._acc is None:
             self._acc = torch.zeros(3, len(self.fields), dtype=torch.float64, device=rows.device)
         keep = rows[:, :1] > 0

@@ -2,7 +2,8 @@
 """Real-checkpoint harness: everything that can be said about a checkpoint in ONE run.
 
     python tools/eval_checkpoint.py --task normal --ckpt pretrained_models/omnidata_dpt_normal_v2.ckpt --images DIR [--gt DIR]
-                                    [--dtypes mixed,bf16x3] [--batch 8] [--device-metrics] [--out report.json]
+                                    [--dtypes mixed,bf16x3] [--batch 8] [--device-metrics] [--align lstsq|median]
+                                    [--out report.json]
 
 What the reference does with a checkpoint is `demo.py:62-72` (load, strip the Lightning prefix, strict load_state_dict) and
 `paper_code/evaluation_metrics.py:14-106` (the metrics of docs/pretrained.html:96-104).  This tool loads the same file through
@@ -20,6 +21,12 @@ every requested dtype reports
     for depth) against ground truth.  Ground-truth files: <gt>/<stem>.npy or <stem>.png for every image <stem>.*; normals as
     [H,W,3] in [0,1] (the reference's (n+1)/2 convention; an .npy in [-1,1] is mapped), depth as [H,W] in [0,1]; optional
     validity mask <stem>_mask.png (non-zero = valid).  They are resized / centre-cropped like the input.
+    A depth network's output is defined up to a scale and a shift per image, so raw depth metrics say little about a real
+    depth checkpoint: with --align lstsq (or median) every prediction is first fitted to its ground truth on the mask
+    (losses/midas_loss.py:10-30, :33-56) and the metrics are those of the fitted prediction, with abs_rel, sq_rel, rmse,
+    rmse_log and delta1..3 on top (omnidata_amd.gpu_metrics.aligned_depth_metrics, one HIP call; implies --device-metrics,
+    depth only).  The entry then carries "alignment": the mean and range of scale and shift over its images that have a
+    valid pixel (an image with an empty mask has no fit and is left out).
 
 There is no CPU fallback: the forward runs on an MI355X through libdptx.so.  No network is needed or used.
 """
@@ -78,9 +85,11 @@ def load_gt(gt_dir: str, stem: str, task: str):
 
 
 def evaluate(task: str, ckpt: str, images, gt_dir=None, dtypes=("mixed", "bf16x3"), batch: int = 8, backbone: str = "vitb_rn50_384",
-             device: str = "cuda:0", device_metrics: bool = False) -> dict:
+             device: str = "cuda:0", device_metrics: bool = False, align=None) -> dict:
     from omnidata_amd import preprocess as pp
-    if device_metrics:   # the same numbers from libdptx's eval kernels: one device-to-host copy instead of about ten reads
+    if align is not None and task != "depth":
+        raise ValueError(f"--align {align} needs --task depth: there is no aligned evaluation of task {task!r}")
+    if device_metrics or align is not None:   # the same numbers from libdptx's eval kernels: one device-to-host copy instead of about ten reads
         from omnidata_amd.gpu_metrics import get_metrics
     else:
         from omnidata_amd.metrics import get_metrics
@@ -135,7 +144,23 @@ def evaluate(task: str, ckpt: str, images, gt_dir=None, dtypes=("mixed", "bf16x3
                 tgt = torch.stack([g[0] for _, g in pairs]).to(dev)
                 msk = torch.stack([g[1] for _, g in pairs]).to(dev)
                 pred = y[idx].clamp(0, 1)   # demo.py:140
-                entry["metrics"] = get_metrics(pred, tgt, "normal" if task == "normal" else "depth_zbuffer", msk)
+                if align is not None:   # fit every image to its ground truth first; the fitted value is clamped again
+                    from omnidata_amd import gpu_metrics
+                    d, co = gpu_metrics.aligned_depth_metrics(pred, tgt, msk, align=align, return_coeffs=True)
+                    fields = gpu_metrics.ALIGNED_DEPTH_FIELDS
+                    n_img = len(idx)   # one copy: the batch row, the coefficients, which images have a valid pixel at all
+                    host = torch.cat([torch.stack([d[k] for k in fields]), co.double().flatten(),
+                                      msk.flatten(1).any(1).double()]).cpu()
+                    row = dict(zip(fields, host[:len(fields)].tolist()))
+                    entry["metrics"] = None if row.pop("num_valid") < 1 else row
+                    co = host[len(fields):len(fields) + 2 * n_img].view(n_img, 2)[host[len(fields) + 2 * n_img:] > 0]
+                    # images with an empty mask have no fit (their coefficients are (0, 0) or (1, 0)) and are left out
+                    entry["alignment"] = {"mode": align, "images": int(co.shape[0]),
+                                          **{name: ({"mean": float(co[:, k].mean()), "min": float(co[:, k].min()),
+                                                     "max": float(co[:, k].max())} if co.shape[0] else None)
+                                             for k, name in enumerate(("scale", "shift"))}}
+                else:
+                    entry["metrics"] = get_metrics(pred, tgt, "normal" if task == "normal" else "depth_zbuffer", msk)
                 entry["metrics_images"] = len(idx)
         report["dtypes"][dt] = entry
         del model
@@ -154,8 +179,13 @@ def main(argv=None):
     ap.add_argument("--backbone", default="vitb_rn50_384", choices=["vitb_rn50_384", "vitl16_384"])
     ap.add_argument("--device-metrics", action="store_true",
                     help="compute the --gt metrics with omnidata_amd.gpu_metrics (HIP kernels) instead of omnidata_amd.metrics (torch ops)")
+    ap.add_argument("--align", default="none", choices=["none", "lstsq", "median"],
+                    help="depth only: fit every prediction to its ground truth (scale and shift per image) before the --gt metrics; "
+                         "implies --device-metrics")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    if args.align != "none" and args.task != "depth":
+        ap.error(f"--align {args.align} needs --task depth")
     if os.path.isdir(args.images):
         images = sorted(p for p in glob.glob(os.path.join(args.images, "*")) if p.lower().endswith(IMG_EXT) and not p.endswith("_mask.png"))
     else:
@@ -164,7 +194,7 @@ def main(argv=None):
         print("invalid file path!")   # demo.py:161-163
         sys.exit(1)
     rep = evaluate(args.task, args.ckpt, images, args.gt, tuple(d for d in args.dtypes.split(",") if d), args.batch, args.backbone,
-                   device_metrics=args.device_metrics)
+                   device_metrics=args.device_metrics, align=None if args.align == "none" else args.align)
     txt = json.dumps(rep, indent=1)
     if args.out:
         with open(args.out, "w") as f:
