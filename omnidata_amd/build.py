@@ -11,8 +11,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdptx.so")
-SOURCES = ["gemm.hip", "gemm_fp16.hip", "gemm_fp16e.hip", "gemm_x3.hip", "gemm_x2.hip", "gemm_fp8.hip", "conv1x1.hip", "attention.hip", "norm.hip", "misc.hip", "stem.hip", "head.hip", "prepost.hip", "prepost_batch.hip", "fullframe.hip", "guided.hip", "tta.hip", "tta_depth.hip", "tiles.hip", "refocus.hip", "midas_loss.hip", "vnl_loss.hip", "normal_loss.hip", "eval_metrics.hip", "unet.hip", "unet_engine.hip", "engine.hip", "ops.hip"]
-HEADERS = ["common.h", "kernels.h", "gemm_impl.h", "select.h", "midas_stats.h", "unet.h", "resample_batch.h", "tta_common.h", "tta_depth_align.h", os.path.join("..", "..", "include", "dptx.h")]
+SOURCES = ["launch_forms.hip", "gemm.hip", "gemm_fp16.hip", "gemm_fp16e.hip", "gemm_x3.hip", "gemm_x2.hip", "gemm_fp8.hip", "conv1x1.hip", "attention.hip", "norm.hip", "misc.hip", "stem.hip", "head.hip", "prepost.hip", "prepost_batch.hip", "fullframe.hip", "guided.hip", "tta.hip", "tta_depth.hip", "tiles.hip", "refocus.hip", "midas_loss.hip", "vnl_loss.hip", "normal_loss.hip", "eval_metrics.hip", "unet.hip", "unet_engine.hip", "engine.hip", "ops.hip"]
+HEADERS = ["common.h", "kernels.h", "host_util.h", "gemm_impl.h", "select.h", "midas_stats.h", "unet.h", "resample_batch.h", "tta_common.h", "tta_depth_align.h", os.path.join("..", "..", "include", "dptx.h")]
 # Per-source compiler flags.  Every kernel source except attention / stem / head / prepost is built WITHOUT packed fp32 arithmetic
 # (refocus.hip, midas_loss.hip, vnl_loss.hip, normal_loss.hip, eval_metrics.hip, prepost_batch.hip, fullframe.hip, guided.hip, tta.hip, tta_depth.hip, tiles.hip: VALU code, built the same way from the start).
 # norm.hip / misc.hip (round 4): hipcc's SLP vectoriser emitted v_pk_add_f32 / v_pk_fma_f32 with op_sel swizzles there (low lane

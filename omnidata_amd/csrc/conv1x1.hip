@@ -369,4 +369,24 @@ hipError_t launch_conv1x1_stream(int mode, const GemmParams& p0, hipStream_t str
   return launch_c1_form<C1_GN>(mode, p, stream);
 }
 
+// one pass of conv1x1 + GroupNorm folded into three launches: how the statistics pass and the epilogue pass derive their
+// parameters from the plain convolution's, and what the finalize pass reads from them (images = M / a_rpi, rows per image =
+// a_rpi, one record per 32 rows)
+hipError_t launch_conv1x1_gn_pass(int mode, const GemmParams& conv, const ConvGnFold& f, int pass, hipStream_t stream) {
+  GemmParams q = conv;
+  if (pass == C1_PASS_STATS) {
+    q.gn_part = f.records;
+    return launch_conv1x1_stream(mode, q, stream, C1_STATS);
+  }
+  const bool r_gn = f.r_gamma != nullptr;
+  if (pass == C1_PASS_FINALIZE) {
+    if (conv.a_rpi <= 0) return hipErrorInvalidValue;
+    return launch_gn_finalize(f.records, f.gamma, f.beta, r_gn ? f.r_records : nullptr, f.r_gamma, r_gn ? f.r_beta : nullptr,
+                              f.tables, conv.M / conv.a_rpi, conv.a_rpi, conv.N, conv.a_rpi / 32, f.eps, stream);
+  }
+  if (pass != C1_PASS_EPILOGUE) return hipErrorInvalidValue;
+  q.R1 = f.R; q.act = f.relu ? 1 : 0; q.gn_tab = f.tables; q.gn_tab_rgn = r_gn;
+  return launch_conv1x1_stream(mode, q, stream, C1_GN);
+}
+
 }  // namespace dptx

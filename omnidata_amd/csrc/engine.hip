@@ -5,9 +5,9 @@
 // Reference being replaced (paths under omnidata_tools/torch/modules/midas/):
 //   dpt_depth.py:67-85  DPT.forward          -> Run::forward
 //   vit.py:119-155      forward_flex         -> stem / stages / tokens / 12 (24) blocks
-//   vit.py:61-99        forward_vit          -> the `readout` lambda: readout + reassemble (act_postprocess1..4)
-//   blocks.py:263-341   RCU / FeatureFusion  -> Run::rcu and the fusion loop of the `decode` lambda
-//   dpt_depth.py:91-99  head                 -> head convs + head tail / head_out (end of `decode`)
+//   vit.py:61-99        forward_vit          -> Run::readout: readout + reassemble (act_postprocess1..4)
+//   blocks.py:263-341   RCU / FeatureFusion  -> Run::rcu and the fusion loop of Run::decode
+//   dpt_depth.py:91-99  head                 -> head convs + head tail / head_out (end of Run::decode)
 // timm 0.4.12 vit_base_resnet50_384 (vit.py:483) is restated per SURVEY.md A.2.
 #include <hip/hip_runtime.h>
 
@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/dptx.h"
+#include "host_util.h"
 #include "kernels.h"
 
 using namespace dptx;
@@ -36,42 +37,7 @@ const int STAGE_DEPTH[3] = {3, 4, 9};
 const int STAGE_OUT[3] = {256, 512, 1024};
 const int STAGE_STRIDE[3] = {1, 2, 2};
 
-// ---------------------------------------------------------------- host 16-bit conversions
-inline uint16_t f32_to_bf16(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // quiet NaN
-  u += 0x7fffu + ((u >> 16) & 1u);                                            // RNE
-  return (uint16_t)(u >> 16);
-}
-inline uint16_t f32_to_fp16(float f) {
-  uint32_t x;
-  memcpy(&x, &f, 4);
-  const uint32_t sign = (x >> 16) & 0x8000u;
-  x &= 0x7fffffffu;
-  if (x >= 0x7f800000u) return (uint16_t)(sign | (x > 0x7f800000u ? 0x7e00u : 0x7c00u));
-  if (x >= 0x477ff000u) {  // >= 65520 rounds to inf
-    return (uint16_t)(sign | 0x7c00u);
-  }
-  if (x < 0x38800000u) {  // subnormal half (|f| < 2^-14)
-    if (x < 0x33000000u) return (uint16_t)sign;  // < 2^-25 -> 0
-    const int e = (int)(x >> 23);                // biased exponent
-    uint32_t m = (x & 0x7fffffu) | 0x800000u;    // 24-bit significand
-    const int shift = 126 - e;                   // 14..24: result = m >> shift with RNE (units of 2^-24)
-    const uint32_t q = m >> shift;
-    const uint32_t rem = m & ((1u << shift) - 1u);
-    const uint32_t half = 1u << (shift - 1);
-    uint32_t r = q;
-    if (rem > half || (rem == half && (q & 1u))) r++;
-    return (uint16_t)(sign | r);
-  }
-  uint32_t r = x - 0x38000000u;  // rebias exponent (127-15)<<23
-  const uint32_t rem = r & 0x1fffu;
-  r >>= 13;
-  if (rem > 0x1000u || (rem == 0x1000u && (r & 1u))) r++;
-  return (uint16_t)(sign | r);
-}
-
+// ---------------------------------------------------------------- host 16-bit conversions (f32 -> 16-bit: host_util.h)
 inline float fp16_to_f32(uint16_t h) {
   const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
   uint32_t e = (h >> 10) & 0x1fu, m = h & 0x3ffu, u;
@@ -270,7 +236,6 @@ inline size_t numel(const std::vector<int64_t>& s) {
   for (auto d : s) n *= (size_t)d;
   return n;
 }
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 constexpr int STEM_K = 176;  // stem K axis ordered (c, ky, kx) with kx padded 7 -> 8 (168) and rounded up to 11 MFMA k-steps
 
@@ -488,21 +453,6 @@ struct dptx_engine {
 };
 
 namespace {
-
-// Makes cfg.device_id current for the duration of a C entry point and restores the caller's device afterwards (a process
-// that drives several GPUs keeps its own current device; torch.cuda.current_device() is not switched behind its back).
-struct DeviceGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) err = hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
 
 #define HIPCHK(e, call)                                                                   \
   do {                                                                                    \
@@ -753,7 +703,7 @@ int pack_host(dptx_engine* e) {
 }
 
 // ------------------------------------------------------------------------------ schedule
-// What one GEMM of the schedule does besides the plain product (Run::conv, Run::rcu and the `dense` lambda of Run::forward).
+// What one GEMM of the schedule does besides the plain product (Run::conv, Run::rcu and Run::dense).
 // Every call names what it sets: GemmOpt().bias(b).act(1)
 enum { LN_NONE = 0, LN_CONSUMER = 1, LN_PRODUCER = 2 };
 struct GemmOpt {
@@ -819,6 +769,16 @@ struct Run {
   void q8_measure(const void* out, size_t n, int relu, int slot) {
     if (e->calibrating && e->d_amax) chk(launch_amax(MODE_BF16, out, n, relu, e->d_amax + slot, st), "fp8.amax");
   }
+  // the epilogue of p also writes the e4m3 copy of its output `out`, which takes the next slot (returned)
+  int fp8_copy(GemmParams& p, const void* out, int relu) {
+    const int slot = q8_produce(out);
+    gemm_add_fp8_copy(p, e->q8(out), relu, e->act_scale[slot]);
+    return slot;
+  }
+  // p multiplies the e4m3 copies of `in` and of the weight; the accumulators are rescaled by the inverses of their scales
+  void fp8_operands(GemmParams& p, const void* in, const std::string& wkey) {
+    gemm_use_fp8_operands(p, e->q8(in), e->w8(wkey), 1.0f / q8_scale_of(in), e->wscale(wkey));
+  }
 
   char* A(const Buf& b) const { return e->d_arena + abase + (half ? b.off2 : b.off); }
 
@@ -869,29 +829,19 @@ struct Run {
     GemmParams p;
     gemm_params_conv(p, B, Hin, Win, Cin, Cout, ksz, stride, pad_t, pad_l, Hout, Wout, f8 ? 1 : 2);
     p.A = in; p.W = e->w(wkey); p.C = out; p.bias = o.bias_; p.R1 = o.R1_; p.R2 = o.R2_;
-    int slot = -1;
-    if (e->fp8() && o.q_) {
-      slot = q8_produce(out);
-      p.C8 = e->q8(out); p.q_relu = o.q_ == 2; p.q_scale = e->act_scale[slot];
-    }
+    const int slot = e->fp8() && o.q_ ? fp8_copy(p, out, o.q_ == 2) : -1;
     p.act = o.act_; p.a_relu = o.a_relu_; p.planes = e->pl;
-    if (o.gn_part_) { p.gn_part = o.gn_part_; p.gn_hw = Hout * Wout; p.gn_blocks = Hout * Wout / 32; p.gn_cpg = Cout / 32; }
-    if (f8) {
-      p.A = e->q8(in); p.W = e->w8(wkey); p.a_relu = 0;
-      p.out_scale = 1.0f / q8_scale_of(in); p.out_scale_v = e->wscale(wkey);
-    }
+    if (o.gn_part_) gemm_add_gn_records(p, o.gn_part_, Hout * Wout);
+    if (f8) fp8_operands(p, in, wkey);
     int mode = f8 ? MODE_FP8 : dt;
     if (o.out_lo_ >= 0 && e->mixed()) {  // per-layer policy
       const bool x3 = e->layer_x3(wkey, cur_group), a_lo = e->layer_reads_lo(wkey, cur_group);
-      p.a_hi_only = x3 && !a_lo;
       if (a_lo && !has_lo(in)) {  // cannot happen with the schedule below: every producer honours its consumers' needs
         if (err == hipSuccess) { err = hipErrorInvalidValue; where = "precision policy: a 3-MFMA layer reads a tensor without lo plane"; }
         return;
       }
       const bool r1lo = o.R1_ != nullptr && has_lo(o.R1_), r2lo = o.R2_ != nullptr && has_lo(o.R2_);
-      mode = x3 ? MODE_FP16X3 : MODE_FP16;
-      p.r1_hi_only = !r1lo; p.r2_hi_only = !r2lo; p.c_hi_only = !o.out_lo_;
-      p.epi2 = (!x3 && (o.out_lo_ || r1lo || r2lo)) ? 1 : 0;
+      mode = gemm_set_plane_policy(p, x3, a_lo, r1lo, r2lo, o.out_lo_ != 0);
       mark_lo(out, o.out_lo_ != 0);
     }
     gemm(mode, p, wkey.c_str());
@@ -904,12 +854,9 @@ struct Run {
   void gn_stats(const void* X, float* part, int HW, int C) { chk(launch_gn_stats(dt, X, part, B, HW, C, e->pl, st), "gn_stats", 2); }
   void gn_apply(void* X, const std::string& nkey, float* part, int HW, int C, int relu, const void* R = nullptr,
                 const std::string& rkey = "", const float* rpart = nullptr) {
-    GnParams g{};
-    g.nrec = gn_fusable(HW) ? HW / 32 : 0;
-    g.X = X; g.Y = X; g.gamma = e->f(nkey + ".weight"); g.beta = e->f(nkey + ".bias"); g.partial = part;
-    g.R = R;
-    if (!rkey.empty()) { g.r_gamma = e->f(rkey + ".weight"); g.r_beta = e->f(rkey + ".bias"); g.r_partial = rpart; }
-    g.B = B; g.HW = HW; g.C = C; g.relu = relu; g.eps = 1e-5f;
+    GnParams g = gn_params(X, X, e->f(nkey + ".weight"), e->f(nkey + ".bias"), part, B, HW, C, relu, 1e-5f, gn_fusable(HW));
+    if (rkey.empty()) gn_add_residual(g, R);
+    else gn_add_residual(g, R, e->f(rkey + ".weight"), e->f(rkey + ".bias"), rpart);
     chk(launch_gn_apply(dt, g, e->pl, st), nkey.c_str(), 2);
   }
 
@@ -926,21 +873,16 @@ struct Run {
     gemm_params_conv(p, B, H, W, Cin, Cout, 1, 1, 0, 0, H, W, 2);
     p.A = in; p.W = e->w(wkey); p.C = out; p.planes = e->pl;
     if (!conv1x1_gn_eligible(dt, p) || !((flags & 64) || conv1x1_gn_adopted(p))) return false;
-    float* tab = (float*)A(e->gntab);
-    const double macs = (double)p.M / B * p.N * p.K;
-    GemmParams q = p;
-    q.gn_part = part;
-    exec_macs += macs; cat_macs[0] += macs;
-    chk(launch_conv1x1_stream(dt, q, st, C1_STATS), (wkey + ".stats").c_str(), 0);
     const bool r_gn = !rkey.empty();
-    chk(launch_gn_finalize(part, e->f(nkey + ".weight"), e->f(nkey + ".bias"), r_gn ? rpart : nullptr,
-                           r_gn ? e->f(rkey + ".weight") : nullptr, r_gn ? e->f(rkey + ".bias") : nullptr, tab, B, H * W, Cout,
-                           H * W / 32, 1e-5f, st),
-        (nkey + ".finalize").c_str(), 2);
-    q = p;
-    q.R1 = R; q.act = relu; q.gn_tab = tab; q.gn_tab_rgn = r_gn;
+    const ConvGnFold f{part, e->f(nkey + ".weight"), e->f(nkey + ".bias"), R, r_gn ? rpart : nullptr,
+                       r_gn ? e->f(rkey + ".weight") : nullptr, r_gn ? e->f(rkey + ".bias") : nullptr, (float*)A(e->gntab), relu,
+                       1e-5f};
+    const double macs = (double)p.M / B * p.N * p.K;
     exec_macs += macs; cat_macs[0] += macs;
-    chk(launch_conv1x1_stream(dt, q, st, C1_GN), wkey.c_str(), 0);
+    chk(launch_conv1x1_gn_pass(dt, p, f, C1_PASS_STATS, st), (wkey + ".stats").c_str(), 0);
+    chk(launch_conv1x1_gn_pass(dt, p, f, C1_PASS_FINALIZE, st), (nkey + ".finalize").c_str(), 2);
+    exec_macs += macs; cat_macs[0] += macs;
+    chk(launch_conv1x1_gn_pass(dt, p, f, C1_PASS_EPILOGUE, st), wkey.c_str(), 0);
     return true;
   }
 
@@ -956,53 +898,131 @@ struct Run {
          GemmOpt().bias(e->f(p + "conv2.bias")).R1(x).R2(o.R2_).q(o.q_).out_lo(e->mixed() ? o.out_lo_ : -1));
   }
 
-  int forward(const void* x, void* y, void* y2);
+  // ---- one forward: the geometry and the pointers every stage uses (begin() fills them), then the stages in schedule order
+  const std::string vp = "pretrained.model.";
+  const void* x = nullptr;   // the caller's input
+  int D_VIT = 0, D_MLP = 0, N_HEADS = 0;
+  bool large = false;        // DPT-Large (vitl16_384): no ResNet, patchify + 24 blocks, four readouts
+  float *part0 = nullptr, *part1 = nullptr, *part2 = nullptr, *part3 = nullptr;  // GroupNorm records
+  int h2 = 0, w2 = 0, h4 = 0, w4 = 0, gh = 0, gw = 0, h32 = 0, w32 = 0;
+  int NP = 0;                // patch tokens per image (576 at 384x384)
+  int S = 0;                 // + cls
+  int M = 0;                 // token rows of the batch
+  size_t tok_elems = 0;
+  const float* pos = nullptr;  // position embedding of this input's patch grid
+  float* X = nullptr;          // fp32 token stream
+  // LayerNorm fold (kernels.h GemmParams::ln_stats): every launch that writes the fp32 token stream also writes its 16-bit
+  // copy into Hn and the per-row (sum, sum of squares) records into lnst; qkv / fc1 read Hn and normalise in the epilogue
+  float* lnst = nullptr;
+  int ln_nblk = 0;    // records per token row (6 or 8; the row stride is always 8)
+  bool s16 = false;   // Hn is the (16-bit) token stream; X is not written
+  int hn_slot = -1;   // fp8 ViT: calibration slot of the token stream's latest e4m3 copy
+  bool mx = false;    // MIXED dtype
+
+  void begin(const void* x_in);
+  void resnet();
+  void embed();
+  void tok_tap(int idx, const char* name);
+  void dense(const void* in, const std::string& wkey, int N, int K, void* C, const GemmOpt& o);
+  void vit_block(int l);
+  void readout(int n);
+  void mark_encoder_planes();
+  void decode(const std::string& pre, int ch, void* yout);
+  int finish();
+  int forward(const void* x_in, void* y, void* y2);
+
+  // MIXED dtype, decoder groups (false / -1 / dt elsewhere)
+  bool X3(const std::string& key, int grp) const { return mx && e->layer_x3(key, grp); }            // computes with lo planes
+  bool RLO(const std::string& key, int grp) const { return mx && e->layer_reads_lo(key, grp); }   // reads its input's lo plane
+  int lo_of(bool need) const { return mx ? (int)need : -1; }
+  int planes_mode(const void* t) const { return mx ? (has_lo(t) ? MODE_FP16X3 : MODE_FP16) : dt; }  // elementwise kernels
 };
 
-int Run::forward(const void* x, void* y, void* y2) {
-  dptx_engine* E = e;
-  E->taps.clear();
-  E->event_cat.clear();
-  E->event_name.clear();
-  if (E->profiling) {
-    if (E->events.empty()) {
-      hipEvent_t ev;
-      if (hipEventCreate(&ev) == hipSuccess) E->events.push_back(ev);
+// The schedule of one forward, stage by stage (DPT.forward, dpt_depth.py:67-85)
+int Run::forward(const void* x_in, void* y, void* y2) {
+  begin(x_in);
+  if (!large) resnet();
+  embed();
+  // ---- 12 (24) transformer blocks (timm Block; LN eps 1e-6) -------------------------------
+  for (int l = 0; l < e->depth; ++l) {
+    vit_block(l);
+    if (large) {
+      if (l % 6 == 5) readout(l / 6 + 1);  // dpt_depth.py:41-45 hooks [5, 11, 17, 23]
+    } else {
+      if (l == 8) readout(3);  // hooks [0, 1, 8, 11]: the first two are the ResNet stages
+      if (l == 11) readout(4);
     }
-    if (!E->events.empty()) (void)hipEventRecord(E->events[0], st);
   }
-  const std::string vp = "pretrained.model.";
-  const std::string bp = vp + "patch_embed.backbone.";
-  const int D_VIT = E->dv, D_MLP = E->dm, N_HEADS = E->nh;
-  const bool large = E->backbone == DPTX_BACKBONE_VITL16_384;
-  float* part0 = (float*)A(E->part[0]);
-  float* part1 = (float*)A(E->part[1]);
-  float* part2 = (float*)A(E->part[2]);
-  float* part3 = (float*)A(E->part[3]);
-  const int h2 = Hi / 2, w2 = Wi / 2, h4 = Hi / 4, w4 = Wi / 4, gh = Hi / 16, gw = Wi / 16, h32 = Hi / 32, w32 = Wi / 32;
-  const int NP = gh * gw;   // patch tokens per image (576 at 384x384)
-  const int S = NP + 1;     // + cls
-  const bool native = (gh == 24 && gw == 24);
-  const float* pos = E->f("pretrained.model.pos_embed");
-  if (!native) {  // vit.py:119-125: forward_flex resizes pos_embed to the input's patch grid on every call
-    chk(launch_pos_resize(pos, (float*)A(E->pos_alt), 24, gh, gw, D_VIT, st), "pos_resize");
-    pos = (const float*)A(E->pos_alt);
+  // timm's final model.norm is dead compute in the reference (vit.py:153, result discarded :64)
+  mark_encoder_planes();
+  decode("", e->cfg.num_channels, y);
+  if (e->cfg.dual_task) {
+    // the second decoder re-uses the first one's arena buffers: the first one's stage taps are gone (debug a decoder
+    // with a single-task handle -- its results are bit-identical)
+    for (const char* n : {"l1_rn", "l2_rn", "l3_rn", "l4_rn", "p1", "p2", "p3", "p4", "h0", "h1"}) e->taps.erase(n);
+    decode("depth.", 1, y2);
   }
+  return finish();
+}
 
-  if (!large) {
+void Run::begin(const void* x_in) {
+  x = x_in;
+  e->taps.clear();
+  e->event_cat.clear();
+  e->event_name.clear();
+  if (e->profiling) {
+    if (e->events.empty()) {
+      hipEvent_t ev;
+      if (hipEventCreate(&ev) == hipSuccess) e->events.push_back(ev);
+    }
+    if (!e->events.empty()) (void)hipEventRecord(e->events[0], st);
+  }
+  D_VIT = e->dv; D_MLP = e->dm; N_HEADS = e->nh;
+  large = e->backbone == DPTX_BACKBONE_VITL16_384;
+  part0 = (float*)A(e->part[0]);
+  part1 = (float*)A(e->part[1]);
+  part2 = (float*)A(e->part[2]);
+  part3 = (float*)A(e->part[3]);
+  h2 = Hi / 2; w2 = Wi / 2; h4 = Hi / 4; w4 = Wi / 4; gh = Hi / 16; gw = Wi / 16; h32 = Hi / 32; w32 = Wi / 32;
+  NP = gh * gw;
+  S = NP + 1;
+  M = B * S;
+  tok_elems = (size_t)M * D_VIT;
+  X = (float*)A(e->X);
+  lnst = (float*)A(e->lnst);
+  ln_nblk = D_VIT / 128;
+  s16 = e->stream16;
+  mx = e->mixed();
+  const bool native = (gh == 24 && gw == 24);
+  pos = e->f("pretrained.model.pos_embed");
+  if (!native) {  // vit.py:119-125: forward_flex resizes pos_embed to the input's patch grid on every call
+    chk(launch_pos_resize(pos, (float*)A(e->pos_alt), 24, gh, gw, D_VIT, st), "pos_resize");
+    pos = (const float*)A(e->pos_alt);
+  }
+}
+
+int Run::finish() {
+  e->n_q8 = q8_count < dptx_engine::MAX_Q8 ? q8_count : dptx_engine::MAX_Q8;
+  if (err != hipSuccess) return e->fail(DPTX_E_HIP, std::string("launch failed at ") + where + ": " + hipGetErrorString(err));
+  return DPTX_OK;
+}
+
+// ---- the ResNetV2 of the hybrid model: stem, then stages (3,4,9)
+void Run::resnet() {
+  const std::string bp = vp + "patch_embed.backbone.";
   // ---- stem: fused conv7x7 s2 SAME (stem.hip, no im2col) -> GN+ReLU -> MaxPool2dSame(3,2) ---------
   group(DPTX_GROUP_RESNET);
-  chk(launch_stem_conv(dt, x, io, E->w(bp + "stem.conv.weight"), A(E->sraw), B, Hi, Wi, E->pl, st), "stem.conv", 0);
+  chk(launch_stem_conv(dt, x, io, e->w(bp + "stem.conv.weight"), A(e->sraw), B, Hi, Wi, e->pl, st), "stem.conv", 0);
   exec_macs += (double)h2 * w2 * 64 * STEM_K;
   cat_macs[0] += (double)h2 * w2 * 64 * STEM_K;
-  gn_stats(A(E->sraw), part0, h2 * w2, 64);
-  chk(launch_gn_relu_maxpool(dt, A(E->sraw), A(E->stem), E->f(bp + "stem.norm.weight"), E->f(bp + "stem.norm.bias"),
-                             part0, B, h2, w2, 64, 1e-5f, E->pl, st),
+  gn_stats(A(e->sraw), part0, h2 * w2, 64);
+  chk(launch_gn_relu_maxpool(dt, A(e->sraw), A(e->stem), e->f(bp + "stem.norm.weight"), e->f(bp + "stem.norm.bias"),
+                             part0, B, h2, w2, 64, 1e-5f, e->pl, st),
       "stem.pool", 2);
-  tap("stem", A(E->stem), h4, w4, 64);
+  tap("stem", A(e->stem), h4, w4, 64);
 
   // ---- ResNetV2 stages (3,4,9) non-preact bottlenecks -----------------------------------
-  const void* cur = A(E->stem);
+  const void* cur = A(e->stem);
   int H = h4, Wd = w4, cin = 64;
   for (int s = 0; s < 3; ++s) {
     const int cout = STAGE_OUT[s], mid = cout / 4;
@@ -1010,29 +1030,29 @@ int Run::forward(const void* x, void* y, void* y2) {
       const std::string p = bp + "stages." + std::to_string(s) + ".blocks." + std::to_string(b) + ".";
       const int stride = (b == 0) ? STAGE_STRIDE[s] : 1;
       const int Ho = H / stride, Wo = Wd / stride;
-      void* out = (b == STAGE_DEPTH[s] - 1) ? (void*)A(E->S[s]) : (void*)((b & 1) ? A(E->PB) : A(E->PA));
+      void* out = (b == STAGE_DEPTH[s] - 1) ? (void*)A(e->S[s]) : (void*)((b & 1) ? A(e->PB) : A(e->PA));
       const bool f_in = gn_fusable(H * Wd), f_out = gn_fusable(Ho * Wo);  // statistics from the conv epilogues
       if (b == 0) {
-        conv(cur, H, Wd, cin, p + "downsample.conv.weight", 1, stride, 0, 0, Ho, Wo, cout, A(E->DS), GemmOpt().gn_part(f_out ? part3 : nullptr));
-        if (!f_out) gn_stats(A(E->DS), part3, Ho * Wo, cout);
+        conv(cur, H, Wd, cin, p + "downsample.conv.weight", 1, stride, 0, 0, Ho, Wo, cout, A(e->DS), GemmOpt().gn_part(f_out ? part3 : nullptr));
+        if (!f_out) gn_stats(A(e->DS), part3, Ho * Wo, cout);
       }
-      conv(cur, H, Wd, cin, p + "conv1.weight", 1, 1, 0, 0, H, Wd, mid, A(E->T1), GemmOpt().gn_part(f_in ? part0 : nullptr));
-      if (!f_in) gn_stats(A(E->T1), part0, H * Wd, mid);
-      gn_apply(A(E->T1), p + "norm1", part0, H * Wd, mid, 1);
+      conv(cur, H, Wd, cin, p + "conv1.weight", 1, 1, 0, 0, H, Wd, mid, A(e->T1), GemmOpt().gn_part(f_in ? part0 : nullptr));
+      if (!f_in) gn_stats(A(e->T1), part0, H * Wd, mid);
+      gn_apply(A(e->T1), p + "norm1", part0, H * Wd, mid, 1);
       // 3x3, stride on conv2 (V1.5); TF-SAME: s1 -> pad (1,1); s2 on even H -> pad (0,1)
       const int pad = (stride == 1) ? 1 : 0;
-      conv(A(E->T1), H, Wd, mid, p + "conv2.weight", 3, stride, pad, pad, Ho, Wo, mid, A(E->T2), GemmOpt().gn_part(f_out ? part1 : nullptr));
-      if (!f_out) gn_stats(A(E->T2), part1, Ho * Wo, mid);
-      gn_apply(A(E->T2), p + "norm2", part1, Ho * Wo, mid, 1);
+      conv(A(e->T1), H, Wd, mid, p + "conv2.weight", 3, stride, pad, pad, Ho, Wo, mid, A(e->T2), GemmOpt().gn_part(f_out ? part1 : nullptr));
+      if (!f_out) gn_stats(A(e->T2), part1, Ho * Wo, mid);
+      gn_apply(A(e->T2), p + "norm2", part1, Ho * Wo, mid, 1);
       // conv3 + norm3 (+ shortcut + ReLU): folded into two passes of the streaming kernel where that was adopted
-      const bool folded = b == 0 ? conv_gn_folded(A(E->T2), Ho, Wo, mid, p + "conv3.weight", cout, out, p + "norm3", part2, 1, A(E->DS),
+      const bool folded = b == 0 ? conv_gn_folded(A(e->T2), Ho, Wo, mid, p + "conv3.weight", cout, out, p + "norm3", part2, 1, A(e->DS),
                                                   p + "downsample.norm", part3)
-                                 : conv_gn_folded(A(E->T2), Ho, Wo, mid, p + "conv3.weight", cout, out, p + "norm3", part2, 1, cur);
+                                 : conv_gn_folded(A(e->T2), Ho, Wo, mid, p + "conv3.weight", cout, out, p + "norm3", part2, 1, cur);
       if (!folded) {
-        conv(A(E->T2), Ho, Wo, mid, p + "conv3.weight", 1, 1, 0, 0, Ho, Wo, cout, out, GemmOpt().gn_part(f_out ? part2 : nullptr));
+        conv(A(e->T2), Ho, Wo, mid, p + "conv3.weight", 1, 1, 0, 0, Ho, Wo, cout, out, GemmOpt().gn_part(f_out ? part2 : nullptr));
         if (!f_out) gn_stats(out, part2, Ho * Wo, cout);
         if (b == 0)
-          gn_apply(out, p + "norm3", part2, Ho * Wo, cout, 1, A(E->DS), p + "downsample.norm", part3);
+          gn_apply(out, p + "norm3", part2, Ho * Wo, cout, 1, A(e->DS), p + "downsample.norm", part3);
         else
           gn_apply(out, p + "norm3", part2, Ho * Wo, cout, 1, cur);
       }
@@ -1044,183 +1064,153 @@ int Run::forward(const void* x, void* y, void* y2) {
     const char* names[3] = {"s0", "s1", "s2"};
     tap(names[s], cur, H, Wd, cout);
   }
-  }  // !large
+}
 
-  // ---- tokens: 1x1 proj + bias + pos_embed -> fp32 stream X[b*S + 1 + p] (S = 577 at 384x384); cls rows ----
-  float* X = (float*)A(E->X);
-  // LayerNorm fold (kernels.h GemmParams::ln_stats): every launch that writes the fp32 token stream also writes its 16-bit
-  // copy into Hn and the per-row (sum, sum of squares) records into lnst; qkv / fc1 read Hn and normalise in the epilogue
-  float* lnst = (float*)A(E->lnst);
-  const int ln_nblk = D_VIT / 128;  // records per token row (6 or 8; the row stride is always 8)
-  const bool s16 = E->stream16;     // Hn is the (16-bit) token stream; X is not written
+// ---- tokens: 1x1 proj + bias + pos_embed -> fp32 stream X[b*S + 1 + p] (S = 577 at 384x384); cls rows ----
+void Run::embed() {
   group(DPTX_GROUP_EMBED);
-  int hn_slot = -1;   // fp8 ViT: calibration slot of the token stream's latest e4m3 copy
   {
     // hybrid: the 1x1 projection of the ResNet's 1/16-resolution map (K = 1024); DPT-Large: timm PatchEmbed, a 16x16
     // stride-16 convolution = a dense GEMM over the patch matrix (K = 3*16*16 = 768, misc.hip patchify16)
     const int Kp = large ? 768 : 1024;
     // (the patch matrix lives in F1, which is free here: Hn receives the 16-bit copy of the token stream below)
-    if (large) chk(launch_patchify16(dt, x, io, A(E->F1), B, Hi, Wi, E->pl, st), "patchify");
+    if (large) chk(launch_patchify16(dt, x, io, A(e->F1), B, Hi, Wi, e->pl, st), "patchify");
     GemmParams p;
-    gemm_params_dense(p, B * NP, D_VIT, Kp);
-    p.A = large ? A(E->F1) : A(E->S[2]); p.W = E->w(vp + "patch_embed.proj.weight"); p.C = X;
-    p.bias = E->f(vp + "patch_embed.proj.bias");
-    p.c_rpi = NP; p.c_img_rows = S; p.c_row_off = 1; p.ldc = D_VIT; p.c_fp32 = 1;
-    p.R2 = pos; p.r2_bcast = 1; p.r2_fp32 = 1; p.planes = E->pl;
-    if (E->ln_fold) { p.C16 = A(E->Hn); p.row_stats = lnst; p.stats_nblk = 8; }
-    if (s16) { p.C = A(E->Hn); p.c_fp32 = 0; p.C16 = nullptr; }  // the 16-bit tensor is the stream itself
+    gemm_params_patch_embed(p, B, NP, S, D_VIT, Kp);
+    p.A = large ? A(e->F1) : A(e->S[2]); p.W = e->w(vp + "patch_embed.proj.weight"); p.C = X;
+    p.bias = e->f(vp + "patch_embed.proj.bias");
+    p.R2 = pos; p.planes = e->pl;
+    if (s16) { p.C = A(e->Hn); p.c_fp32 = 0; }  // the 16-bit tensor is the stream itself
+    if (e->ln_fold) gemm_add_ln_producer(p, s16 ? nullptr : A(e->Hn), lnst);
     // fp8 ViT (DPTX_FLAG_FP8_VIT): block 0's qkv multiplies the e4m3 copy of the stream
-    hn_slot = E->fp8_use(vp + "blocks.0.attn.qkv.weight") ? q8_produce(A(E->Hn)) : -1;
-    if (hn_slot >= 0) { p.C8 = E->q8(A(E->Hn)); p.q_relu = 0; p.q_scale = E->act_scale[hn_slot]; }
+    hn_slot = e->fp8_use(vp + "blocks.0.attn.qkv.weight") ? fp8_copy(p, A(e->Hn), 0) : -1;
     gemm(dt, p, "patch_embed.proj");
   }
-  chk(launch_cls_rows(E->mode_of(DPTX_GROUP_VIT), E->f(vp + "cls_token"), pos, s16 ? nullptr : X, B, S, D_VIT,
-                      E->ln_fold ? A(E->Hn) : nullptr, E->ln_fold ? lnst : nullptr, st,
-                      hn_slot >= 0 ? E->q8(A(E->Hn)) : nullptr, hn_slot >= 0 ? E->act_scale[hn_slot] : 1.0f),
+  chk(launch_cls_rows(e->mode_of(DPTX_GROUP_VIT), e->f(vp + "cls_token"), pos, s16 ? nullptr : X, B, S, D_VIT,
+                      e->ln_fold ? A(e->Hn) : nullptr, e->ln_fold ? lnst : nullptr, st,
+                      hn_slot >= 0 ? e->q8(A(e->Hn)) : nullptr, hn_slot >= 0 ? e->act_scale[hn_slot] : 1.0f),
       "cls_rows");
-  if (hn_slot >= 0) q8_measure(A(E->Hn), (size_t)B * S * D_VIT, 0, hn_slot);
-  const int M = B * S;
-  const size_t tok_elems = (size_t)M * D_VIT;
-  auto tok_tap = [&](int idx, const char* name) {
-    if (!E->taps_on) return;
-    float* dst = E->d_tok_taps + (size_t)idx * E->tok_tap_stride;
-    if (s16) {  // debug copy: not a launch of the schedule (not counted, not timed)
-      const hipError_t r = launch_to_f32(E->mode_of(DPTX_GROUP_VIT), A(E->Hn), dst, tok_elems, E->pl, st);
-      if (err == hipSuccess && r != hipSuccess) { err = r; where = "tok_tap"; }
-    } else if (err == hipSuccess) {
-      err = hipMemcpyAsync(dst, X, tok_elems * 4, hipMemcpyDeviceToDevice, st);
-    }
-    E->taps[name] = TapInfo{dst, {B, S, D_VIT, 1}, true, dt};
-  };
+  if (hn_slot >= 0) q8_measure(A(e->Hn), (size_t)B * S * D_VIT, 0, hn_slot);
   tok_tap(0, "tok0");
+}
 
-  // One linear layer of a transformer block over the M token rows
-  auto dense = [&](const void* A, const std::string& wkey, int N, int K, void* C, const GemmOpt& o) {
-    GemmParams p;
-    gemm_params_dense(p, M, N, K);
-    p.A = A; p.W = E->w(wkey); p.C = C; p.c_fp32 = o.c_fp32_; p.bias = o.bias_; p.act = o.act_;
-    p.R1 = o.R1_; p.r1_fp32 = o.r1_fp32_; p.planes = E->pl;
-    if (o.ln_ == LN_CONSUMER) { p.ln_stats = lnst; p.ln_colsum = o.colsum_; p.ln_nblk = ln_nblk; p.ln_eps = 1e-6f; p.ln_inv_dim = 1.0f / (float)K; }
-    if (o.ln_ == LN_PRODUCER) { p.C16 = this->A(E->Hn); p.row_stats = lnst; p.stats_nblk = 8; }
-    if (o.ln_ == LN_PRODUCER && s16) {  // in place on the 16-bit stream: every thread reads exactly the elements it then writes
-      p.C = this->A(E->Hn); p.c_fp32 = 0; p.R1 = this->A(E->Hn); p.r1_fp32 = 0; p.C16 = nullptr;
-    }
-    int mode = dt;
-    if (E->fp8_use(wkey) && !E->calibrating) {  // e4m3 operands: the e4m3 copies of A and of the (folded) weight
-      p.A = E->q8(A); p.W = E->w8(wkey); p.a_bytes /= 2;
-      p.out_scale = 1.0f / q8_scale_of(A); p.out_scale_v = E->wscale(wkey);
-      if (o.ln_ == LN_CONSUMER) p.ln_colsum = E->f(wkey.substr(0, wkey.size() - 6) + "lnsum8");
-      mode = MODE_FP8;
-    }
-    int slot = -1;
-    if (o.q_) {
-      slot = q8_produce(p.C);
-      p.C8 = E->q8(p.C); p.q_relu = 0; p.q_scale = E->act_scale[slot];
-    }
-    gemm(mode, p, wkey.c_str());
-    if (slot >= 0) q8_measure(p.C, (size_t)M * N, 0, slot);
-  };
-
-  // ProjectReadout + reassemble for hook n (hybrid: 3 -> block 8, 4 -> block 11; DPT-Large: 1..4 -> blocks 5, 11, 17, 23,
-  // n = 1, 2 followed by a ConvTranspose2d with kernel == stride: a GEMM whose N enumerates (dy, dx, co) + a re-layout)
-  auto readout = [&](int n) {
-    group(DPTX_GROUP_REASSEMBLE);
-    const std::string pp = "pretrained.act_postprocess" + std::to_string(n) + ".";
-    float* clsb = (float*)A(E->clsb);
-    chk(launch_readout_cls(dt, s16 ? (const float*)A(E->Hn) : X, (long long)S * D_VIT, E->w(pp + "0.project.0.weight"), 2 * D_VIT,
-                           D_VIT, E->f(pp + "0.project.0.bias"), clsb, B, D_VIT, D_VIT, E->pl, st, s16 ? 1 : 0),
-        "readout_cls");
-    // the token GEMM reads a 16-bit image of the fp32 stream: with the LayerNorm fold the last fc2 epilogue has already
-    // written it (single-plane: the fold implies single-pass ViT blocks; a 3-MFMA reassemble group then still needs the
-    // lo plane, so it casts); otherwise Hn is free between blocks
-    if (!(E->ln_fold && !mode_is_x3(dt))) chk(launch_cast_f32(dt, X, A(E->Hn), (size_t)B * S * D_VIT, E->pl, st), "readout_cast");
-    exec_macs += (double)D_VIT * D_VIT;  // per image
-    void* R = (n & 1) ? A(E->R3) : A(E->R4);
-    GemmParams p{};
-    p.A = A(E->Hn); p.a_bytes = (long long)B * S * D_VIT * 2; p.planes = E->pl;
-    p.W = E->w(pp + "0.project.0.weight"); p.ldw = 2 * D_VIT; p.C = R;
-    p.M = B * NP; p.N = D_VIT; p.K = D_VIT;
-    p.a_rpi = NP; p.Wout = NP; p.Hin = 1; p.Win = NP; p.Cin = D_VIT; p.a_pix_stride = D_VIT;
-    p.a_img_stride = (long long)S * D_VIT; p.a_off = D_VIT;  // skip the cls row
-    p.ksz = 1; p.stride = 1;
-    p.c_rpi = NP; p.c_img_rows = NP; p.c_row_off = 0; p.ldc = D_VIT;
-    p.bias = clsb; p.bias_per_img = 1; p.act = 2;
-    gemm(dt, p, "readout");
-    const int f = n == 1 ? 256 : (n == 2 ? 512 : D_VIT);  // n <= 2: DPT-Large only
-    conv(R, gh, gw, D_VIT, pp + "3.weight", 1, 1, 0, 0, gh, gw, f, n == 3 ? A(E->L3) : A(E->T4), GemmOpt().bias(E->f(pp + "3.bias")));
-    if (n <= 2) {
-      const int k = n == 1 ? 4 : 2;
-      GemmParams d;
-      gemm_params_dense(d, B * NP, k * k * f, f);
-      d.A = A(E->T4); d.W = E->w(pp + "4.weight"); d.C = A(E->F1); d.bias = E->f(pp + "4.bias"); d.planes = E->pl;
-      gemm(dt, d, "reassemble.deconv");
-      chk(launch_depth_to_space(dt, A(E->F1), A(E->S[n - 1]), B, gh, gw, k, f, E->pl, st), "reassemble.d2s");
-      tap(n == 1 ? "l1" : "l2", A(E->S[n - 1]), gh * k, gw * k, f);
-    } else if (n == 3) {
-      tap("l3", A(E->L3), gh, gw, D_VIT);
-    } else {
-      conv(A(E->T4), gh, gw, D_VIT, pp + "4.weight", 3, 2, 1, 1, h32, w32, D_VIT, A(E->L4), GemmOpt().bias(E->f(pp + "4.bias")));
-      tap("l4", A(E->L4), h32, w32, D_VIT);
-    }
-  };
-
-  // ---- 12 (24) transformer blocks (timm Block; LN eps 1e-6) -------------------------------
-  for (int l = 0; l < E->depth; ++l) {
-    group(DPTX_GROUP_VIT);
-    const std::string p = vp + "blocks." + std::to_string(l) + ".";
-    const bool lf = E->ln_fold;
-    const int ln_in = lf ? LN_CONSUMER : LN_NONE, ln_out = lf ? LN_PRODUCER : LN_NONE;  // qkv, fc1 / proj, fc2
-    if (!lf) chk(launch_layernorm(dt, X, E->f(p + "norm1.weight"), E->f(p + "norm1.bias"), A(E->Hn), M, D_VIT, 1e-6f, E->pl, st), "ln1", 2);
-    // fp8 ViT: the tensors that an e4m3 GEMM reads get their e4m3 copy from the epilogue that produces them -- the stream
-    // after proj (fc1's operand), the GELU output (fc2's), the stream after fc2 (the next block's qkv)
-    const std::string pn = vp + "blocks." + std::to_string(l + 1) + ".";
-    const bool q_fc1 = E->fp8_use(p + "mlp.fc1.weight"), q_fc2 = E->fp8_use(p + "mlp.fc2.weight");
-    const bool q_next = l + 1 < E->depth && E->fp8_use(pn + "attn.qkv.weight");
-    dense(A(E->Hn), p + "attn.qkv.weight", 3 * D_VIT, D_VIT, A(E->QKV),
-          GemmOpt().bias(E->f(p + "attn.qkv.bias")).ln(ln_in).colsum(E->f(p + "attn.qkv.lnsum")));
-    chk(launch_attention(dt, A(E->QKV), A(E->AO), B, S, N_HEADS, E->pl, st), "attention", 1);
-    exec_macs += 2.0 * N_HEADS * (double)S * S * 64;
-    cat_macs[1] += 2.0 * N_HEADS * (double)S * S * 64;
-    dense(A(E->AO), p + "attn.proj.weight", D_VIT, D_VIT, X,
-          GemmOpt().c_fp32(1).bias(E->f(p + "attn.proj.bias")).R1(X).r1_fp32(1).ln(ln_out).q(q_fc1));
-    if (!lf) chk(launch_layernorm(dt, X, E->f(p + "norm2.weight"), E->f(p + "norm2.bias"), A(E->Hn), M, D_VIT, 1e-6f, E->pl, st), "ln2", 2);
-    dense(A(E->Hn), p + "mlp.fc1.weight", D_MLP, D_VIT, A(E->F1),
-          GemmOpt().bias(E->f(p + "mlp.fc1.bias")).act(2).ln(ln_in).colsum(E->f(p + "mlp.fc1.lnsum")).q(q_fc2));
-    dense(A(E->F1), p + "mlp.fc2.weight", D_VIT, D_MLP, X,
-          GemmOpt().c_fp32(1).bias(E->f(p + "mlp.fc2.bias")).R1(X).r1_fp32(1).ln(ln_out).q(q_next));
-    {
-      char nm[16];
-      snprintf(nm, sizeof nm, "blk%d", l);
-      tok_tap(l + 1, nm);
-    }
-    if (large) {
-      if (l % 6 == 5) readout(l / 6 + 1);  // dpt_depth.py:41-45 hooks [5, 11, 17, 23]
-    } else {
-      if (l == 8) readout(3);  // hooks [0, 1, 8, 11]: the first two are the ResNet stages
-      if (l == 11) readout(4);
-    }
+void Run::tok_tap(int idx, const char* name) {
+  if (!e->taps_on) return;
+  float* dst = e->d_tok_taps + (size_t)idx * e->tok_tap_stride;
+  if (s16) {  // debug copy: not a launch of the schedule (not counted, not timed)
+    const hipError_t r = launch_to_f32(e->mode_of(DPTX_GROUP_VIT), A(e->Hn), dst, tok_elems, e->pl, st);
+    if (err == hipSuccess && r != hipSuccess) { err = r; where = "tok_tap"; }
+  } else if (err == hipSuccess) {
+    err = hipMemcpyAsync(dst, X, tok_elems * 4, hipMemcpyDeviceToDevice, st);
   }
-  // timm's final model.norm is dead compute in the reference (vit.py:153, result discarded :64)
+  e->taps[name] = TapInfo{dst, {B, S, D_VIT, 1}, true, dt};
+}
 
-  // one decoder = scratch.* of one task ("" -> scratch.*, "depth." -> depth.scratch.*); the dual-task engine runs two
-  // on the same encoder outputs (S[0], S[1], L3, L4 are not modified by a decoder)
-  // MIXED dtype: the decoder groups follow the per-LAYER precision table (dptx_engine::layer_prec); a producer writes the lo
-  // plane of its output exactly when a consumer multiplies it with 3 MFMAs (or, for the path tensors, when it was computed
-  // with 3 MFMAs itself), whatever its own arithmetic is.  The encoder's outputs carry lo planes when their groups are 3-MFMA.
-  const bool mx = E->mixed();
+// One linear layer of a transformer block over the M token rows
+void Run::dense(const void* in, const std::string& wkey, int N, int K, void* C, const GemmOpt& o) {
+  const bool f8 = e->fp8_use(wkey) && !e->calibrating;  // e4m3 operands: the e4m3 copies of A and of the (folded) weight
+  GemmParams p;
+  gemm_params_dense(p, M, N, K, f8 ? 1 : 2);
+  p.A = in; p.W = e->w(wkey); p.C = C; p.c_fp32 = o.c_fp32_; p.bias = o.bias_; p.act = o.act_;
+  p.R1 = o.R1_; p.r1_fp32 = o.r1_fp32_; p.planes = e->pl;
+  if (o.ln_ == LN_CONSUMER)
+    gemm_add_ln_consumer(p, lnst, f8 ? e->f(wkey.substr(0, wkey.size() - 6) + "lnsum8") : o.colsum_, ln_nblk, 1e-6f);
+  if (o.ln_ == LN_PRODUCER) {
+    if (s16) {  // in place on the 16-bit stream: every thread reads exactly the elements it then writes
+      p.C = A(e->Hn); p.c_fp32 = 0; p.R1 = A(e->Hn); p.r1_fp32 = 0;
+    }
+    gemm_add_ln_producer(p, s16 ? nullptr : A(e->Hn), lnst);
+  }
+  if (f8) fp8_operands(p, in, wkey);
+  const int slot = o.q_ ? fp8_copy(p, p.C, 0) : -1;
+  gemm(f8 ? MODE_FP8 : dt, p, wkey.c_str());
+  if (slot >= 0) q8_measure(p.C, (size_t)M * N, 0, slot);
+}
+
+// ProjectReadout + reassemble for hook n (hybrid: 3 -> block 8, 4 -> block 11; DPT-Large: 1..4 -> blocks 5, 11, 17, 23,
+// n = 1, 2 followed by a ConvTranspose2d with kernel == stride: a GEMM whose N enumerates (dy, dx, co) + a re-layout)
+void Run::readout(int n) {
+  group(DPTX_GROUP_REASSEMBLE);
+  const std::string pp = "pretrained.act_postprocess" + std::to_string(n) + ".";
+  float* clsb = (float*)A(e->clsb);
+  chk(launch_readout_cls(dt, s16 ? (const float*)A(e->Hn) : X, (long long)S * D_VIT, e->w(pp + "0.project.0.weight"), 2 * D_VIT,
+                         D_VIT, e->f(pp + "0.project.0.bias"), clsb, B, D_VIT, D_VIT, e->pl, st, s16 ? 1 : 0),
+      "readout_cls");
+  // the token GEMM reads a 16-bit image of the fp32 stream: with the LayerNorm fold the last fc2 epilogue has already
+  // written it (single-plane: the fold implies single-pass ViT blocks; a 3-MFMA reassemble group then still needs the
+  // lo plane, so it casts); otherwise Hn is free between blocks
+  if (!(e->ln_fold && !mode_is_x3(dt))) chk(launch_cast_f32(dt, X, A(e->Hn), (size_t)B * S * D_VIT, e->pl, st), "readout_cast");
+  exec_macs += (double)D_VIT * D_VIT;  // per image
+  void* R = (n & 1) ? A(e->R3) : A(e->R4);
+  GemmParams p;
+  gemm_params_readout(p, B, NP, S, D_VIT);
+  p.A = A(e->Hn); p.planes = e->pl;
+  p.W = e->w(pp + "0.project.0.weight"); p.C = R;
+  p.bias = clsb; p.act = 2;
+  gemm(dt, p, "readout");
+  const int f = n == 1 ? 256 : (n == 2 ? 512 : D_VIT);  // n <= 2: DPT-Large only
+  conv(R, gh, gw, D_VIT, pp + "3.weight", 1, 1, 0, 0, gh, gw, f, n == 3 ? A(e->L3) : A(e->T4), GemmOpt().bias(e->f(pp + "3.bias")));
+  if (n <= 2) {
+    const int k = n == 1 ? 4 : 2;
+    GemmParams d;
+    gemm_params_dense(d, B * NP, k * k * f, f);
+    d.A = A(e->T4); d.W = e->w(pp + "4.weight"); d.C = A(e->F1); d.bias = e->f(pp + "4.bias"); d.planes = e->pl;
+    gemm(dt, d, "reassemble.deconv");
+    chk(launch_depth_to_space(dt, A(e->F1), A(e->S[n - 1]), B, gh, gw, k, f, e->pl, st), "reassemble.d2s");
+    tap(n == 1 ? "l1" : "l2", A(e->S[n - 1]), gh * k, gw * k, f);
+  } else if (n == 3) {
+    tap("l3", A(e->L3), gh, gw, D_VIT);
+  } else {
+    conv(A(e->T4), gh, gw, D_VIT, pp + "4.weight", 3, 2, 1, 1, h32, w32, D_VIT, A(e->L4), GemmOpt().bias(e->f(pp + "4.bias")));
+    tap("l4", A(e->L4), h32, w32, D_VIT);
+  }
+}
+
+// one transformer block (timm Block; LN eps 1e-6)
+void Run::vit_block(int l) {
+  group(DPTX_GROUP_VIT);
+  const std::string p = vp + "blocks." + std::to_string(l) + ".";
+  const bool lf = e->ln_fold;
+  const int ln_in = lf ? LN_CONSUMER : LN_NONE, ln_out = lf ? LN_PRODUCER : LN_NONE;  // qkv, fc1 / proj, fc2
+  if (!lf) chk(launch_layernorm(dt, X, e->f(p + "norm1.weight"), e->f(p + "norm1.bias"), A(e->Hn), M, D_VIT, 1e-6f, e->pl, st), "ln1", 2);
+  // fp8 ViT: the tensors that an e4m3 GEMM reads get their e4m3 copy from the epilogue that produces them -- the stream
+  // after proj (fc1's operand), the GELU output (fc2's), the stream after fc2 (the next block's qkv)
+  const std::string pn = vp + "blocks." + std::to_string(l + 1) + ".";
+  const bool q_fc1 = e->fp8_use(p + "mlp.fc1.weight"), q_fc2 = e->fp8_use(p + "mlp.fc2.weight");
+  const bool q_next = l + 1 < e->depth && e->fp8_use(pn + "attn.qkv.weight");
+  dense(A(e->Hn), p + "attn.qkv.weight", 3 * D_VIT, D_VIT, A(e->QKV),
+        GemmOpt().bias(e->f(p + "attn.qkv.bias")).ln(ln_in).colsum(e->f(p + "attn.qkv.lnsum")));
+  chk(launch_attention(dt, A(e->QKV), A(e->AO), B, S, N_HEADS, e->pl, st), "attention", 1);
+  exec_macs += 2.0 * N_HEADS * (double)S * S * 64;
+  cat_macs[1] += 2.0 * N_HEADS * (double)S * S * 64;
+  dense(A(e->AO), p + "attn.proj.weight", D_VIT, D_VIT, X,
+        GemmOpt().c_fp32(1).bias(e->f(p + "attn.proj.bias")).R1(X).r1_fp32(1).ln(ln_out).q(q_fc1));
+  if (!lf) chk(launch_layernorm(dt, X, e->f(p + "norm2.weight"), e->f(p + "norm2.bias"), A(e->Hn), M, D_VIT, 1e-6f, e->pl, st), "ln2", 2);
+  dense(A(e->Hn), p + "mlp.fc1.weight", D_MLP, D_VIT, A(e->F1),
+        GemmOpt().bias(e->f(p + "mlp.fc1.bias")).act(2).ln(ln_in).colsum(e->f(p + "mlp.fc1.lnsum")).q(q_fc2));
+  dense(A(e->F1), p + "mlp.fc2.weight", D_VIT, D_MLP, X,
+        GemmOpt().c_fp32(1).bias(e->f(p + "mlp.fc2.bias")).R1(X).r1_fp32(1).ln(ln_out).q(q_next));
+  char nm[16];
+  snprintf(nm, sizeof nm, "blk%d", l);
+  tok_tap(l + 1, nm);
+}
+
+// MIXED dtype: the decoder groups follow the per-LAYER precision table (dptx_engine::layer_prec); a producer writes the lo
+// plane of its output exactly when a consumer multiplies it with 3 MFMAs (or, for the path tensors, when it was computed
+// with 3 MFMAs itself), whatever its own arithmetic is.  The encoder's outputs carry lo planes when their groups are 3-MFMA.
+void Run::mark_encoder_planes() {
   if (mx) {
-    const bool enc_lo = mode_is_x3(E->mode_of(large ? DPTX_GROUP_REASSEMBLE : DPTX_GROUP_RESNET));
-    const bool re_lo = mode_is_x3(E->mode_of(DPTX_GROUP_REASSEMBLE));
-    mark_lo(A(E->S[0]), enc_lo); mark_lo(A(E->S[1]), enc_lo); mark_lo(A(E->L3), re_lo); mark_lo(A(E->L4), re_lo);
+    const bool enc_lo = mode_is_x3(e->mode_of(large ? DPTX_GROUP_REASSEMBLE : DPTX_GROUP_RESNET));
+    const bool re_lo = mode_is_x3(e->mode_of(DPTX_GROUP_REASSEMBLE));
+    mark_lo(A(e->S[0]), enc_lo); mark_lo(A(e->S[1]), enc_lo); mark_lo(A(e->L3), re_lo); mark_lo(A(e->L4), re_lo);
   }
-  auto X3 = [&](const std::string& key, int grp) { return mx && E->layer_x3(key, grp); };            // computes with lo planes
-  auto RLO = [&](const std::string& key, int grp) { return mx && E->layer_reads_lo(key, grp); };   // reads its input's lo plane
-  auto lo_of = [&](bool need) { return mx ? (int)need : -1; };
-  auto planes_mode = [&](const void* t) { return mx ? (has_lo(t) ? MODE_FP16X3 : MODE_FP16) : dt; };  // elementwise kernels
+}
 
-  auto decode = [&](const std::string& pre, int ch, void* yout) {
+// one decoder = scratch.* of one task ("" -> scratch.*, "depth." -> depth.scratch.*); the dual-task engine runs two
+// on the same encoder outputs (S[0], S[1], L3, L4 are not modified by a decoder)
+void Run::decode(const std::string& pre, int ch, void* yout) {
   // ---- scratch.layerN_rn (3x3, no bias) ---------------------------------------------------
-  const void* rn_in[4] = {A(E->S[0]), A(E->S[1]), A(E->L3), A(E->L4)};
+  const void* rn_in[4] = {A(e->S[0]), A(e->S[1]), A(e->L3), A(e->L4)};
   const int rn_h[4] = {h4, Hi / 8, gh, h32};
   const int rn_w[4] = {w4, Wi / 8, gw, w32};
   const int rn_c[4] = {256, 512, D_VIT, D_VIT};
@@ -1230,9 +1220,9 @@ int Run::forward(const void* x, void* y, void* y2) {
     // consumer of lrn[i] as a GEMM operand: refinenet4.resConfUnit2.conv1 (i = 3), refinenet{i+1}.resConfUnit1.conv1 (else)
     const std::string cons = pre + "scratch.refinenet" + std::to_string(i + 1) + (i == 3 ? ".resConfUnit2.conv1.weight" : ".resConfUnit1.conv1.weight");
     conv(rn_in[i], rn_h[i], rn_w[i], rn_c[i], pre + "scratch.layer" + std::to_string(i + 1) + "_rn.weight", 3, 1, 1, 1, rn_h[i],
-         rn_w[i], FEAT, A(E->lrn[i]),
-         GemmOpt().q(/*every consumer pre-activates*/ E->fp8_use(cons) ? 2 : 0).out_lo(lo_of(RLO(cons, DPTX_GROUP_FUSION))));
-    tap((pre + rn_names[i]).c_str(), A(E->lrn[i]), rn_h[i], rn_w[i], FEAT);
+         rn_w[i], FEAT, A(e->lrn[i]),
+         GemmOpt().q(/*every consumer pre-activates*/ e->fp8_use(cons) ? 2 : 0).out_lo(lo_of(RLO(cons, DPTX_GROUP_FUSION))));
+    tap((pre + rn_names[i]).c_str(), A(e->lrn[i]), rn_h[i], rn_w[i], FEAT);
   }
 
   // ---- RefineNet fusion 4 -> 1 (blocks.py:320-341).  out_conv (1x1) is applied BEFORE the x2
@@ -1247,79 +1237,68 @@ int Run::forward(const void* x, void* y, void* y2) {
     const int h = rn_h[i - 1], w = rn_w[i - 1];
     const void* sum;
     if (i == 4) {
-      sum = A(E->lrn[3]);
+      sum = A(e->lrn[3]);
     } else {
-      rcu(p + "resConfUnit1.", A(E->lrn[i - 1]), h, w, A(E->tA), A(E->tB),  // tB = path + RCU1(lrn)
-          GemmOpt().R2(path).q(E->fp8_use(p + "resConfUnit2.conv1.weight") ? 2 : 0)
+      rcu(p + "resConfUnit1.", A(e->lrn[i - 1]), h, w, A(e->tA), A(e->tB),  // tB = path + RCU1(lrn)
+          GemmOpt().R2(path).q(e->fp8_use(p + "resConfUnit2.conv1.weight") ? 2 : 0)
               .out_lo(lo_of(RLO(p + "resConfUnit2.conv1.weight", DPTX_GROUP_FUSION))));
-      sum = A(E->tB);
+      sum = A(e->tB);
     }
-    rcu(p + "resConfUnit2.", sum, h, w, A(E->tA), A(E->tC),
-        GemmOpt().q(E->fp8_use(p + "out_conv.weight") ? 1 : 0).out_lo(lo_of(RLO(p + "out_conv.weight", DPTX_GROUP_FUSION))));
+    rcu(p + "resConfUnit2.", sum, h, w, A(e->tA), A(e->tC),
+        GemmOpt().q(e->fp8_use(p + "out_conv.weight") ? 1 : 0).out_lo(lo_of(RLO(p + "out_conv.weight", DPTX_GROUP_FUSION))));
     // the path tensor keeps a lo plane when out_conv computed one (it is added to the next stage's sum in fp32) and when
     // the first head conv multiplies it with 3 MFMAs.  A 2-MFMA head conv reads the hi plane only: path_1 is then interpolated
     // from both planes of the low-resolution tensor and rounded ONCE, into the hi plane
-    conv(A(E->tC), h, w, FEAT, p + "out_conv.weight", 1, 1, 0, 0, h, w, FEAT, A(E->tA),
-         GemmOpt().bias(E->f(p + "out_conv.bias"))
+    conv(A(e->tC), h, w, FEAT, p + "out_conv.weight", 1, 1, 0, 0, h, w, FEAT, A(e->tA),
+         GemmOpt().bias(e->f(p + "out_conv.bias"))
              .out_lo(lo_of(X3(p + "out_conv.weight", DPTX_GROUP_FUSION) || (i == 1 && X3(oc + "0.weight", DPTX_GROUP_HEAD)))));
     // path_1 feeds the first head conv: in the fp8 dtype the up-sampling also writes its e4m3 copy
     {
-      const bool up8 = i == 1 && E->fp8_use(oc + "0.weight");
-      const int slot = up8 ? q8_produce(A(E->P[0])) : -1;
-      const bool hi_only = mx && i == 1 && has_lo(A(E->tA)) && !RLO(oc + "0.weight", DPTX_GROUP_HEAD);
-      chk(launch_upsample2x(planes_mode(A(E->tA)), A(E->tA), A(E->P[i - 1]), B, h, w, FEAT, E->pl, st,
-                            up8 ? E->q8(A(E->P[0])) : nullptr, up8 ? E->act_scale[slot] : 1.0f, hi_only),
+      const bool up8 = i == 1 && e->fp8_use(oc + "0.weight");
+      const int slot = up8 ? q8_produce(A(e->P[0])) : -1;
+      const bool hi_only = mx && i == 1 && has_lo(A(e->tA)) && !RLO(oc + "0.weight", DPTX_GROUP_HEAD);
+      chk(launch_upsample2x(planes_mode(A(e->tA)), A(e->tA), A(e->P[i - 1]), B, h, w, FEAT, e->pl, st,
+                            up8 ? e->q8(A(e->P[0])) : nullptr, up8 ? e->act_scale[slot] : 1.0f, hi_only),
           "fusion.up");
-      if (up8) q8_measure(A(E->P[0]), (size_t)B * 4 * h * w * FEAT, 0, slot);
-      if (mx) mark_lo(A(E->P[i - 1]), has_lo(A(E->tA)) && !hi_only);
+      if (up8) q8_measure(A(e->P[0]), (size_t)B * 4 * h * w * FEAT, 0, slot);
+      if (mx) mark_lo(A(e->P[i - 1]), has_lo(A(e->tA)) && !hi_only);
     }
-    path = A(E->P[i - 1]);
+    path = A(e->P[i - 1]);
     tap((pre + p_names[i - 1]).c_str(), path, 2 * h, 2 * w, FEAT);
   }
 
   // ---- head (dpt_depth.py:91-99) ----------------------------------------------------------
   group(DPTX_GROUP_HEAD);
   const bool conv2_x3 = mx ? X3(oc + "2.weight", DPTX_GROUP_HEAD) : mode_is_x3(dt);
-  conv(path, h2, w2, FEAT, oc + "0.weight", 3, 1, 1, 1, h2, w2, 128, A(E->H0), GemmOpt().bias(E->f(oc + "0.bias")).out_lo(lo_of(conv2_x3)));
-  tap((pre + "h0").c_str(), A(E->H0), h2, w2, 128);
+  conv(path, h2, w2, FEAT, oc + "0.weight", 3, 1, 1, 1, h2, w2, 128, A(e->H0), GemmOpt().bias(e->f(oc + "0.bias")).out_lo(lo_of(conv2_x3)));
+  tap((pre + "h0").c_str(), A(e->H0), h2, w2, 128);
   // fp16-plane dtypes: did anything upstream leave the fp16 range?  (one pass over the hi plane of H0: every decoder path and,
   // through them, the ViT blocks reach it by residual adds; the ResNetV2 stages cannot overflow -- standardised weights and
   // a GroupNorm behind every convolution bound them whatever the checkpoint)
-  if (E->range_check() && E->d_range)
-    chk(launch_nonfinite_scan(mx ? MODE_FP16 : dt, A(E->H0), (size_t)B * h2 * w2 * 128, E->d_range, st), "range.scan");
+  if (e->range_check() && e->d_range)
+    chk(launch_nonfinite_scan(mx ? MODE_FP16 : dt, A(e->H0), (size_t)B * h2 * w2 * 128, e->d_range, st), "range.scan");
   // (a 2-MFMA second head conv -- dptx_set_layer_precision(..., 2) -- has no fused form: head_tail_x3_kernel always spends three
   //  MFMAs and reads H0's lo plane, so the fused and the tapped forward would differ; it takes the three-launch tail.  ADVICE r4)
-  const bool conv2_two = mx && E->layer_mfmas(oc + "2.weight", DPTX_GROUP_HEAD) == 2;
-  if (E->head_fused(conv2_x3) && !conv2_two) {
+  const bool conv2_two = mx && e->layer_mfmas(oc + "2.weight", DPTX_GROUP_HEAD) == 2;
+  if (e->head_fused(conv2_x3) && !conv2_two) {
     // x2 upsample + conv 128->32 + ReLU + conv 1x1 + ReLU in one launch (head.hip): the 37.7 MB/image up-sampled map
     // and the 32-channel map never reach memory.  Not with a 3-MFMA conv2, and not while stage taps are recorded ("h1").
-    chk(launch_head_tail(conv2_x3 ? MODE_FP16X3 : (mx ? MODE_FP16 : dt), A(E->H0), E->w(oc + "2.weight"), E->f(oc + "2.bias"),
-                         E->f(oc + "4.weight"), E->f(oc + "4.bias"), yout, io, B, h2, w2, ch, E->cfg.non_negative, st, E->pl),
+    chk(launch_head_tail(conv2_x3 ? MODE_FP16X3 : (mx ? MODE_FP16 : dt), A(e->H0), e->w(oc + "2.weight"), e->f(oc + "2.bias"),
+                         e->f(oc + "4.weight"), e->f(oc + "4.bias"), yout, io, B, h2, w2, ch, e->cfg.non_negative, st, e->pl),
         "head.tail", 0);
     exec_macs += (double)Hi * Wi * 32 * 1152;
     cat_macs[0] += (double)Hi * Wi * 32 * (1152 + ch);
   } else {
-    chk(launch_upsample2x(planes_mode(A(E->H0)), A(E->H0), A(E->H0U), B, h2, w2, 128, E->pl, st), "head.up");
-    if (mx) mark_lo(A(E->H0U), has_lo(A(E->H0)));
-    conv(A(E->H0U), Hi, Wi, 128, oc + "2.weight", 3, 1, 1, 1, Hi, Wi, 32, A(E->H1),
-         GemmOpt().bias(E->f(oc + "2.bias")).act(1).out_lo(lo_of(conv2_x3)));
-    tap((pre + "h1").c_str(), A(E->H1), Hi, Wi, 32);
-    chk(launch_head_out(planes_mode(A(E->H1)), A(E->H1), E->f(oc + "4.weight"), E->f(oc + "4.bias"), yout, io, B, Hi * Wi, ch,
-                        E->cfg.non_negative, E->pl, st),
+    chk(launch_upsample2x(planes_mode(A(e->H0)), A(e->H0), A(e->H0U), B, h2, w2, 128, e->pl, st), "head.up");
+    if (mx) mark_lo(A(e->H0U), has_lo(A(e->H0)));
+    conv(A(e->H0U), Hi, Wi, 128, oc + "2.weight", 3, 1, 1, 1, Hi, Wi, 32, A(e->H1),
+         GemmOpt().bias(e->f(oc + "2.bias")).act(1).out_lo(lo_of(conv2_x3)));
+    tap((pre + "h1").c_str(), A(e->H1), Hi, Wi, 32);
+    chk(launch_head_out(planes_mode(A(e->H1)), A(e->H1), e->f(oc + "4.weight"), e->f(oc + "4.bias"), yout, io, B, Hi * Wi, ch,
+                        e->cfg.non_negative, e->pl, st),
         "head.out");
   }
   exec_macs += (double)Hi * Wi * 32 * ch;
-  };
-  decode("", E->cfg.num_channels, y);
-  if (E->cfg.dual_task) {
-    // the second decoder re-uses the first one's arena buffers: the first one's stage taps are gone (debug a decoder
-    // with a single-task handle -- its results are bit-identical)
-    for (const char* n : {"l1_rn", "l2_rn", "l3_rn", "l4_rn", "p1", "p2", "p3", "p4", "h0", "h1"}) E->taps.erase(n);
-    decode("depth.", 1, y2);
-  }
-  E->n_q8 = q8_count < dptx_engine::MAX_Q8 ? q8_count : dptx_engine::MAX_Q8;
-  if (err != hipSuccess) return E->fail(DPTX_E_HIP, std::string("launch failed at ") + where + ": " + hipGetErrorString(err));
-  return DPTX_OK;
 }
 
 }  // namespace

@@ -7,26 +7,6 @@ hipError_t launch_gemm_16(int dt, const GemmParams& p, hipStream_t stream) {
   return dt == DT_BF16 ? launch_dt<DT_BF16, 1>(p, stream) : launch_gemm_fp16(p, stream);
 }
 
-void gemm_params_dense(GemmParams& p, int M, int N, int K) {
-  p = GemmParams{};
-  p.M = M; p.N = N; p.K = K; p.ldw = K;
-  p.a_rpi = M > 0 ? M : 1; p.Wout = p.a_rpi; p.Hin = 1; p.Win = p.a_rpi; p.Cin = K; p.a_pix_stride = K;
-  p.a_img_stride = 0; p.a_off = 0; p.ksz = 1; p.stride = 1; p.pad_t = 0; p.pad_l = 0;
-  p.c_rpi = 0x7fffffff; p.c_img_rows = 0; p.c_row_off = 0; p.ldc = N;
-  p.a_bytes = (long long)M * K * 2;
-}
-
-void gemm_params_conv(GemmParams& p, int B, int Hin, int Win, int Cin, int Cout, int ksz, int stride, int pad_t, int pad_l,
-                      int Hout, int Wout, int a_elem_bytes) {
-  p = GemmParams{};
-  p.M = B * Hout * Wout; p.N = Cout; p.K = ksz * ksz * Cin; p.ldw = p.K;
-  p.a_rpi = Hout * Wout; p.Wout = Wout; p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.a_pix_stride = Cin;
-  p.a_img_stride = (long long)Hin * Win * Cin; p.a_off = 0; p.ksz = ksz; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
-  p.c_rpi = 0x7fffffff; p.c_img_rows = 0; p.c_row_off = 0; p.ldc = Cout;
-  p.a_bytes = (long long)B * Hin * Win * Cin * a_elem_bytes;
-  p.k_tap_fast = (ksz == 3 && Cin >= 512) ? 1 : 0;  // measured per layer: profiles/r01_experiments.md
-}
-
 // debug state is per host thread, like the tile-share state below: a test thread that switches launch forms or records a
 // trace does not change what another thread's forwards launch
 static thread_local long long* g_trace = nullptr;

@@ -94,12 +94,39 @@ struct GemmParams {
   int gn_tab_rgn;
 };
 
-// Fills the "plain dense row-major" defaults for A [M,K] (lda = K) and C [M,N].
-void gemm_params_dense(GemmParams& p, int M, int N, int K);
+// ---- the launch forms of the schedule (launch_forms.hip): how each form is parameterised is written there and nowhere else.
+// The forward (engine.hip) and the op-level entry points (ops.hip) call these and assign only pointers and their own choices
+// (A, W, C, bias, R1, R2, act, a_relu, a_fp32, c_fp32, r*_fp32, planes) themselves.
+// The four gemm_params_* reset p and fill a geometry; the gemm_add_* / gemm_use_* / gemm_set_* add one form to it.
+// Fills the "plain dense row-major" defaults for A [M,K] (lda = K) and C [M,N].  a_elem_bytes: 2, or 1 for e4m3 operands.
+void gemm_params_dense(GemmParams& p, int M, int N, int K, int a_elem_bytes = 2);
 // Fills the geometry of an NHWC convolution [B,Hin,Win,Cin] -> [B,Hout,Wout,Cout] (weights [Cout][ksz][ksz][Cin], C dense
 // [M,N]): M, N, K, ldw, the a_* and c_* fields, ldc and the tap order k_tap_fast.  a_elem_bytes: 2, or 1 for e4m3 operands.
 void gemm_params_conv(GemmParams& p, int B, int Hin, int Win, int Cin, int Cout, int ksz, int stride, int pad_t, int pad_l,
                       int Hout, int Wout, int a_elem_bytes);
+// Patch embedding: dense A [B*NP, K] -> rows 1 .. NP of every image's S = NP + 1 token rows of the fp32 stream C [B*S, D] (row 0
+// is the cls row), plus R2 = the fp32 position embedding [S, D], broadcast over the images.  The caller assigns R2 (and C).
+void gemm_params_patch_embed(GemmParams& p, int B, int NP, int S, int D, int K);
+// ProjectReadout's token GEMM: A = the NP patch rows of every image of the 16-bit stream [B*S, D] (the cls row is skipped),
+// W = the token half of the [D][2D] projection, bias = one row per image (the cls half, launch_readout_cls); C [B*NP, D].
+void gemm_params_readout(GemmParams& p, int B, int NP, int S, int D);
+// GroupNorm(32) records of the output from the epilogue (GemmParams::gn_part); HW rows per image, HW % 32 == 0
+void gemm_add_gn_records(GemmParams& p, float* part, int HW);
+// LayerNorm fold, consumer side (qkv, fc1): (mu, rstd) of row m from the records stats[m][0 .. nblk), row stride 8
+void gemm_add_ln_consumer(GemmParams& p, const float* stats, const float* colsum, int nblk, float eps);
+// LayerNorm fold, producer side: row_stats[row][8] of the stream this launch writes -- p.C, assigned by the caller, who also
+// assigns R1 = C where the launch adds to the stream in place (proj, fc2).  C16 != null: C is the fp32 stream and C16 receives
+// its 16-bit copy; C16 == null: C is the 16-bit stream itself.
+void gemm_add_ln_producer(GemmParams& p, void* C16, float* row_stats);
+// e4m3 operands (MODE_FP8; the geometry was filled with a_elem_bytes = 1): the accumulators are multiplied by out_scale (the
+// inverse of the activation tensor's scale) and by out_scale_v[n] (the inverses of the weight's channel scales; may be null)
+void gemm_use_fp8_operands(GemmParams& p, const void* A8, const void* W8, float out_scale, const float* out_scale_v);
+// e4m3 copy of the output times scale, ReLU'd first when relu
+void gemm_add_fp8_copy(GemmParams& p, void* C8, int relu, float scale);
+// per-layer plane policy of the "mixed" dtype: x3 = the layer multiplies on hi/lo planes (2 or 3 MFMAs per product),
+// a_reads_lo = it reads the lo plane of A (3 MFMAs), r1_lo / r2_lo = the residuals have a lo plane, out_lo = a consumer needs
+// the lo plane of C.  Returns the kernel mode to launch with (MODE_FP16X3 / MODE_FP16).
+int gemm_set_plane_policy(GemmParams& p, bool x3, bool a_reads_lo, bool r1_lo, bool r2_lo, bool out_lo);
 // dtype 0 bf16 / 1 fp16.  Picks the tile configuration from (M, N).  Returns hipError_t.
 hipError_t launch_gemm(int dtype, const GemmParams& p, hipStream_t stream);
 // debug: every following GEMM launch stamps s_memtime per k-tile phase for the 8 waves of block 0 into dev_buf
@@ -131,6 +158,19 @@ enum { C1_PLAIN = 0, C1_STATS = 1, C1_GN = 2 };
 bool conv1x1_gn_eligible(int mode, const GemmParams& p);
 bool conv1x1_gn_adopted(const GemmParams& p);
 hipError_t launch_conv1x1_stream(int mode, const GemmParams& p, hipStream_t stream, int form = C1_PLAIN);
+// The folded schedule as one definition: its operands, and one pass of it launched from the parameters of the plain
+// convolution (A, W, C, planes assigned; conv1x1_gn_eligible).  Whether to take the folded schedule stays the caller's decision.
+struct ConvGnFold {
+  float* records;                          // (sum, sum of squares) records of the convolution output: a_rpi / 32 per image
+  const float *gamma, *beta;               // [N]
+  const void* R;                           // optional shortcut, addressed like C
+  const float *r_records, *r_gamma, *r_beta;  // optional GroupNorm of the shortcut (all three or none)
+  float* tables;                           // [imgs][4][N], written by the finalize pass, read by the epilogue pass
+  int relu;
+  float eps;
+};
+enum { C1_PASS_STATS = 1, C1_PASS_FINALIZE = 2, C1_PASS_EPILOGUE = 4 };
+hipError_t launch_conv1x1_gn_pass(int mode, const GemmParams& conv, const ConvGnFold& f, int pass, hipStream_t stream);
 // tile selection: the following launches share the chip with (1 / share - 1) concurrent streams of the same forward
 void gemm_set_cu_share(float share);
 
@@ -152,6 +192,13 @@ struct GnParams {
   int nrec;  // partial records per image in `partial` / `r_partial`: 0 = gn_chunks(HW, C) (written by launch_gn_stats),
              // HW / 32 when a GEMM epilogue wrote them (GemmParams::gn_part)
 };
+// launch_forms.hip: Y = act( gn(X) ) with the records in `partial`; from_gemm_records: a GEMM epilogue wrote them
+// (gemm_add_gn_records) and not launch_gn_stats.  gn_add_residual: + R, normalised with its own triple when r_gamma != null
+// (its records come from the same kind of producer as `partial`).
+GnParams gn_params(const void* X, void* Y, const float* gamma, const float* beta, float* partial, int B, int HW, int C, int relu,
+                   float eps, bool from_gemm_records);
+void gn_add_residual(GnParams& g, const void* R, const float* r_gamma = nullptr, const float* r_beta = nullptr,
+                     const float* r_partial = nullptr);
 // the affines launch_gn_apply computes in its prologue, as tables for the GroupNorm epilogue of the streaming 1x1 kernel
 // (GemmParams::gn_tab): tab[b][0..1][C] = (a, d) of (partial, gamma, beta), tab[b][2..3][C] those of the r_ triple (skipped
 // when r_partial is null); nrec records per image.  One launch, one block per (image, triple).

@@ -1,6 +1,6 @@
 // ops.hip -- the op-level entry points of include/dptx.h (dptx_op_*) and the process-wide debug switches of the GEMM
 // launcher: single launches on caller-owned device buffers, for the op-level tests.  None of them touches a handle; the
-// parameter fills are the ones the forward's schedule uses (kernels.h gemm_params_dense / gemm_params_conv).
+// launch forms are the ones the forward's schedule uses (kernels.h / launch_forms.hip: gemm_params_*, gemm_add_*, gn_params).
 #include <hip/hip_runtime.h>
 
 #include "../../include/dptx.h"
@@ -35,7 +35,7 @@ int dptx_op_gemm_ln(int32_t dtype, const void* A, const void* W, const float* bi
   GemmParams p;
   gemm_params_dense(p, M, N, K);
   p.A = A; p.W = W; p.C = C; p.bias = bias; p.act = act; p.planes = g_op_planes;
-  p.ln_stats = ln_stats; p.ln_colsum = ln_colsum; p.ln_nblk = ln_nblk; p.ln_eps = ln_eps; p.ln_inv_dim = 1.0f / (float)K;
+  gemm_add_ln_consumer(p, ln_stats, ln_colsum, ln_nblk, ln_eps);
   return rc(launch_gemm(dtype, p, (hipStream_t)stream));
 }
 
@@ -46,7 +46,7 @@ int dptx_op_gemm_stream(int32_t dtype, const void* A, const void* W, const float
   GemmParams p;
   gemm_params_dense(p, M, N, K);
   p.A = A; p.W = W; p.C = C; p.R1 = C; p.bias = bias; p.planes = g_op_planes;
-  p.row_stats = row_stats; p.stats_nblk = 8;
+  gemm_add_ln_producer(p, nullptr, row_stats);
   return rc(launch_gemm(dtype, p, (hipStream_t)stream));
 }
 
@@ -55,8 +55,8 @@ int dptx_op_gemm_stream32(int32_t dtype, const void* A, const void* W, const flo
                           int32_t M, int32_t N, int32_t K, void* stream) {
   GemmParams p;
   gemm_params_dense(p, M, N, K);
-  p.A = A; p.W = W; p.C = X; p.c_fp32 = 1; p.R1 = X; p.r1_fp32 = 1; p.C16 = C16; p.bias = bias; p.planes = g_op_planes;
-  p.row_stats = row_stats; p.stats_nblk = 8;
+  p.A = A; p.W = W; p.C = X; p.c_fp32 = 1; p.R1 = X; p.r1_fp32 = 1; p.bias = bias; p.planes = g_op_planes;
+  gemm_add_ln_producer(p, C16, row_stats);
   return rc(launch_gemm(dtype, p, (hipStream_t)stream));
 }
 
@@ -96,6 +96,9 @@ int dptx_op_conv_planes(int32_t dtype, const void* X, const void* Wt, const floa
   GemmParams p;
   gemm_params_conv(p, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, 2);
   p.A = X; p.W = Wt; p.C = Y; p.bias = bias; p.R1 = R; p.act = act; p.a_relu = a_relu; p.planes = g_op_planes;
+  // the raw bits, set directly and not through gemm_set_plane_policy: this entry point's arguments are the fields themselves
+  // and admit combinations that function never produces (epi2 with every lo plane switched off, r2_hi_only left 0), so
+  // mapping them through it would need a second code path
   p.epi2 = epi2 & 1; p.a_hi_only = (epi2 >> 1) & 1; p.c_hi_only = c_hi_only; p.r1_hi_only = r1_hi_only;
   return rc(launch_gemm(dtype, p, (hipStream_t)stream));
 }
@@ -123,9 +126,8 @@ int dptx_op_groupnorm(int32_t dtype, const void* X, const float* gamma, const fl
   if (scratch_f32 == nullptr) return DPTX_E_INVALID;
   hipError_t r = launch_gn_stats(dtype, X, (float*)scratch_f32, B, HW, C, g_op_planes, (hipStream_t)stream);
   if (r != hipSuccess) return DPTX_E_HIP;
-  GnParams g{};
-  g.X = X; g.Y = Y; g.gamma = gamma; g.beta = beta; g.partial = (float*)scratch_f32; g.R = R;
-  g.B = B; g.HW = HW; g.C = C; g.relu = relu; g.eps = eps;
+  GnParams g = gn_params(X, Y, gamma, beta, (float*)scratch_f32, B, HW, C, relu, eps, false);
+  gn_add_residual(g, R);
   return rc(launch_gn_apply(dtype, g, g_op_planes, (hipStream_t)stream));
 }
 
@@ -161,7 +163,9 @@ int dptx_op_conv_fp8(const void* X8, const void* Wt8, const float* bias, const v
                      int32_t Wo, int32_t act, int32_t q_relu, float out_scale, void* stream) {
   GemmParams p;
   gemm_params_conv(p, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, 1);
-  p.A = X8; p.W = Wt8; p.C = Y; p.bias = bias; p.R1 = R; p.C8 = Y8; p.q_relu = q_relu; p.out_scale = out_scale; p.act = act;
+  p.C = Y; p.bias = bias; p.R1 = R; p.act = act;
+  gemm_use_fp8_operands(p, X8, Wt8, out_scale, nullptr);
+  gemm_add_fp8_copy(p, Y8, q_relu, 0.f);
   return rc(launch_gemm(MODE_FP8, p, (hipStream_t)stream));
 }
 
@@ -173,11 +177,10 @@ int dptx_op_conv_groupnorm(int32_t dtype, const void* X, const void* Wt, void* Y
   GemmParams p;
   gemm_params_conv(p, B, H, W, Cin, Cout, ksize, stride, pad_t, pad_l, Ho, Wo, 2);
   p.A = X; p.W = Wt; p.C = Yraw; p.planes = g_op_planes;
-  p.gn_part = (float*)scratch_f32; p.gn_hw = Ho * Wo; p.gn_blocks = Ho * Wo / 32; p.gn_cpg = Cout / 32;
+  gemm_add_gn_records(p, (float*)scratch_f32, Ho * Wo);
   if (launch_gemm(dtype, p, (hipStream_t)stream) != hipSuccess) return DPTX_E_HIP;
-  GnParams g{};
-  g.X = Yraw; g.Y = Y; g.gamma = gamma; g.beta = beta; g.partial = (float*)scratch_f32; g.R = R;
-  g.B = B; g.HW = Ho * Wo; g.C = Cout; g.relu = relu; g.eps = eps; g.nrec = Ho * Wo / 32;
+  GnParams g = gn_params(Yraw, Y, gamma, beta, (float*)scratch_f32, B, Ho * Wo, Cout, relu, eps, true);
+  gn_add_residual(g, R);
   return rc(launch_gn_apply(dtype, g, g_op_planes, (hipStream_t)stream));
 }
 
@@ -195,22 +198,9 @@ int dptx_op_conv_groupnorm_fused(int32_t dtype, const void* X, const void* Wt, c
   gemm_params_conv(p, B, H, W, Cin, Cout, 1, 1, 0, 0, H, W, 2);
   p.A = X; p.W = Wt; p.C = Y; p.planes = g_op_planes;
   if (!conv1x1_gn_eligible(dtype, p)) return DPTX_E_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  if (passes & 1) {
-    GemmParams q = p;
-    q.gn_part = (float*)records_f32;
-    if (launch_conv1x1_stream(dtype, q, st, C1_STATS) != hipSuccess) return DPTX_E_HIP;
-  }
-  if (passes & 2) {
-    if (launch_gn_finalize((const float*)records_f32, gamma, beta, r_records, r_gamma, r_beta, (float*)tables_f32, B, H * W, Cout,
-                           H * W / 32, eps, st) != hipSuccess)
-      return DPTX_E_HIP;
-  }
-  if (passes & 4) {
-    GemmParams q = p;
-    q.R1 = R; q.act = relu ? 1 : 0; q.gn_tab = (const float*)tables_f32; q.gn_tab_rgn = r_gamma != nullptr;
-    if (launch_conv1x1_stream(dtype, q, st, C1_GN) != hipSuccess) return DPTX_E_HIP;
-  }
+  const ConvGnFold f{(float*)records_f32, gamma, beta, R, r_records, r_gamma, r_beta, (float*)tables_f32, relu, eps};
+  for (int pass : {C1_PASS_STATS, C1_PASS_FINALIZE, C1_PASS_EPILOGUE})
+    if ((passes & pass) && launch_conv1x1_gn_pass(dtype, p, f, pass, (hipStream_t)stream) != hipSuccess) return DPTX_E_HIP;
   return DPTX_OK;
 }
 

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/dptx.h"
+#include "host_util.h"
 #include "kernels.h"
 #include "unet.h"
 
@@ -30,21 +31,6 @@ namespace {
 
 constexpr int LEVELS = 6;
 inline int chan(int i) { return 16 << i; }
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-inline uint16_t to_bf16(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);  // RNE
-  return (uint16_t)(u >> 16);
-}
-inline uint16_t to_fp16(float f) {
-  const _Float16 h = (_Float16)f;  // RNE
-  uint16_t r;
-  memcpy(&r, &h, 2);
-  return r;
-}
 
 struct ConvLayer {
   std::string name;        // "down1.conv1", "mid_conv1", ...
@@ -183,18 +169,6 @@ int fail(dptx_unet_engine* h, int code, const std::string& msg) {
     if (r_ != hipSuccess) return fail(h, DPTX_E_HIP, std::string(#call) + ": " + hipGetErrorString(r_)); \
   } while (0)
 
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DevGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
 // launch classes of dptx_unet_debug_forward_classes
 constexpr int CLS_SMALL = 1, CLS_GEMM = 2, CLS_PASS = 4;
 
@@ -313,7 +287,7 @@ int check_forward_args(dptx_unet_engine* h, const void* x, void* y, int B, int H
 int forward_impl(dptx_unet_engine* h, const void* x, void* y, int B, int H, int W, int x_dtype, void* stream, int classes) {
   const int rc = check_forward_args(h, x, y, B, H, W, x_dtype);
   if (rc != DPTX_OK) return rc;
-  DevGuard guard(h->cfg.device_id);
+  DeviceGuard guard(h->cfg.device_id);
   Fwd f{h, (hipStream_t)stream, B, H, W, classes};
   f.run(x, x_dtype, (float*)y);
   if (f.rc != hipSuccess) return fail(h, DPTX_E_HIP, std::string(f.where) + ": " + hipGetErrorString(f.rc));
@@ -363,7 +337,7 @@ int dptx_unet_create(dptx_unet_handle* out, const dptx_unet_config* cfg) {
 void dptx_unet_destroy(dptx_unet_handle h) {
   if (!h) return;
   if (h->cfg.device_id >= 0) {
-    DevGuard guard(h->cfg.device_id);
+    DeviceGuard guard(h->cfg.device_id);
     if (h->d_blob) (void)hipFree(h->d_blob);
     if (h->d_arena) (void)hipFree(h->d_arena);
     if (h->d_flag) (void)hipFree(h->d_flag);
@@ -406,7 +380,7 @@ int dptx_unet_finalize_weights(dptx_unet_handle h) {
   if (nmiss) return fail(h, DPTX_E_KEY, "missing tensors (" + std::to_string(nmiss) + "): " + missing + (nmiss > 16 ? ", ..." : ""));
   h->blob.assign(h->packed_bytes, 0);
   const bool bf = h->mode == MODE_BF16;
-  auto cvt = [&](float f) { return bf ? to_bf16(f) : to_fp16(f); };
+  auto cvt = [&](float f) { return bf ? f32_to_bf16(f) : f32_to_fp16(f); };
   for (const std::string& k : h->keys) {
     const Entry& en = h->entries[k];
     uint8_t* dst = h->blob.data() + h->packed_off[k].first;
@@ -427,7 +401,7 @@ int dptx_unet_finalize_weights(dptx_unet_handle h) {
     }
   }
   if (h->cfg.device_id >= 0) {
-    DevGuard guard(h->cfg.device_id);
+    DeviceGuard guard(h->cfg.device_id);
     if (!h->d_blob) UCHK(h, hipMalloc((void**)&h->d_blob, h->packed_bytes));
     if (!h->d_arena) UCHK(h, hipMalloc((void**)&h->d_arena, h->arena_bytes));
     if (!h->d_flag) {
@@ -479,7 +453,7 @@ int dptx_unet_range_status(dptx_unet_handle h, int32_t* nonfinite, int32_t reset
   *nonfinite = 0;
   if (h->cfg.device_id < 0) return fail(h, DPTX_E_NODEVICE, "host-only handle");
   if (!h->d_flag) return DPTX_OK;  // no forward yet
-  DevGuard guard(h->cfg.device_id);
+  DeviceGuard guard(h->cfg.device_id);
   unsigned v = 0;
   UCHK(h, hipMemcpyAsync(&v, h->d_flag, sizeof v, hipMemcpyDeviceToHost, (hipStream_t)stream));
   UCHK(h, hipStreamSynchronize((hipStream_t)stream));
@@ -492,7 +466,7 @@ int dptx_unet_debug_arena_fill(dptx_unet_handle h, int32_t byte_value) {
   if (!h) return DPTX_E_INVALID;
   if (h->cfg.device_id < 0) return fail(h, DPTX_E_NODEVICE, "host-only handle");
   if (!h->d_arena) return fail(h, DPTX_E_INVALID, "weights not finalized");
-  DevGuard guard(h->cfg.device_id);
+  DeviceGuard guard(h->cfg.device_id);
   UCHK(h, hipDeviceSynchronize());
   UCHK(h, hipMemset(h->d_arena, byte_value, h->arena_bytes));
   UCHK(h, hipDeviceSynchronize());
