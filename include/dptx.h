@@ -438,6 +438,62 @@ int dptx_postprocess_guided_batch(const void* y_dev, const void* guide_lo_dev, i
                                   const dptx_guided_params* params, int32_t mode, void* out_dev, const void* lut_dev,
                                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Training augmentations: the blur chain on the image and the crop / resize of a batch's task tensors (no handle; DEVICE
+ * pointers unless stated) ----
+ * The two steps of omnidata_tools/torch/data/augmentation.py:14-118 (augment_rgb, resize_augmentation) as kernels; the random
+ * decisions stay with the caller (omnidata_amd/augmentation.py).  Conventions as above: stream-ordered, no workspace, no
+ * allocation, no host synchronisation (graph-capturable), DPTX_E_INVALID before anything is launched; no atomics, bitwise
+ * reproducible; an image's result does not depend on the batch.  All arithmetic fp32; "fma chain" below means acc = 0, then
+ * acc = fma(weight, value, acc) for the taps in row-major order, one rounding per tap.
+ *
+ * dptx_augment_filter_chain: x [B][C][H][W] fp32 -> out, the same shape; every filter works per channel with the parameters of
+ * its sample b.  The active stages (a non-NULL parameter pointer) run in the order sharpness, motion blur, Gaussian blur, each
+ * on the previous stage's result and each with its own rule at the image border.  One launch.
+ *   Sharpness, f = sharp_factor[b] (Pillow's ImageEnhance.Sharpness: SMOOTH filter, untouched border, blend):
+ *     1. d(y, x) = fma chain of x over the 3 x 3 window around (y, x) with the weights fl(1/13), centre fl(5/13), for
+ *        1 <= y <= H - 2 and 1 <= x <= W - 2; d = x on the one-pixel border and everywhere when H < 3 or W < 3;
+ *     2. s = d + (x - d) * f: a subtraction, a product, a sum, each rounded;  f == 1: s = x, bit for bit.
+ *   Motion blur, t = motion_taps[b] ([km][km], km in {3, 5, 7}; the caller builds and normalises the table):
+ *     m(y, x) = fma chain over t[r][q] and s(y + r - km/2, x + q - km/2), a correlation; s is 0 outside the image.
+ *   Gaussian blur, gy = gauss_y[b] ([kgy]), gx = gauss_x[b] ([kgx]), kgy, kgx in {1, 3, 5, 7}, H > kgy/2 and W > kgx/2:
+ *     g(y, x) = fma chain over the weights gy[i] * gx[j] (one fp32 product) and m(R(y + i - kgy/2, H), R(x + j - kgx/2, W)) with
+ *     the reflection R(i, n) = -i for i < 0, 2 (n - 1) - i for i >= n (F.pad's 'reflect': the edge is not repeated).
+ *   A table that is the identity (one weight 1, the others 0) returns its stage's input for finite values.
+ * out must not overlap x.  Range: 1 <= B, C; 1 <= H, W <= 16384; at least one stage; gauss_y and gauss_x both or neither.
+ *
+ * dptx_augment_resize_tasks: the same window or the same resize for every task tensor of a batch, in one launch.  `tasks` is a
+ * HOST array of 1..8 descriptors read before the call returns: src [B][C][Hs][Ws] -> dst [B][C][h][w], contiguous, of 4-byte
+ * (DPTX_AUG_F32) or 1-byte (DPTX_AUG_U8) elements; dst must not overlap src.
+ *   DPTX_AUG_CROP    dst(y, x) = src(y0 + y, x0 + x), bit for bit; the window lies inside the source;
+ *   DPTX_AUG_RESIZE  F.interpolate(src, (h, w)) with align_corners=False (y0, x0 ignored):
+ *     DPTX_AUG_NEAREST   src(min((int)floorf(y * sh), Hs - 1), min((int)floorf(x * sw), Ws - 1)) with sh = (float)Hs / h,
+ *                        sw = (float)Ws / w -- CPU ATen's index rule, bit for bit;
+ *     DPTX_AUG_BILINEAR  (DPTX_AUG_F32 only) the coordinates and the blend of dptx_postprocess_resize_batch's bilinear modes:
+ *                        s = max(sh * (y + 0.5) - 0.5, 0), i0 = min(floor(s), Hs - 1), i1 = i0 + (i0 < Hs - 1), l1 = s - i0,
+ *                        l0 = 1 - l1 (an axis whose sizes agree copies); ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d),
+ *                        every operation rounded on its own.
+ * Range: 1 <= B, C; 1 <= Hs, Ws, h, w <= 16384. */
+#define DPTX_AUG_F32 0
+#define DPTX_AUG_U8 1
+#define DPTX_AUG_BILINEAR 0
+#define DPTX_AUG_NEAREST 1
+#define DPTX_AUG_CROP 0
+#define DPTX_AUG_RESIZE 1
+#define DPTX_AUG_MAX_TASKS 8
+typedef struct dptx_augment_task {
+  const void* src; /* [B][C][Hs][Ws] */
+  void* dst;       /* [B][C][h][w]   */
+  int32_t C;
+  int32_t dtype;   /* DPTX_AUG_F32 / DPTX_AUG_U8 */
+  int32_t interp;  /* DPTX_AUG_BILINEAR / DPTX_AUG_NEAREST; read for DPTX_AUG_RESIZE only */
+  int32_t reserved;
+} dptx_augment_task;
+int dptx_augment_filter_chain(const void* x_dev, int32_t B, int32_t C, int32_t H, int32_t W, const float* sharp_factor_dev,
+                              const float* motion_taps_dev, int32_t km, const float* gauss_y_dev, const float* gauss_x_dev,
+                              int32_t kgy, int32_t kgx, void* out_dev, void* stream);
+int dptx_augment_resize_tasks(const dptx_augment_task* tasks, int32_t n_tasks, int32_t B, int32_t Hs, int32_t Ws, int32_t op,
+                              int32_t y0, int32_t x0, int32_t h, int32_t w, void* stream);
+
 /* ---- Test-time augmentation for surface normals: the merge of an image's views (no handle; DEVICE pointers unless stated) ----
  * The protocol of paper_code/oasis_eval_tta.py:440-448,487-534 (SurfaceNormalsTTAWrapper, MedianMerger): every view -- a window
  * of the image, possibly mirrored, at its own network size -- is mapped back into its window, and the views that cover a pixel

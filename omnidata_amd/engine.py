@@ -109,6 +109,8 @@ ABI = [
     ("dptx_postprocess_guided_workspace_bytes", C.c_int, [_i32, _i32, _i64p]),
     ("dptx_postprocess_guided_batch", C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, C.c_int64,
                                                 _vp]),
+    ("dptx_augment_filter_chain", C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    ("dptx_augment_resize_tasks", C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_refocus_workspace_bytes", C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64p]),
     ("dptx_refocus_quantiles", C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
     ("dptx_refocus", C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
