@@ -26,13 +26,11 @@ forward per image, edges where the image has them.  It excludes tta and tiled.
 """
 from __future__ import annotations
 
+import math
 import os
-from collections import deque
+import warnings
 from concurrent.futures import ThreadPoolExecutor
 
-import warnings
-
-import numpy as np
 import torch
 from PIL import Image
 
@@ -82,6 +80,35 @@ def plan_full_frame(sizes, mode: str, image_size: int = 384, batch_size: int = 3
     return chunks, capped
 
 
+def lookahead(pool, items, chunks, stop_on_error: bool = False):
+    """Yields (indices, decoded images, error) per chunk of `chunks` (lists of indices into items), in order: the decodes of the
+    next chunk are queued before this one is handed out, so they run while the caller has the GPU work of this one in flight.
+    A decode that raises propagates; with stop_on_error it ends the sequence instead: the images before it in its chunk are
+    handed out together with the exception, and the decodes queued behind it are cancelled."""
+    def submit(k):
+        return [pool.submit(_decode, items[i]) for i in chunks[k]] if k < len(chunks) else []
+
+    futures = submit(0)
+    for k, idxs in enumerate(chunks):
+        following = submit(k + 1)
+        images, error = [], None
+        for f in futures:
+            try:
+                images.append(f.result())
+            except Exception as e:  # noqa: BLE001 -- re-raised by the caller once the earlier images are done
+                if not stop_on_error:
+                    raise
+                error = e
+                break
+        if error is not None:
+            for f in following:
+                f.cancel()
+        yield idxs, images, error
+        if error is not None:
+            return
+        futures = following
+
+
 class BatchPredictor:
     def __init__(self, model, task: str, batch_size: int = 32, workers: int = 8, image_size: int = 384, full_frame=None,
                  renormalize: bool = False, tta=None, tta_merger: str = "median", tta_options=None, tta_align=None, tiled=None,
@@ -122,17 +149,17 @@ class BatchPredictor:
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
             raise RuntimeError("BatchPredictor needs the model on an AMD GPU: the forward is implemented as HIP kernels only")
-        self.tta = None
+        self._runner = None   # the TTA or tiled object that takes the images instead of the batched paths below
         if tta is not None and task == "depth":   # tta_options: DepthTTA's multiple / max_side / chunk_images
             from .tta import DepthTTA
-            self.tta = DepthTTA(model, tta, tta_merger, tta_align, batch_size=self.batch_size, **(tta_options or {}))
+            self._runner = DepthTTA(model, tta, tta_merger, tta_align, batch_size=self.batch_size, **(tta_options or {}))
         elif tta is not None:   # tta_options: NormalsTTA's multiple / max_side / chunk_images / normalize_views
             from .tta import NormalsTTA
-            self.tta = NormalsTTA(model, tta, tta_merger, batch_size=self.batch_size, **(tta_options or {}))
+            self._runner = NormalsTTA(model, tta, tta_merger, batch_size=self.batch_size, **(tta_options or {}))
         elif tiled is not None:   # the tiled classes are called as the TTA ones are: chunk_images inputs -> maps at their own sizes
             from .tiled import TiledDepth, TiledNormals
             options = dict(batch_size=self.batch_size, **({} if tiled is True else tiled))
-            self.tta = (TiledDepth if task == "depth" else TiledNormals)(model, **options)
+            self._runner = (TiledDepth if task == "depth" else TiledNormals)(model, **options)
 
     # ---- GPU side of one batch: decoded images -> final pixels, still on the device
     def _run(self, images) -> torch.Tensor:
@@ -143,31 +170,6 @@ class BatchPredictor:
             if self.task == "depth":
                 return pp.depths_to_rgba_gpu(pp.depths_to_512_gpu(y))
             return pp.normals_to_u8_gpu(y)
-
-    def _batches(self, items, pool):
-        """Yields (first index, decoded images, error): the decodes of the next batch are queued before this one is handed
-        out, so they run while the caller has the GPU work of this one in flight.  A decode that raises ends the sequence:
-        the images before it in its batch are handed out with the exception."""
-        chunks = [items[i:i + self.batch_size] for i in range(0, len(items), self.batch_size)]
-        if not chunks:
-            return
-        futures = [pool.submit(_decode, it) for it in chunks[0]]
-        for k, _ in enumerate(chunks):
-            nxt = [pool.submit(_decode, it) for it in chunks[k + 1]] if k + 1 < len(chunks) else []
-            images, error = [], None
-            for f in futures:
-                try:
-                    images.append(f.result())
-                except Exception as e:  # noqa: BLE001 -- re-raised by the caller once the earlier images are done
-                    error = e
-                    break
-            if error is not None:
-                for f in nxt:
-                    f.cancel()
-            yield k * self.batch_size, images, error
-            if error is not None:
-                return
-            futures = nxt
 
     # ---- full frame: the whole image in, a map of the image's own size out
     def _run_full(self, images, net_hw):
@@ -193,49 +195,58 @@ class BatchPredictor:
             mode = "depth_rgba" if self.task == "depth" else "normal_u8"
             return pp.guided_outputs_gpu(y, guide_lo, pixels, descs, sizes, mode, self.renormalize, **self.guided)
 
-    def _full_chunks(self, items, pool):
-        """Yields (input indices, decoded images, outputs) per chunk of plan_full_frame(), in the plan's order; the next chunk is
-        decoded while this one is on the GPU.  The sizes come from the files' headers first: an unreadable file raises here,
-        before anything has run."""
-        sizes = list(pool.map(_size_of, items))
-        chunks, self.capped = plan_full_frame(sizes, self.full_frame, self.image_size, self.batch_size)
-        if self.capped:
-            warnings.warn(f"full_frame='aspect': the network size of {len(self.capped)} image(s) was cut back to a side of "
-                          f"{pp.MAX_NET_SIDE} (BatchPredictor.capped lists them)", stacklevel=3)
-        futures = [pool.submit(_decode, items[i]) for i in chunks[0][1]] if chunks else []
-        for k, (net_hw, idxs) in enumerate(chunks):
-            following = [pool.submit(_decode, items[i]) for i in chunks[k + 1][1]] if k + 1 < len(chunks) else []
-            images = [f.result() for f in futures]
-            yield idxs, images, self._run_full(images, net_hw)
-            futures = following
-
-    def _tta_chunks(self, items, pool):
-        """_full_chunks for tta: chunks of chunk_images inputs in input order (one upload and one merge each); NormalsTTA returns
-        [H,W,3] uint8 and DepthTTA [H,W,4] uint8 RGBA by default."""
-        n = self.tta.chunk_images
-        chunks = [list(range(i, min(i + n, len(items)))) for i in range(0, len(items), n)]
-        futures = [pool.submit(_decode, items[i]) for i in chunks[0]] if chunks else []
-        for k, idxs in enumerate(chunks):
-            following = [pool.submit(_decode, items[i]) for i in chunks[k + 1]] if k + 1 < len(chunks) else []
-            images = [f.result() for f in futures]
-            yield idxs, images, self.tta(images)
-            futures = following
-
     def _chunks(self, items, pool):
-        return self._tta_chunks(items, pool) if self.tta is not None else self._full_chunks(items, pool)
+        """Yields (input indices, decoded images, outputs, error) per chunk; the next chunk is decoded while this one is on the GPU.
+        Centre crop: batch_size inputs in input order, outputs one tensor [B,...]; an unreadable file ends the sequence, the
+        images before it in its chunk handed out with the exception (lookahead's stop_on_error).  Full frame: the chunks of
+        plan_full_frame(), in the plan's order; tta and tiled: chunk_images inputs in input order (one upload and one merge or
+        blend each); outputs a list of tensors, image i at its own size.  There the sizes come from the files' headers first and
+        a decode error propagates: an unreadable file raises before anything has run."""
+        crop = self._runner is None and self.full_frame is None
+        if self._runner is None and not crop:
+            sizes = list(pool.map(_size_of, items))
+            plan, self.capped = plan_full_frame(sizes, self.full_frame, self.image_size, self.batch_size)
+            if self.capped:
+                warnings.warn(f"full_frame='aspect': the network size of {len(self.capped)} image(s) was cut back to a side of "
+                              f"{pp.MAX_NET_SIDE} (BatchPredictor.capped lists them)", stacklevel=3)
+        else:
+            step = self.batch_size if crop else self._runner.chunk_images
+            plan = [(None, list(range(i, min(i + step, len(items))))) for i in range(0, len(items), step)]
+        for (net_hw, _), (idxs, images, error) in zip(plan, lookahead(pool, items, [idxs for _, idxs in plan], crop)):
+            if crop:
+                outs = self._run(images) if images else None
+            else:
+                outs = self._runner(images) if self._runner is not None else self._run_full(images, net_hw)
+            yield idxs, images, outs, error
 
-    def _predict_full(self, items):
+    def predict(self, images_or_paths):
+        """Yields one device tensor per input, in input order (normal: [S,S,3] uint8, depth: [512,512,4] uint8 RGBA; with
+        full_frame, tta or tiled the image's own size: [H,W,3] uint8, depth [H,W,4] uint8 RGBA).  Nothing is read back."""
+        items = list(images_or_paths)
         ready, nxt = {}, 0   # outputs that wait for an earlier input of another bucket stay on the device
         with ThreadPoolExecutor(self.workers) as pool:
-            for idxs, _, outs in self._chunks(items, pool):
-                ready.update(zip(idxs, outs))
+            for idxs, images, outs, error in self._chunks(items, pool):
+                ready.update(zip(idxs, outs if images else ()))
                 while nxt in ready:
                     yield ready.pop(nxt)
                     nxt += 1
+                if error is not None:
+                    raise error
 
-    def _predict_full_to_dir(self, paths, output_path, verbose):
+    def predict_to_dir(self, paths, output_path, verbose: bool = False):
+        """Writes <stem>_<task>.png and <stem>_rgb.png for every path, as demo.py does; with `verbose` also its two lines per
+        file, in input order.  An unreadable file raises what Image.open raises, after every earlier file has been written.
+        With full_frame, tta or tiled: <stem>_<task>.png at the image's own size, <stem>_rgb.png = the image unchanged, and an
+        unreadable file raises before anything is written."""
+        paths = [os.fspath(p) for p in paths]
+        os.makedirs(output_path, exist_ok=True)
+        crop = self.full_frame is None and self._runner is None
+
         def save(img, pixels, stem):
-            rgb = img if img.mode in ("1", "L", "LA", "P", "RGB", "RGBA", "I", "I;16") else img.convert("RGB")
+            if crop:
+                rgb = pp.rgb_preview(img)
+            else:
+                rgb = img if img.mode in ("1", "L", "LA", "P", "RGB", "RGBA", "I", "I;16") else img.convert("RGB")
             rgb.save(os.path.join(output_path, f"{stem}_rgb.png"))
             Image.fromarray(pixels).save(os.path.join(output_path, f"{stem}_{self.task}.png"))
 
@@ -251,72 +262,28 @@ class BatchPredictor:
                     print(f"Writing output {save_path} ...")
                 nxt += 1
 
-        with ThreadPoolExecutor(self.workers) as pool:
-            for idxs, images, outs in self._chunks(paths, pool):
-                flat = torch.cat([o.reshape(-1) for o in outs])
-                host = torch.empty(flat.shape, dtype=flat.dtype, pin_memory=True)
-                host.copy_(flat, non_blocking=True)
-                torch.cuda.current_stream(self.device).synchronize()
-                arr, at = host.numpy(), 0
-                for i, img, o in zip(idxs, images, outs):
-                    stem = os.path.splitext(os.path.basename(paths[i]))[0]
-                    pixels = arr[at:at + o.numel()].reshape(tuple(o.shape))
-                    at += o.numel()
-                    writes[i] = (pool.submit(save, img, pixels, stem), os.path.join(output_path, f"{stem}_{self.task}.png"))
-                flush(False)
-            flush(True)
-
-    def predict(self, images_or_paths):
-        """Yields one device tensor per input, in input order (normal: [S,S,3] uint8, depth: [512,512,4] uint8 RGBA; with
-        full_frame, tta or tiled the image's own size: [H,W,3] uint8, depth [H,W,4] uint8 RGBA).  Nothing is read back."""
-        items = list(images_or_paths)
-        if self.full_frame is not None or self.tta is not None:
-            yield from self._predict_full(items)
-            return
-        with ThreadPoolExecutor(self.workers) as pool:
-            for _, images, error in self._batches(items, pool):
-                if images:
-                    yield from self._run(images).unbind(0)
-                if error is not None:
-                    raise error
-
-    def predict_to_dir(self, paths, output_path, verbose: bool = False):
-        """Writes <stem>_<task>.png and <stem>_rgb.png for every path, as demo.py does; with `verbose` also its two lines per
-        file, in input order.  An unreadable file raises what Image.open raises, after every earlier file has been written."""
-        paths = [os.fspath(p) for p in paths]
-        os.makedirs(output_path, exist_ok=True)
-        if self.full_frame is not None or self.tta is not None:   # <stem>_<task>.png at the image's own size, <stem>_rgb.png = the image unchanged
-            return self._predict_full_to_dir(paths, output_path, verbose)
-        writes = deque()   # (future, path, save_path) in input order
-
-        def save(img, pixels, stem):
-            pp.rgb_preview(img).save(os.path.join(output_path, f"{stem}_rgb.png"))
-            Image.fromarray(pixels).save(os.path.join(output_path, f"{stem}_{self.task}.png"))
-
-        def flush(everything):
-            while writes and (everything or writes[0][0].done()):
-                f, path, save_path = writes.popleft()
-                f.result()
-                if verbose:
-                    print(f"Reading input {path} ...")
-                    print(f"Writing output {save_path} ...")
+        def write(pool, idxs, images, flat, shapes):
+            """One read-back of a chunk's pixels (flat: one device tensor, image i its next prod(shapes[i]) elements) into pinned
+            memory, and one save per image in the pool."""
+            host = torch.empty(flat.shape, dtype=flat.dtype, pin_memory=True)
+            host.copy_(flat, non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            arr, at = host.numpy(), 0
+            for i, img, shape in zip(idxs, images, shapes):
+                stem = os.path.splitext(os.path.basename(paths[i]))[0]
+                pixels = arr[at:at + math.prod(shape)].reshape(shape)
+                at += pixels.size
+                writes[i] = (pool.submit(save, img, pixels, stem), os.path.join(output_path, f"{stem}_{self.task}.png"))
 
         with ThreadPoolExecutor(self.workers) as pool:
-            for first, images, error in self._batches(paths, pool):
-                if images:
-                    out = self._run(images)
-                    host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
-                    host.copy_(out, non_blocking=True)
-                    torch.cuda.current_stream(self.device).synchronize()
-                    arr = host.numpy()
-                    for j, img in enumerate(images):
-                        path = paths[first + j]
-                        stem = os.path.splitext(os.path.basename(path))[0]
-                        save_path = os.path.join(output_path, f"{stem}_{self.task}.png")
-                        writes.append((pool.submit(save, img, arr[j], stem), path, save_path))
+            for idxs, images, outs, error in self._chunks(paths, pool):
+                if images and crop:
+                    write(pool, idxs, images, outs.reshape(-1), [tuple(outs.shape[1:])] * len(images))
+                elif images:
+                    write(pool, idxs, images, torch.cat([o.reshape(-1) for o in outs]), [tuple(o.shape) for o in outs])
                 flush(error is not None)
                 if error is not None:
                     if verbose:
-                        print(f"Reading input {paths[first + len(images)]} ...")
+                        print(f"Reading input {paths[idxs[len(images)]]} ...")
                     raise error
             flush(True)

@@ -93,7 +93,7 @@ def image_to_input_gpu(img, task: str, device="cuda:0") -> torch.Tensor:
     """Same result as image_to_input() (bit-identical), computed on the GPU from the raw uint8 pixels: only the
     undecoded image crosses PCIe.  RGB / greyscale uint8 images; other modes (RGBA is premultiplied by Pillow's
     resize) take the PIL path."""
-    from .engine import load_library
+    from ._native import call
     if isinstance(img, Image.Image):
         if img.mode not in ("RGB", "L"):
             return image_to_input(img, task).to(device)
@@ -106,32 +106,25 @@ def image_to_input_gpu(img, task: str, device="cuda:0") -> torch.Tensor:
     a = a.to(device).contiguous()
     H, W, C = a.shape
     x = torch.empty(1, 3, 384, 384, dtype=torch.float32, device=device)
-    rc = load_library().dptx_preprocess_u8(a.data_ptr(), H, W, C, W * C, int(task == "depth"), x.data_ptr(),
-                                           torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"dptx_preprocess_u8 failed ({rc})")
+    call("dptx_preprocess_u8", a.data_ptr(), H, W, C, W * C, int(task == "depth"), x.data_ptr(), torch.cuda.current_stream().cuda_stream)
     return x
 
 
 def normal_to_u8_gpu(output: torch.Tensor) -> torch.Tensor:
     """[3,384,384] float (cuda) -> [384,384,3] uint8 (cuda): clamp(0,1)*255 truncated, as ToPILImage does."""
-    from .engine import load_library
+    from ._native import call
     y = output.detach().float().contiguous()
     out = torch.empty(384, 384, 3, dtype=torch.uint8, device=y.device)
-    rc = load_library().dptx_postprocess_normal_u8(y.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"dptx_postprocess_normal_u8 failed ({rc})")
+    call("dptx_postprocess_normal_u8", y.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
     return out
 
 
 def depth_to_512_gpu(output: torch.Tensor) -> torch.Tensor:
     """[384,384] float (cuda) -> [512,512] float (cuda): bicubic, clamp(0,1), 1-x (demo.py:143-145)."""
-    from .engine import load_library
+    from ._native import call
     y = output.detach().float().reshape(384, 384).contiguous()
     out = torch.empty(512, 512, dtype=torch.float32, device=y.device)
-    rc = load_library().dptx_postprocess_depth(y.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"dptx_postprocess_depth failed ({rc})")
+    call("dptx_postprocess_depth", y.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
     return out
 
 
@@ -147,9 +140,6 @@ class ImageDesc(_C.Structure):
     _fields_ = [("offset", _C.c_int64), ("H", _C.c_int32), ("W", _C.c_int32), ("C", _C.c_int32), ("row_stride_bytes", _C.c_int32)]
 
 
-_lut_cache: dict = {}
-
-
 def _as_hwc_u8(img) -> np.ndarray:
     a = np.asarray(img)
     if a.ndim == 2:
@@ -159,8 +149,9 @@ def _as_hwc_u8(img) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
-def batch_supported(img, image_size: int = 384) -> bool:
-    """Whether dptx_preprocess_u8_batch takes this image (mode RGB / L inside the supported range); the others go through PIL."""
+def _supported(img, limit) -> bool:
+    """Whether the batched resize kernels take this image: a PIL image of mode RGB / L or a uint8 HW / HW1 / HW3 array whose sides
+    limit(h, w) accepts."""
     if isinstance(img, Image.Image):
         if img.mode not in ("RGB", "L"):
             return False
@@ -170,7 +161,12 @@ def batch_supported(img, image_size: int = 384) -> bool:
         if a.dtype not in (np.uint8, torch.uint8) or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)):
             return False
         h, w = a.shape[:2]
-    return 1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE and min(h, w) <= MAX_SCALE * image_size
+    return limit(h, w)
+
+
+def batch_supported(img, image_size: int = 384) -> bool:
+    """Whether dptx_preprocess_u8_batch takes this image (mode RGB / L inside the supported range); the others go through PIL."""
+    return _supported(img, lambda h, w: 1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE and min(h, w) <= MAX_SCALE * image_size)
 
 
 def pack_images(images):
@@ -190,38 +186,60 @@ def pack_images(images):
     return buf, descs
 
 
-def images_to_input_gpu(images, task: str, image_size: int = 384, device="cuda:0") -> torch.Tensor:
-    """[B,3,S,S] fp32 on `device`: image_to_input() of every image (bit-identical), from ONE host->device copy of the raw
-    pixels and one ragged-batch resize on the GPU.  Images the kernel does not take (other modes than RGB / L, sides outside
-    its range) go through image_to_input() and are copied into their slot."""
-    from ._native import call, workspace
+def _as_pil(img) -> Image.Image:
+    return img if isinstance(img, Image.Image) else Image.fromarray(np.asarray(img))
+
+
+def _upload_and_resize(images, task: str, out_hw, device, supported, entry, unsupported: str, fallback, return_pixels: bool = False):
+    """What images_to_input_gpu and images_to_input_rect_gpu share: the images `supported` accepts are packed, uploaded in one
+    copy and resized by entry = (entry point, its workspace entry, the shape arguments both take after the count) -- straight
+    into x when that is all of them, else scattered into their slots --; the others go through fallback(PIL image) -> [1,3,OH,OW].
+    `unsupported` is the ValueError's text where the workspace entry rejects the shape.  return_pixels: see
+    images_to_input_rect_gpu."""
+    from ._native import MAX_DESCS, at, call, chunks, workspace
     images = list(images)
-    B, S = len(images), int(image_size)
+    B, (OH, OW) = len(images), out_hw
     device = torch.device(device)
-    x = torch.empty(B, 3, S, S, dtype=torch.float32, device=device)
+    x = torch.empty(B, 3, OH, OW, dtype=torch.float32, device=device)
     if B == 0:
-        return x
-    fast = [i for i, im in enumerate(images) if batch_supported(im, S)]
+        return (x, torch.empty(16, dtype=torch.uint8, device=device), (ImageDesc * 1)()) if return_pixels else x
+    fast = [i for i, im in enumerate(images) if supported(im)]
     slow = sorted(set(range(B)) - set(fast))
-    if fast:
+    dev = all_descs = None
+    if return_pixels:   # one buffer with every image; the resize reads the descriptors of the images it takes
+        buf, all_descs = pack_images([_as_pil(im).convert("RGB") if i in slow else im for i, im in enumerate(images)])
+        descs = (ImageDesc * max(len(fast), 1))(*[all_descs[i] for i in fast])
+        if not fast:
+            with torch.cuda.device(device):
+                dev = buf.to(device, non_blocking=True)
+    elif fast:
         buf, descs = pack_images([images[i] for i in fast])
-        ws = workspace("dptx_preprocess_batch_workspace_bytes", device, (min(len(fast), 4096), S),
-                       f"image_size {S} is not a multiple of 32 in [32, 1024]")
+    if fast:
+        name, ws_name, shape = entry
+        ws = workspace(ws_name, device, (min(len(fast), MAX_DESCS), *shape), unsupported)
         with torch.cuda.device(device):
             dev = buf.to(device, non_blocking=True)
             stream = torch.cuda.current_stream().cuda_stream
             direct = len(fast) == B
-            xf = x if direct else torch.empty(len(fast), 3, S, S, dtype=torch.float32, device=device)
-            for b0 in range(0, len(fast), 4096):
-                n = min(4096, len(fast) - b0)
-                call("dptx_preprocess_u8_batch", dev.data_ptr(), _C.addressof(descs) + b0 * _C.sizeof(ImageDesc), n, S,
-                     int(task == "depth"), xf[b0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
+            xf = x if direct else torch.empty(len(fast), 3, OH, OW, dtype=torch.float32, device=device)
+            for b0, n in chunks(len(fast)):
+                call(name, dev.data_ptr(), at(descs, b0), n, *shape, int(task == "depth"), xf[b0:].data_ptr(), ws.data_ptr(),
+                     ws.numel(), stream)
             if not direct:
                 x[torch.tensor(fast, device=device)] = xf
     for i in slow:
-        im = images[i] if isinstance(images[i], Image.Image) else Image.fromarray(np.asarray(images[i]))
-        x[i:i + 1] = image_to_input(im, task, S).to(device)
-    return x
+        x[i:i + 1] = fallback(_as_pil(images[i])).to(device)
+    return (x, dev, all_descs) if return_pixels else x
+
+
+def images_to_input_gpu(images, task: str, image_size: int = 384, device="cuda:0") -> torch.Tensor:
+    """[B,3,S,S] fp32 on `device`: image_to_input() of every image (bit-identical), from ONE host->device copy of the raw
+    pixels and one ragged-batch resize on the GPU.  Images the kernel does not take (other modes than RGB / L, sides outside
+    its range) go through image_to_input() and are copied into their slot."""
+    S = int(image_size)
+    return _upload_and_resize(images, task, (S, S), device, lambda im: batch_supported(im, S),
+                              ("dptx_preprocess_u8_batch", "dptx_preprocess_batch_workspace_bytes", (S,)),
+                              f"image_size {S} is not a multiple of 32 in [32, 1024]", lambda im: image_to_input(im, task, S))
 
 
 def normals_to_u8_gpu(output: torch.Tensor) -> torch.Tensor:
@@ -256,14 +274,11 @@ def viridis_lut() -> np.ndarray:
 
 def depths_to_rgba_gpu(maps: torch.Tensor) -> torch.Tensor:
     """[B,H,W] float (cuda) -> [B,H,W,4] uint8 (cuda): colorize_viridis() of every map (its own min / max), on the GPU."""
-    from ._native import call, check_cuda, workspace
+    from ._native import call, check_cuda, viridis_lut_on, workspace
     check_cuda("maps", maps)
     m = maps.detach().float().contiguous()
     B, N = m.shape[0], m[0].numel()
-    key = str(m.device)
-    lut = _lut_cache.get(key)
-    if lut is None:
-        lut = _lut_cache[key] = torch.from_numpy(viridis_lut()).to(m.device)
+    lut = viridis_lut_on(m.device)
     ws = workspace("dptx_colorize_workspace_bytes", m.device, (B, N), f"colorize: unsupported shape {tuple(m.shape)}")
     out = torch.empty(*m.shape, 4, dtype=torch.uint8, device=m.device)
     with torch.cuda.device(m.device):
@@ -322,20 +337,7 @@ def image_to_input_rect(img: Image.Image, task: str, net_hw) -> torch.Tensor:
 def rect_supported(img, net_hw) -> bool:
     """Whether dptx_preprocess_u8_rect_batch takes this image for the target (OH, OW); the others go through PIL."""
     OH, OW = net_hw
-    if isinstance(img, Image.Image):
-        if img.mode not in ("RGB", "L"):
-            return False
-        w, h = img.size
-    else:
-        a = np.asarray(img) if not isinstance(img, torch.Tensor) else img
-        if a.dtype not in (np.uint8, torch.uint8) or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)):
-            return False
-        h, w = a.shape[:2]
-    return 1 <= h <= min(MAX_SIDE, MAX_SCALE * OH) and 1 <= w <= min(MAX_SIDE, MAX_SCALE * OW)
-
-
-def _as_pil(img) -> Image.Image:
-    return img if isinstance(img, Image.Image) else Image.fromarray(np.asarray(img))
+    return _supported(img, lambda h, w: 1 <= h <= min(MAX_SIDE, MAX_SCALE * OH) and 1 <= w <= min(MAX_SIDE, MAX_SCALE * OW))
 
 
 def images_to_input_rect_gpu(images, task: str, net_hw, device="cuda:0", return_pixels: bool = False):
@@ -343,42 +345,11 @@ def images_to_input_rect_gpu(images, task: str, net_hw, device="cuda:0", return_
     pixels and one ragged-batch resize on the GPU.  Images the kernel does not take go through PIL into their slot.
     return_pixels=True -> (x, pixels_dev, descs): also the uploaded uint8 pixel buffer and the ImageDesc array of ALL B images in
     input order, for guided_outputs_gpu; an image that takes the PIL path is packed as img.convert("RGB").  x is the same."""
-    from ._native import call, workspace
-    images = list(images)
-    OH, OW = int(net_hw[0]), int(net_hw[1])
-    B = len(images)
-    device = torch.device(device)
-    x = torch.empty(B, 3, OH, OW, dtype=torch.float32, device=device)
-    if B == 0:
-        return (x, torch.empty(16, dtype=torch.uint8, device=device), (ImageDesc * 1)()) if return_pixels else x
-    fast = [i for i, im in enumerate(images) if rect_supported(im, (OH, OW))]
-    slow = sorted(set(range(B)) - set(fast))
-    dev = all_descs = None
-    if return_pixels:   # one buffer with every image; the resize reads the descriptors of the images it takes
-        buf, all_descs = pack_images([_as_pil(im).convert("RGB") if i in slow else im for i, im in enumerate(images)])
-        descs = (ImageDesc * max(len(fast), 1))(*[all_descs[i] for i in fast])
-        if not fast:
-            with torch.cuda.device(device):
-                dev = buf.to(device, non_blocking=True)
-    elif fast:
-        buf, descs = pack_images([images[i] for i in fast])
-    if fast:
-        ws = workspace("dptx_preprocess_rect_batch_workspace_bytes", device, (min(len(fast), 4096), OH, OW),
-                       f"network size {(OH, OW)}: both sides must be multiples of 32 in [64, 1024]")
-        with torch.cuda.device(device):
-            dev = buf.to(device, non_blocking=True)
-            stream = torch.cuda.current_stream().cuda_stream
-            direct = len(fast) == B
-            xf = x if direct else torch.empty(len(fast), 3, OH, OW, dtype=torch.float32, device=device)
-            for b0 in range(0, len(fast), 4096):
-                n = min(4096, len(fast) - b0)
-                call("dptx_preprocess_u8_rect_batch", dev.data_ptr(), _C.addressof(descs) + b0 * _C.sizeof(ImageDesc), n, OH, OW,
-                     int(task == "depth"), xf[b0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
-            if not direct:
-                x[torch.tensor(fast, device=device)] = xf
-    for i in slow:
-        x[i:i + 1] = image_to_input_rect(_as_pil(images[i]), task, (OH, OW)).to(device)
-    return (x, dev, all_descs) if return_pixels else x
+    hw = (int(net_hw[0]), int(net_hw[1]))
+    return _upload_and_resize(images, task, hw, device, lambda im: rect_supported(im, hw),
+                              ("dptx_preprocess_u8_rect_batch", "dptx_preprocess_rect_batch_workspace_bytes", hw),
+                              f"network size {hw}: both sides must be multiples of 32 in [64, 1024]",
+                              lambda im: image_to_input_rect(im, task, hw), return_pixels)
 
 
 def output_layout(sizes, mode: str):
@@ -394,44 +365,65 @@ def output_layout(sizes, mode: str):
     return descs, off
 
 
+def _one_of(name: str, value, allowed) -> None:
+    """ValueError('<name> must be "a" or "b"') -- 'one of [...]' for more than two -- unless value is one of `allowed`."""
+    if value not in allowed:
+        names = [f'"{a}"' if isinstance(a, str) else str(a) for a in allowed]
+        raise ValueError(f"{name} must be " + (" or ".join(names) if len(names) == 2 else f"one of {sorted(allowed)}"))
+
+
+def _int_sizes(sizes):
+    return [(int(H), int(W)) for H, W in sizes]
+
+
+def _packed_outputs(sizes, mode: str, device):
+    """-> (descs, out): output_layout() of `sizes` and the uint8 device buffer it describes; _output_views() slices it."""
+    descs, total = output_layout(sizes, mode)
+    return descs, torch.empty(max(total, 16), dtype=torch.uint8, device=device)
+
+
+def _resize_code(mode: str, renormalize: bool) -> int:
+    """The mode argument of the resize and guided entry points; ValueError for an unknown mode or renormalize on depth."""
+    _one_of("mode", mode, RESIZE_MODES)
+    if renormalize and not mode.startswith("normal"):
+        raise ValueError("renormalize applies to surface normals only")
+    return RESIZE_MODES[mode] | (RESIZE_RENORM if renormalize else 0)
+
+
+def _resize_outputs(sizes, mode: str, code: int, device, ws_entry: str):
+    """-> (descs, out, (lut pointer, workspace pointer, workspace bytes)): the packed outputs of `sizes`, whose sides are checked,
+    and what depth_rgba needs besides, the colormap and the workspace of the range pass (zeros for the other modes)."""
+    from ._native import MAX_DESCS, viridis_lut_on, workspace
+    if any(not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE) for H, W in sizes):
+        raise ValueError(f"output sides must be in [1, {MAX_SIDE}]")
+    descs, out = _packed_outputs(sizes, mode, device)
+    if mode != "depth_rgba":
+        return descs, out, (0, 0, 0)
+    ws = workspace(ws_entry, device, (min(len(sizes), MAX_DESCS), code), "unsupported mode")
+    return descs, out, (viridis_lut_on(device).data_ptr(), ws.data_ptr(), ws.numel())
+
+
 def resize_outputs_gpu(y: torch.Tensor, sizes, mode: str, renormalize: bool = False):
     """y [B,3,h,w] (normal_*) or [B,h,w] / [B,1,h,w] (depth_*) float (cuda), sizes [(H, W)] * B -> list of B device tensors
     (views of one packed buffer), output i at its own size: normal_u8 [H,W,3] uint8, normal_f32 [3,H,W] fp32, depth_f32 [H,W]
     fp32, depth_rgba [H,W,4] uint8 (viridis over the map's own range).  One entry-point call per 4096 outputs."""
-    from ._native import call, check_cuda, workspace
+    from ._native import at, call, check_cuda, chunks
     check_cuda("y", y)
-    if mode not in RESIZE_MODES:
-        raise ValueError(f"mode must be one of {sorted(RESIZE_MODES)}")
-    normal = mode.startswith("normal")
-    if renormalize and not normal:
-        raise ValueError("renormalize applies to surface normals only")
+    code = _resize_code(mode, renormalize)
     h, w = y.shape[-2:]
-    y = y.detach().float().reshape(-1, 3 if normal else 1, h, w).contiguous()
-    sizes = [(int(H), int(W)) for H, W in sizes]
+    y = y.detach().float().reshape(-1, 3 if mode.startswith("normal") else 1, h, w).contiguous()
+    sizes = _int_sizes(sizes)
     B = y.shape[0]
     if len(sizes) != B:
         raise ValueError(f"{B} maps but {len(sizes)} sizes")
     if B == 0:
         return []
-    if any(not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE) for H, W in sizes):
-        raise ValueError(f"output sides must be in [1, {MAX_SIDE}]")
-    descs, total = output_layout(sizes, mode)
-    code = RESIZE_MODES[mode] | (RESIZE_RENORM if renormalize else 0)
-    out = torch.empty(max(total, 16), dtype=torch.uint8, device=y.device)
-    lut_ptr = ws_ptr = ws_n = 0
-    if mode == "depth_rgba":
-        key = str(y.device)
-        lut = _lut_cache.get(key)
-        if lut is None:
-            lut = _lut_cache[key] = torch.from_numpy(viridis_lut()).to(y.device)
-        ws = workspace("dptx_postprocess_resize_workspace_bytes", y.device, (min(B, 4096), code), "unsupported mode")
-        lut_ptr, ws_ptr, ws_n = lut.data_ptr(), ws.data_ptr(), ws.numel()
+    descs, out, tail = _resize_outputs(sizes, mode, code, y.device, "dptx_postprocess_resize_workspace_bytes")
     with torch.cuda.device(y.device):
         stream = torch.cuda.current_stream().cuda_stream
-        for b0 in range(0, B, 4096):
-            n = min(4096, B - b0)
-            call("dptx_postprocess_resize_batch", y[b0:].data_ptr(), n, y.shape[1], h, w,
-                 _C.addressof(descs) + b0 * _C.sizeof(ImageDesc), code, out.data_ptr(), lut_ptr, ws_ptr, ws_n, stream)
+        for b0, n in chunks(B):
+            call("dptx_postprocess_resize_batch", y[b0:].data_ptr(), n, y.shape[1], h, w, at(descs, b0), code, out.data_ptr(), *tail,
+                 stream)
     return _output_views(out, descs, sizes, mode)
 
 
@@ -491,54 +483,36 @@ def guided_outputs_gpu(y: torch.Tensor, guide_lo: torch.Tensor, pixels_dev: torc
       quantisation; depth: clamp, 1 - x; depth_rgba: viridis over the map's own range).
     radius R in {1, 2, 3}, sigma_space in low-resolution pixels, sigma_range in [0, 1] colour units.  include/dptx.h ("Guided
     upsampling") is the full statement.  One entry-point call per 4096 outputs; bitwise reproducible, independent of the batch."""
-    from ._native import call, check_cuda, workspace
+    from ._native import at, call, check_cuda, chunks
     check_cuda("y", y)
     check_cuda("guide_lo", guide_lo)
     check_cuda("pixels_dev", pixels_dev)
-    if mode not in RESIZE_MODES:
-        raise ValueError(f"mode must be one of {sorted(RESIZE_MODES)}")
-    normal = mode.startswith("normal")
-    if renormalize and not normal:
-        raise ValueError("renormalize applies to surface normals only")
+    code = _resize_code(mode, renormalize)
     params = GuidedParams(**guided_params(dict(radius=radius, sigma_space=sigma_space, sigma_range=sigma_range)))
     h, w = y.shape[-2:]
-    y = y.detach().float().reshape(-1, 3 if normal else 1, h, w).contiguous()
+    y = y.detach().float().reshape(-1, 3 if mode.startswith("normal") else 1, h, w).contiguous()
     B = y.shape[0]
     if tuple(guide_lo.shape) != (B, 3, h, w):
         raise ValueError(f"guide_lo must be [{B}, 3, {h}, {w}], the maps' resolution; got {tuple(guide_lo.shape)}")
     guide_lo = guide_lo.detach().float().contiguous()
     if pixels_dev.dtype != torch.uint8 or not pixels_dev.is_contiguous() or guide_lo.device != y.device or pixels_dev.device != y.device:
         raise ValueError("pixels_dev must be a contiguous uint8 tensor, and the guides must be on the maps' device")
-    sizes = [(int(H), int(W)) for H, W in sizes]
+    sizes = _int_sizes(sizes)
     if len(sizes) != B or len(descs) < B:
         raise ValueError(f"{B} maps but {len(sizes)} sizes and {len(descs)} guide descriptors")
     if B == 0:
         return []
-    if any(not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE) for H, W in sizes):
-        raise ValueError(f"output sides must be in [1, {MAX_SIDE}]")
+    outs, out, tail = _resize_outputs(sizes, mode, code, y.device, "dptx_postprocess_guided_workspace_bytes")
     for i, (H, W) in enumerate(sizes):
         d = descs[i]
         if (d.H, d.W) != (H, W) or d.C not in (1, 3) or d.row_stride_bytes < d.W * d.C or d.offset < 0 or \
                 d.offset + (d.H - 1) * d.row_stride_bytes + d.W * d.C > pixels_dev.numel():
             raise ValueError(f"guide {i}: a {d.H}x{d.W}x{d.C} image at offset {d.offset} does not describe {H}x{W} pixels inside pixels_dev")
-    outs, total = output_layout(sizes, mode)
-    code = RESIZE_MODES[mode] | (RESIZE_RENORM if renormalize else 0)
-    out = torch.empty(max(total, 16), dtype=torch.uint8, device=y.device)
-    lut_ptr = ws_ptr = ws_n = 0
-    if mode == "depth_rgba":
-        key = str(y.device)
-        lut = _lut_cache.get(key)
-        if lut is None:
-            lut = _lut_cache[key] = torch.from_numpy(viridis_lut()).to(y.device)
-        ws = workspace("dptx_postprocess_guided_workspace_bytes", y.device, (min(B, 4096), code), "unsupported mode")
-        lut_ptr, ws_ptr, ws_n = lut.data_ptr(), ws.data_ptr(), ws.numel()
     with torch.cuda.device(y.device):
         stream = torch.cuda.current_stream().cuda_stream
-        for b0 in range(0, B, 4096):
-            n = min(4096, B - b0)
+        for b0, n in chunks(B):
             call("dptx_postprocess_guided_batch", y[b0:].data_ptr(), guide_lo[b0:].data_ptr(), n, y.shape[1], h, w,
-                 pixels_dev.data_ptr(), _C.addressof(descs) + b0 * _C.sizeof(ImageDesc), _C.addressof(outs) + b0 * _C.sizeof(ImageDesc),
-                 _C.addressof(params), code, out.data_ptr(), lut_ptr, ws_ptr, ws_n, stream)
+                 pixels_dev.data_ptr(), at(descs, b0), at(outs, b0), _C.addressof(params), code, out.data_ptr(), *tail, stream)
     return _output_views(out, outs, sizes, mode)
 
 
@@ -568,7 +542,7 @@ def views_to_input_gpu(pixels_dev: torch.Tensor, descs, flips, net_hw, task: str
     -- bit-identical to Pillow.  pixels_dev: the packed uint8 pixels on the device (pack_images, uploaded once); descs: ImageDesc
     of whole images or of windows of them (window_desc); flips: one truth value per descriptor, or None.  One entry-point call
     per 4096 views (dptx_preprocess_u8_views_batch)."""
-    from ._native import call, check_cuda, workspace
+    from ._native import MAX_DESCS, at, call, check_cuda, chunks, workspace
     check_cuda("pixels_dev", pixels_dev)
     descs = list(descs)
     B, (OH, OW) = len(descs), (int(net_hw[0]), int(net_hw[1]))
@@ -579,15 +553,13 @@ def views_to_input_gpu(pixels_dev: torch.Tensor, descs, flips, net_hw, task: str
         raise ValueError(f"{B} views but {len(flips)} flips")
     arr = (ImageDesc * B)(*descs)
     fl = (_C.c_uint8 * B)(*[1 if f else 0 for f in flips]) if flips is not None else None
-    ws = workspace("dptx_preprocess_rect_batch_workspace_bytes", pixels_dev.device, (min(B, 4096), OH, OW),
+    ws = workspace("dptx_preprocess_rect_batch_workspace_bytes", pixels_dev.device, (min(B, MAX_DESCS), OH, OW),
                    f"network size {(OH, OW)}: both sides must be multiples of 32 in [64, 1024]")
     with torch.cuda.device(pixels_dev.device):
         stream = torch.cuda.current_stream().cuda_stream
-        for b0 in range(0, B, 4096):
-            n = min(4096, B - b0)
-            call("dptx_preprocess_u8_views_batch", pixels_dev.data_ptr(), _C.addressof(arr) + b0 * _C.sizeof(ImageDesc),
-                 _C.addressof(fl) + b0 if fl is not None else None, n, OH, OW, int(task == "depth"), x[b0:].data_ptr(),
-                 ws.data_ptr(), ws.numel(), stream)
+        for b0, n in chunks(B):
+            call("dptx_preprocess_u8_views_batch", pixels_dev.data_ptr(), at(arr, b0), at(fl, b0) if fl is not None else None, n, OH, OW,
+                 int(task == "depth"), x[b0:].data_ptr(), ws.data_ptr(), ws.numel(), stream)
     return x
 
 
@@ -600,49 +572,56 @@ def merge_normal_views_gpu(maps: torch.Tensor, views, sizes, merger: str = "medi
     (F.interpolate bilinear; a flipped view un-mirrored with x negated), merged per channel by np.median ("median") or the mean
     in view order ("mean"), normalised again and encoded.  -> list of device tensors (views of one packed buffer): [H,W,3] uint8
     (output "u8") or [3,H,W] fp32 ("f32"); a pixel no view covers is the zero vector (0.5 / 127)."""
-    from ._native import call, check_cuda
-    check_cuda("maps", maps)
-    if maps.dtype != torch.float32 or not maps.is_contiguous():
-        raise ValueError("maps must be a contiguous fp32 tensor")
-    if merger not in ("median", "mean"):
-        raise ValueError('merger must be "median" or "mean"')
-    if output not in ("u8", "f32"):
-        raise ValueError('output must be "u8" or "f32"')
+    from ._native import call
+    _check_maps(maps)
+    _one_of("merger", merger, ("median", "mean"))
+    _one_of("output", output, ("u8", "f32"))
     views = list(views)
-    sizes = [(int(H), int(W)) for H, W in sizes]
+    sizes = _int_sizes(sizes)
     if not sizes:
         return []
     mode = "normal_u8" if output == "u8" else "normal_f32"
-    for v in views:
-        if v.offset < 0 or v.offset + 12 * v.h * v.w > maps.numel() * 4:
-            raise ValueError("a view lies outside maps")
-    descs, total = output_layout(sizes, mode)
+    _check_maps(maps, views, lambda v: [(v.offset, 12 * v.h * v.w, "a view lies outside maps")])
+    descs, out = _packed_outputs(sizes, mode, maps.device)
     code = RESIZE_MODES[mode] | (TTA_MEAN if merger == "mean" else 0) | (0 if normalize_views else TTA_RAW_VIEWS)
-    out = torch.empty(max(total, 16), dtype=torch.uint8, device=maps.device)
     arr = (TtaView * max(len(views), 1))(*views)
     with torch.cuda.device(maps.device):
         call("dptx_tta_merge_normals", maps.data_ptr(), _C.addressof(arr), len(views), _C.addressof(descs), len(sizes), code,
              out.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    res = []
-    for d, (H, W) in zip(descs, sizes):
-        if output == "u8":
-            res.append(out[d.offset:d.offset + H * W * 3].view(H, W, 3))
-        else:
-            res.append(out[d.offset:d.offset + 12 * H * W].view(torch.float32).view(3, H, W))
-    return res
+    return _output_views(out, descs, sizes, mode)
 
 
-def _check_depth_views(maps, views, sizes):
+def _check_maps(maps, items=(), spans=None):
+    """maps must be a contiguous fp32 CUDA tensor, and every (offset, bytes, message) that spans(item) lists must lie inside it:
+    ValueError(message) otherwise.  -> the items as a list."""
     from ._native import check_cuda
     check_cuda("maps", maps)
     if maps.dtype != torch.float32 or not maps.is_contiguous():
         raise ValueError("maps must be a contiguous fp32 tensor")
-    views = list(views)
-    sizes = [(int(H), int(W)) for H, W in sizes]
-    for v in views:
-        if v.offset < 0 or v.offset + 4 * v.h * v.w > maps.numel() * 4:
-            raise ValueError("a view lies outside maps")
-    return views, sizes
+    items = list(items)
+    for item in items:
+        for offset, nbytes, message in spans(item):
+            if offset < 0 or offset + nbytes > maps.numel() * 4:
+                raise ValueError(message)
+    return items
+
+
+def _check_depth_views(maps, views, sizes):
+    return _check_maps(maps, views, lambda v: [(v.offset, 4 * v.h * v.w, "a view lies outside maps")]), _int_sizes(sizes)
+
+
+def _check_coeffs(coeffs, rows: int, message: str) -> None:
+    from ._native import check_cuda
+    if coeffs is not None:
+        check_cuda("coeffs", coeffs)
+        if coeffs.dtype != torch.float32 or not coeffs.is_contiguous() or tuple(coeffs.shape) != (rows, 2):
+            raise ValueError(message)
+
+
+def _depth_views(out: torch.Tensor, descs, sizes, output: str):
+    """The depth writers' outputs: the fp32 maps inside the packed buffer, or with output "rgba" depths_to_rgba_gpu of each."""
+    res = _output_views(out, descs, sizes, "depth_f32")
+    return [depths_to_rgba_gpu(m[None])[0] for m in res] if output == "rgba" else res
 
 
 def align_depth_views_gpu(maps: torch.Tensor, views, anchors, sizes):
@@ -681,29 +660,19 @@ def merge_depth_views_gpu(maps: torch.Tensor, views, sizes, coeffs=None, ws=None
     its own range, as the full-frame depth path writes)."""
     from ._native import call
     views, sizes = _check_depth_views(maps, views, sizes)
-    if merger not in ("median", "mean"):
-        raise ValueError('merger must be "median" or "mean"')
-    if output not in ("f32", "rgba"):
-        raise ValueError('output must be "f32" or "rgba"')
+    _one_of("merger", merger, ("median", "mean"))
+    _one_of("output", output, ("f32", "rgba"))
     if not sizes:
         return []
-    if coeffs is not None:
-        from ._native import check_cuda
-        check_cuda("coeffs", coeffs)
-        if coeffs.dtype != torch.float32 or not coeffs.is_contiguous() or tuple(coeffs.shape) != (len(views), 2):
-            raise ValueError("coeffs must be a contiguous fp32 tensor [n_views, 2]")
-    descs, total = output_layout(sizes, "depth_f32")
+    _check_coeffs(coeffs, len(views), "coeffs must be a contiguous fp32 tensor [n_views, 2]")
+    descs, out = _packed_outputs(sizes, "depth_f32", maps.device)
     code = RESIZE_MODES["depth_f32"] | (TTA_MEAN if merger == "mean" else 0)
-    out = torch.empty(max(total, 16), dtype=torch.uint8, device=maps.device)
     arr = (TtaView * max(len(views), 1))(*views)
     with torch.cuda.device(maps.device):
         call("dptx_tta_merge_depth", maps.data_ptr(), _C.addressof(arr), len(views), coeffs.data_ptr() if coeffs is not None else None,
              _C.addressof(descs), len(sizes), code, out.data_ptr(), ws.data_ptr() if ws is not None else None,
              torch.cuda.current_stream().cuda_stream)
-    res = [out[d.offset:d.offset + 4 * H * W].view(torch.float32).view(H, W) for d, (H, W) in zip(descs, sizes)]
-    if output == "rgba":
-        res = [depths_to_rgba_gpu(m[None])[0] for m in res]
-    return res
+    return _depth_views(out, descs, sizes, output)
 
 
 # ------------------------------------------------------------------ tiled inference (tiles.hip; omnidata_amd/tiled.py states the protocol)
@@ -734,20 +703,15 @@ class TileGrid(_C.Structure):
 
 
 def _check_tile_maps(maps, grids, sizes, channels, anchors=False):
-    from ._native import check_cuda
-    check_cuda("maps", maps)
-    if maps.dtype != torch.float32 or not maps.is_contiguous():
-        raise ValueError("maps must be a contiguous fp32 tensor")
-    grids = list(grids)
-    sizes = [(int(H), int(W)) for H, W in sizes]
+    def spans(g):
+        return [(g.offset, 4 * channels * g.h * g.w * g.tiles, "a grid's tiles lie outside maps")] + \
+            ([(g.anchor_offset, 4 * g.ah * g.aw, "a grid's anchor lies outside maps")] if anchors else [])
+
+    _check_maps(maps)
+    grids, sizes = list(grids), _int_sizes(sizes)
     if len(grids) != len(sizes):
         raise ValueError(f"{len(sizes)} images but {len(grids)} grids")
-    for g in grids:
-        if g.offset < 0 or g.offset + 4 * channels * g.h * g.w * g.ny * g.nx > maps.numel() * 4:
-            raise ValueError("a grid's tiles lie outside maps")
-        if anchors and (g.anchor_offset < 0 or g.anchor_offset + 4 * g.ah * g.aw > maps.numel() * 4):
-            raise ValueError("a grid's anchor lies outside maps")
-    return grids, sizes
+    return _check_maps(maps, grids, spans), sizes
 
 
 def blend_normal_tiles_gpu(maps: torch.Tensor, grids, sizes, normalize_views: bool = True, output: str = "u8"):
@@ -758,25 +722,17 @@ def blend_normal_tiles_gpu(maps: torch.Tensor, grids, sizes, normalize_views: bo
     -> list of device tensors (views of one packed buffer): [H,W,3] uint8 (output "u8") or [3,H,W] fp32 ("f32")."""
     from ._native import call
     grids, sizes = _check_tile_maps(maps, grids, sizes, 3)
-    if output not in ("u8", "f32"):
-        raise ValueError('output must be "u8" or "f32"')
+    _one_of("output", output, ("u8", "f32"))
     if not sizes:
         return []
     mode = "normal_u8" if output == "u8" else "normal_f32"
-    descs, total = output_layout(sizes, mode)
+    descs, out = _packed_outputs(sizes, mode, maps.device)
     code = RESIZE_MODES[mode] | (0 if normalize_views else TTA_RAW_VIEWS)
-    out = torch.empty(max(total, 16), dtype=torch.uint8, device=maps.device)
     arr = (TileGrid * len(grids))(*grids)
     with torch.cuda.device(maps.device):
         call("dptx_tile_blend_normals", maps.data_ptr(), _C.addressof(arr), _C.addressof(descs), len(sizes), code, out.data_ptr(),
              torch.cuda.current_stream().cuda_stream)
-    res = []
-    for d, (H, W) in zip(descs, sizes):
-        if output == "u8":
-            res.append(out[d.offset:d.offset + H * W * 3].view(H, W, 3))
-        else:
-            res.append(out[d.offset:d.offset + 12 * H * W].view(torch.float32).view(3, H, W))
-    return res
+    return _output_views(out, descs, sizes, mode)
 
 
 def align_depth_tiles_gpu(maps: torch.Tensor, grids, sizes):
@@ -806,23 +762,15 @@ def blend_depth_tiles_gpu(maps: torch.Tensor, grids, sizes, coeffs=None, output:
     unaligned, for comparison) and weighted with the feathered ramp; sum / weight sum, clamp(0, 1), 1 - x.  The anchors are not
     blended.  -> list of device tensors: [H,W] fp32 (output "f32", views of one packed buffer) or [H,W,4] uint8 ("rgba": viridis
     over the map's own range, as the full-frame depth path writes)."""
-    from ._native import call, check_cuda
+    from ._native import call
     grids, sizes = _check_tile_maps(maps, grids, sizes, 1)
-    if output not in ("f32", "rgba"):
-        raise ValueError('output must be "f32" or "rgba"')
+    _one_of("output", output, ("f32", "rgba"))
     if not sizes:
         return []
-    if coeffs is not None:
-        check_cuda("coeffs", coeffs)
-        if coeffs.dtype != torch.float32 or not coeffs.is_contiguous() or tuple(coeffs.shape) != (sum(g.tiles for g in grids), 2):
-            raise ValueError("coeffs must be a contiguous fp32 tensor [tiles, 2]")
-    descs, total = output_layout(sizes, "depth_f32")
-    out = torch.empty(max(total, 16), dtype=torch.uint8, device=maps.device)
+    _check_coeffs(coeffs, sum(g.tiles for g in grids), "coeffs must be a contiguous fp32 tensor [tiles, 2]")
+    descs, out = _packed_outputs(sizes, "depth_f32", maps.device)
     arr = (TileGrid * len(grids))(*grids)
     with torch.cuda.device(maps.device):
         call("dptx_tile_blend_depth", maps.data_ptr(), _C.addressof(arr), coeffs.data_ptr() if coeffs is not None else None,
              _C.addressof(descs), len(sizes), RESIZE_MODES["depth_f32"], out.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    res = [out[d.offset:d.offset + 4 * H * W].view(torch.float32).view(H, W) for d, (H, W) in zip(descs, sizes)]
-    if output == "rgba":
-        res = [depths_to_rgba_gpu(m[None])[0] for m in res]
-    return res
+    return _depth_views(out, descs, sizes, output)

@@ -35,7 +35,7 @@ from collections import namedtuple
 import torch
 
 from . import preprocess as pp
-from .tta import _as_image, _forward_views
+from .tta import _as_image, _Chunked, _forward_views, _require_depth_model
 
 TilePlan = namedtuple("TilePlan", "net window ramps ys xs anchor_net")
 TilePlan.__doc__ = """net (h, w): every tile's network size; window (ch, cw); ramps (ramp_y, ramp_x); ys / xs: the starts per axis;
@@ -78,18 +78,13 @@ def _tile_views(plan: TilePlan, tile: int):
     return [((x0, y0, x0 + cw, y0 + ch), False, tile, plan.net) for y0 in plan.ys for x0 in plan.xs]
 
 
-class _Tiled:
-    channels, task = 3, "normal"
+class _Tiled(_Chunked):
+    channels, task, kernels = 3, "normal", "the forward and the blend"
 
     def __init__(self, model, tile, scale, overlap, batch_size, multiple, max_side, chunk_images):
-        if batch_size < 1 or chunk_images < 1:
-            raise ValueError("batch_size and chunk_images must be >= 1")
-        plan_tiles(64, 64, tile, scale, overlap, multiple, max_side)   # a bad tile, scale or overlap raises here
-        self.model, self.tile, self.scale, self.overlap = model, int(tile), float(scale), float(overlap)
-        self.batch_size, self.multiple, self.max_side, self.chunk_images = int(batch_size), int(multiple), int(max_side), int(chunk_images)
-        self.device = next(model.parameters()).device
-        if self.device.type != "cuda":
-            raise RuntimeError(f"{type(self).__name__} needs the model on an AMD GPU: the forward and the blend are HIP kernels only")
+        super().__init__(model, batch_size, multiple, max_side, chunk_images,   # a bad tile, scale or overlap raises here
+                         lambda: plan_tiles(64, 64, tile, scale, overlap, multiple, max_side))
+        self.tile, self.scale, self.overlap = int(tile), float(scale), float(overlap)
 
     def _forward(self, images, with_anchor: bool):
         """-> (maps, [TileGrid] per image, [(H, W)]): every tile (and with_anchor the whole image first) through the network."""
@@ -121,7 +116,9 @@ class _Tiled:
 
 class TiledNormals(_Tiled):
     """model: a surface-normal network on the GPU, x [B,3,h,w] in [0, 1] -> [B,3,h,w] (encoded normals), for any h, w that are
-    multiples of `multiple` up to `max_side` and B <= batch_size.  The version-1 UNet takes multiple=64, max_side=512."""
+    multiples of `multiple` up to `max_side` and B <= batch_size.  The version-1 UNet takes multiple=64, max_side=512.
+    Called with images: [H,W,3] uint8 per image, or [3,H,W] fp32 with output="f32"; chunk_images images share one upload and one
+    blend call."""
 
     def __init__(self, model, tile: int = 384, scale: float = 1.0, overlap: float = 0.25, normalize_views: bool = True,
                  batch_size: int = 32, multiple: int = 32, max_side: int = 1024, chunk_images: int = 1):
@@ -134,31 +131,19 @@ class TiledNormals(_Tiled):
             maps, grids, sizes = self._forward(images, False)
             return pp.blend_normal_tiles_gpu(maps, grids, sizes, self.normalize_views, output)
 
-    def __call__(self, images, output: str = "u8"):
-        """images: PIL images or uint8 HW[C] arrays -> list of device tensors at each image's own size: [H,W,3] uint8, or
-        [3,H,W] fp32 with output="f32".  chunk_images images share one upload and one blend call."""
-        if output not in ("u8", "f32"):
-            raise ValueError('output must be "u8" or "f32"')
-        images = list(images)
-        res = []
-        for c0 in range(0, len(images), self.chunk_images):
-            res += self._chunk(images[c0:c0 + self.chunk_images], output)
-        return res
-
 
 class TiledDepth(_Tiled):
     """model: a DPT depth network (hybrid or large) on the GPU, x [B,3,h,w] in [-1, 1] -> [B,h,w].  align: "lstsq" fits every tile
     to the image's whole-image anchor before the blend (the module's definitions); None blends the tiles as they are, for
-    comparison (no anchor is run then)."""
-    channels, task = 1, "depth"
+    comparison (no anchor is run then).
+    Called with images: [H,W,4] uint8 per image (viridis over the map's own range), or [H,W] fp32 (1 - depth) with output="f32";
+    the coefficients of return_coeffs are per tile, in grid order."""
+    channels, task, outputs, aligned = 1, "depth", ("rgba", "f32"), True
 
     def __init__(self, model, tile: int = 384, scale: float = 1.0, overlap: float = 0.25, align="lstsq", batch_size: int = 32,
                  multiple: int = 32, max_side: int = 1024, chunk_images: int = 1):
-        if align not in ("lstsq", None):
-            raise ValueError('align must be "lstsq" or None')
-        from .model import DPTDepthModel
-        if not isinstance(model, DPTDepthModel) or model.num_channels != 1:
-            raise ValueError("TiledDepth takes a DPT depth model (build_model('depth', ...), hybrid or large)")
+        pp._one_of("align", align, ("lstsq", None))
+        _require_depth_model(model, "TiledDepth")
         super().__init__(model, tile, scale, overlap, batch_size, multiple, max_side, chunk_images)
         self.align = align
 
@@ -173,17 +158,3 @@ class TiledDepth(_Tiled):
         if coeffs is None:
             return res, [None] * len(images)
         return res, list(coeffs.split([g.tiles for g in grids]))
-
-    def __call__(self, images, output: str = "rgba", return_coeffs: bool = False):
-        """images: PIL images or uint8 HW[C] arrays -> list of device tensors at each image's own size: [H,W,4] uint8 (viridis
-        over the map's own range), or [H,W] fp32 (1 - depth) with output="f32".  return_coeffs=True: -> (that list, per image the
-        [tiles, 2] fp32 (scale, shift) of its tiles in grid order; None per image with align=None)."""
-        if output not in ("rgba", "f32"):
-            raise ValueError('output must be "rgba" or "f32"')
-        images = list(images)
-        res, coeffs = [], []
-        for c0 in range(0, len(images), self.chunk_images):
-            r, c = self._chunk(images[c0:c0 + self.chunk_images], output, return_coeffs)
-            res += r
-            coeffs += c or []
-        return (res, coeffs) if return_coeffs else res

@@ -140,22 +140,61 @@ def _forward_views(model, images, plans, batch_size: int, device, channels: int,
     return maps, views, [(d.H, d.W) for d in descs[:len(images)]]
 
 
-class NormalsTTA:
-    """model: a surface-normal network on the GPU, x [B,3,h,w] in [0, 1] -> [B,3,h,w] (encoded normals), for any h, w that are
-    multiples of `multiple` up to `max_side` and B <= batch_size.  The version-1 UNet takes multiple=64, max_side=512."""
+def _require_depth_model(model, who: str) -> None:
+    from .model import DPTDepthModel
+    if not isinstance(model, DPTDepthModel) or model.num_channels != 1:
+        raise ValueError(f"{who} takes a DPT depth model (build_model('depth', ...), hybrid or large)")
 
-    def __init__(self, model, preset="oasis", merger: str = "median", normalize_views: bool = True, batch_size: int = 32,
-                 multiple: int = 32, max_side: int = 1024, chunk_images: int = 8):
-        if merger not in ("median", "mean"):
-            raise ValueError('merger must be "median" or "mean"')
+
+class _Chunked:
+    """What NormalsTTA, DepthTTA and the classes of tiled.py share: the constructor's checks, and the call.
+
+    obj(images, output=None, return_coeffs=False): images: PIL images or uint8 HW[C] arrays -> list of device tensors at each
+    image's own size, in the form `output` names (None: the first of the class's `outputs`).  chunk_images images share one upload
+    and one _chunk() call.  return_coeffs=True (the depth classes): -> (that list, per image the [n, 2] fp32 (scale, shift) of its
+    views or tiles; None per image with align=None)."""
+    outputs = ("u8", "f32")
+    aligned = False                              # whether _chunk takes return_coeffs and returns (maps, coefficients)
+    kernels = "the forward and the merge"
+
+    def __init__(self, model, batch_size, multiple, max_side, chunk_images, check_plan):
         if batch_size < 1 or chunk_images < 1:
             raise ValueError("batch_size and chunk_images must be >= 1")
-        plan_views(64, 64, preset, multiple, max_side)   # an unknown preset raises here
-        self.model, self.preset, self.merger, self.normalize_views = model, preset, merger, bool(normalize_views)
+        check_plan()                             # the subclass's other rules: all decided before the model is touched
+        self.model = model
         self.batch_size, self.multiple, self.max_side, self.chunk_images = int(batch_size), int(multiple), int(max_side), int(chunk_images)
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
-            raise RuntimeError("NormalsTTA needs the model on an AMD GPU: the forward and the merge are HIP kernels only")
+            raise RuntimeError(f"{type(self).__name__} needs the model on an AMD GPU: {self.kernels} are HIP kernels only")
+
+    def __call__(self, images, output=None, return_coeffs: bool = False):
+        output = self.outputs[0] if output is None else output
+        pp._one_of("output", output, self.outputs)
+        if return_coeffs and not self.aligned:
+            raise TypeError(f"{type(self).__name__} has no coefficients to return")
+        images = list(images)
+        res, coeffs = [], []
+        for c0 in range(0, len(images), self.chunk_images):
+            r = self._chunk(images[c0:c0 + self.chunk_images], output, *((return_coeffs,) if self.aligned else ()))
+            if self.aligned:
+                r, c = r
+                coeffs += c or []
+            res += r
+        return (res, coeffs) if return_coeffs else res
+
+
+class NormalsTTA(_Chunked):
+    """model: a surface-normal network on the GPU, x [B,3,h,w] in [0, 1] -> [B,3,h,w] (encoded normals), for any h, w that are
+    multiples of `multiple` up to `max_side` and B <= batch_size.  The version-1 UNet takes multiple=64, max_side=512.
+    Called with images: [H,W,3] uint8 per image, or [3,H,W] fp32 with output="f32"; chunk_images images share one upload and one
+    merge call."""
+
+    def __init__(self, model, preset="oasis", merger: str = "median", normalize_views: bool = True, batch_size: int = 32,
+                 multiple: int = 32, max_side: int = 1024, chunk_images: int = 8):
+        pp._one_of("merger", merger, ("median", "mean"))
+        super().__init__(model, batch_size, multiple, max_side, chunk_images,
+                         lambda: plan_views(64, 64, preset, multiple, max_side))   # an unknown preset raises here
+        self.preset, self.merger, self.normalize_views = preset, merger, bool(normalize_views)
 
     def _chunk(self, images, output):
         images = [_as_image(im) for im in images]
@@ -164,40 +203,26 @@ class NormalsTTA:
             maps, views, sizes = _forward_views(self.model, images, plans, self.batch_size, self.device, 3, "normal")
             return pp.merge_normal_views_gpu(maps, views, sizes, self.merger, self.normalize_views, output)
 
-    def __call__(self, images, output: str = "u8"):
-        """images: PIL images or uint8 HW[C] arrays -> list of device tensors at each image's own size: [H,W,3] uint8, or
-        [3,H,W] fp32 with output="f32".  chunk_images images share one upload and one merge call."""
-        if output not in ("u8", "f32"):
-            raise ValueError('output must be "u8" or "f32"')
-        images = list(images)
-        res = []
-        for c0 in range(0, len(images), self.chunk_images):
-            res += self._chunk(images[c0:c0 + self.chunk_images], output)
-        return res
 
-
-class DepthTTA:
+class DepthTTA(_Chunked):
     """model: a DPT depth network (hybrid or large) on the GPU, x [B,3,h,w] in [-1, 1] -> [B,h,w], for any h, w that are
     multiples of `multiple` up to `max_side` and B <= batch_size.  align: "lstsq" fits every view to the image's anchor view
-    before the merge (the module's definitions); None merges the views as they are, for comparison."""
+    before the merge (the module's definitions); None merges the views as they are, for comparison.
+    Called with images: [H,W,4] uint8 per image (viridis over the map's own range), or [H,W] fp32 (1 - depth, as
+    resize_outputs_gpu(..., "depth_f32")) with output="f32"; the coefficients of return_coeffs are in plan_depth_views' order.
+    chunk_images images share one upload, one alignment and one merge call."""
+    outputs, aligned, kernels = ("rgba", "f32"), True, "the forward, the alignment and the merge"
 
     def __init__(self, model, preset="whole", merger: str = "median", align="lstsq", batch_size: int = 32, multiple: int = 32,
                  max_side: int = 1024, chunk_images: int = 8):
-        if merger not in ("median", "mean"):
-            raise ValueError('merger must be "median" or "mean"')
-        if align not in ("lstsq", None):
-            raise ValueError('align must be "lstsq" or None')
-        if batch_size < 1 or chunk_images < 1:
-            raise ValueError("batch_size and chunk_images must be >= 1")
-        from .model import DPTDepthModel
-        if not isinstance(model, DPTDepthModel) or model.num_channels != 1:
-            raise ValueError("DepthTTA takes a DPT depth model (build_model('depth', ...), hybrid or large)")
-        plan_depth_views(64, 64, preset, multiple, max_side)   # an unknown preset raises here
-        self.model, self.preset, self.merger, self.align = model, preset, merger, align
-        self.batch_size, self.multiple, self.max_side, self.chunk_images = int(batch_size), int(multiple), int(max_side), int(chunk_images)
-        self.device = next(model.parameters()).device
-        if self.device.type != "cuda":
-            raise RuntimeError("DepthTTA needs the model on an AMD GPU: the forward, the alignment and the merge are HIP kernels only")
+        def check_plan():
+            _require_depth_model(model, "DepthTTA")
+            plan_depth_views(64, 64, preset, multiple, max_side)   # an unknown preset raises here
+
+        pp._one_of("merger", merger, ("median", "mean"))
+        pp._one_of("align", align, ("lstsq", None))
+        super().__init__(model, batch_size, multiple, max_side, chunk_images, check_plan)
+        self.preset, self.merger, self.align = preset, merger, align
 
     def _chunk(self, images, output, return_coeffs):
         images = [_as_image(im) for im in images]
@@ -223,18 +248,3 @@ class DepthTTA:
             return res, [None] * len(images)
         counts = [sum(1 for v in views if v.image == i) for i in range(len(images))]
         return res, list(coeffs.split(counts))
-
-    def __call__(self, images, output: str = "rgba", return_coeffs: bool = False):
-        """images: PIL images or uint8 HW[C] arrays -> list of device tensors at each image's own size: [H,W,4] uint8 (viridis
-        over the map's own range), or [H,W] fp32 (1 - depth, as resize_outputs_gpu(..., "depth_f32")) with output="f32".
-        return_coeffs=True: -> (that list, per image the [views, 2] fp32 (scale, shift) of its views in plan_depth_views'
-        order; None per image with align=None).  chunk_images images share one upload, one alignment and one merge call."""
-        if output not in ("rgba", "f32"):
-            raise ValueError('output must be "rgba" or "f32"')
-        images = list(images)
-        res, coeffs = [], []
-        for c0 in range(0, len(images), self.chunk_images):
-            r, c = self._chunk(images[c0:c0 + self.chunk_images], output, return_coeffs)
-            res += r
-            coeffs += c or []
-        return (res, coeffs) if return_coeffs else res

@@ -369,6 +369,20 @@ def test_files_have_the_inputs_sizes_and_the_pixels_of_the_pieces_called_by_hand
         assert rgb.size == (w, h) and np.array_equal(np.asarray(rgb), np.asarray(img)), stem
 
 
+def test_an_unreadable_file_raises_before_anything_has_run_or_is_written(tmp_path):
+    """What BatchPredictor._chunks promises for the full-frame paths: the sizes are read from the headers first."""
+    from PIL import UnidentifiedImageError
+    from omnidata_amd.batch_infer import BatchPredictor
+    files = _folder(tmp_path / "in", E2E[:2])
+    bad = tmp_path / "in" / "notes.txt"
+    bad.write_text("not an image\n")
+    out = tmp_path / "out"
+    bp = BatchPredictor(_model("normal"), "normal", batch_size=2, image_size=64, full_frame="squash")
+    with pytest.raises(UnidentifiedImageError):
+        bp.predict_to_dir([files[0], str(bad), files[1]], str(out))
+    assert os.listdir(out) == []
+
+
 def test_without_full_frame_the_predictor_gives_todays_pixels(tmp_path):
     from omnidata_amd.batch_infer import BatchPredictor
     files = _folder(tmp_path / "in", [("a", (400, 520)), ("b", (390, 384))])

@@ -218,7 +218,7 @@ def test_batch_predictor_routes_through_the_tiles_in_input_order_and_excludes_th
     for other in (dict(tta="flip"), dict(full_frame="aspect"), dict(full_frame="squash")):
         with pytest.raises(ValueError, match="tiled excludes"):
             BatchPredictor(model, "normal", tiled=True, **other)
-    assert BatchPredictor(model, "normal", tiled=None).tta is None
+    assert BatchPredictor(model, "normal", tiled=None)._runner is None
 
 
 def test_demo_cli_tiled_depth_writes_files_of_the_images_own_sizes(tmp_path):
