@@ -1141,6 +1141,23 @@ int dptx_op_unet_conv3x3(int32_t dtype, const void* X, int32_t x_pix_stride, int
                          void* Y, float* gn_part, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* scratch,
                          void* stream);
 int32_t dptx_op_unet_conv_records(int32_t H, int32_t W);
+/* dptx_op_unet_conv3x3 for Cin = 3 on a caller image x [B,3,H,W] NCHW of element type io (DPTX_IO_FP32 / _BF16 / _FP16; anything
+ * else: DPTX_E_INVALID): Wt the padded [Cout][32] block, Y, gn_part and scratch (B*H*W*32 16-bit elements) as above. */
+int dptx_op_unet_conv3x3_io(int32_t dtype, const void* x, int32_t io, const void* Wt, const float* bias, void* Y, float* gn_part,
+                            int32_t B, int32_t H, int32_t W, int32_t Cout, void* scratch, void* stream);
+/* A 3x3 convolution (pad 1, stride 1, bias) of the layers with Cin and Cout >= 64, launched exactly as the forward launches
+ * it (the implicit GEMM; BF16 / FP16 only, a plane dtype is DPTX_E_INVALID, and so is whatever the GEMM launcher refuses:
+ * Cin % 64 != 0, Cout % 32 != 0).  X [B][H][W][x_pix_stride] 16-bit, the layer reads channels x_off .. x_off + Cin of every
+ * pixel (x_pix_stride and x_off multiples of 8; dense: x_pix_stride = Cin, x_off = 0); x_bytes = the size of the WHOLE X
+ * buffer in bytes (>= B*H*W*x_pix_stride*2), beyond which nothing is read; Wt [Cout][3][3][Cin] 16-bit; bias [Cout] fp32
+ * (may be NULL); Y [B][H][W][Cout] 16-bit, dense: exactly B*H*W*Cout elements are written. */
+int dptx_op_unet_conv_gemm(int32_t dtype, const void* X, int32_t x_pix_stride, int32_t x_off, int64_t x_bytes, const void* Wt,
+                           const float* bias, void* Y, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* stream);
+/* last_bn + ReLU + last_conv2 in one pass: X [B][HW][16] 16-bit raw values, stats [B][8][2] fp32 (mean, rstd) per (image,
+ * group of 2 channels) supplied by the caller, gamma / beta [16], w [OC][16] and bias [OC] fp32; y [B][OC][HW] fp32 (NCHW):
+ * exactly B*OC*HW elements are written.  OC 1..4, BF16 / FP16; otherwise DPTX_E_INVALID. */
+int dptx_op_unet_gn_head(int32_t dtype, const void* X, const float* stats, const float* gamma, const float* beta, const float* w,
+                         const float* bias, float* y, int32_t B, int32_t HW, int32_t OC, void* stream);
 /* GroupNorm(8) + ReLU of a dense X [B][H][W][C] (C % 16 == 0, 16..1024): statistics pass, (mean, rstd) in double, apply.
  * Y (may be NULL): full size, into channels y_off .. y_off + C of pixels y_pix_stride apart; P (may be NULL; H, W even): the
  * 2x2 / 2 max-pooled result, likewise.  scratch_f32: B * (dptx_op_unet_gn_records(H*W, C) * 16 + 16) floats. */

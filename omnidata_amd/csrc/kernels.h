@@ -104,6 +104,10 @@ void gemm_params_dense(GemmParams& p, int M, int N, int K, int a_elem_bytes = 2)
 // [M,N]): M, N, K, ldw, the a_* and c_* fields, ldc and the tap order k_tap_fast.  a_elem_bytes: 2, or 1 for e4m3 operands.
 void gemm_params_conv(GemmParams& p, int B, int Hin, int Win, int Cin, int Cout, int ksz, int stride, int pad_t, int pad_l,
                       int Hout, int Wout, int a_elem_bytes);
+// The version-1 UNet's 3x3 convolution (pad 1, stride 1) at one level: gemm_params_conv of [B,H,W,Cin] -> [B,H,W,Cout] whose A
+// operand is a channel slice of a wider NHWC buffer -- channels x_off .. x_off + Cin of pixels x_pix_stride elements apart
+// (x_pix_stride = Cin, x_off = 0: dense); x_bytes = the size of the WHOLE buffer, the bound of the buffer descriptor.
+void gemm_params_unet_conv(GemmParams& p, int B, int H, int W, int Cin, int Cout, int x_pix_stride, int x_off, long long x_bytes);
 // Patch embedding: dense A [B*NP, K] -> rows 1 .. NP of every image's S = NP + 1 token rows of the fp32 stream C [B*S, D] (row 0
 // is the cls row), plus R2 = the fp32 position embedding [S, D], broadcast over the images.  The caller assigns R2 (and C).
 void gemm_params_patch_embed(GemmParams& p, int B, int NP, int S, int D, int K);

@@ -1,6 +1,6 @@
 // launch_forms.hip -- how each launch form of the schedule is parameterised (kernels.h): the geometries of GemmParams and what
-// a launch does beyond the plain product, one definition each.  Host code only; the forward (engine.hip) and the op-level
-// entry points (ops.hip) both launch what these functions fill in.
+// a launch does beyond the plain product, one definition each.  Host code only; the forwards (engine.hip, unet_engine.hip) and
+// the op-level entry points (ops.hip, unet.hip) both launch what these functions fill in.
 #include "kernels.h"
 
 namespace dptx {
@@ -23,6 +23,11 @@ void gemm_params_conv(GemmParams& p, int B, int Hin, int Win, int Cin, int Cout,
   p.c_rpi = 0x7fffffff; p.c_img_rows = 0; p.c_row_off = 0; p.ldc = Cout;
   p.a_bytes = (long long)B * Hin * Win * Cin * a_elem_bytes;
   p.k_tap_fast = (ksz == 3 && Cin >= 512) ? 1 : 0;  // measured per layer: profiles/r01_experiments.md
+}
+
+void gemm_params_unet_conv(GemmParams& p, int B, int H, int W, int Cin, int Cout, int x_pix_stride, int x_off, long long x_bytes) {
+  gemm_params_conv(p, B, H, W, Cin, Cout, 3, 1, 1, 1, H, W, 2);
+  p.a_pix_stride = x_pix_stride; p.a_off = x_off; p.a_img_stride = (long long)H * W * x_pix_stride; p.a_bytes = x_bytes;
 }
 
 void gemm_params_patch_embed(GemmParams& p, int B, int NP, int S, int D, int K) {

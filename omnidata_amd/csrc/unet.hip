@@ -465,19 +465,53 @@ extern "C" {
 
 static int urc(hipError_t r) { return r == hipSuccess ? DPTX_OK : (r == hipErrorInvalidValue ? DPTX_E_INVALID : DPTX_E_HIP); }
 
-int dptx_op_unet_conv3x3(int32_t dtype, const void* X, int32_t x_pix_stride, int32_t x_off, const void* Wt, const float* bias, void* Y,
-                         float* gn_part, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* scratch, void* stream) {
+// Cin == 3: X is the caller's NCHW image [B,3,H,W] of element type io
+static int op_conv3x3(int32_t dtype, const void* X, int32_t io, int32_t x_pix_stride, int32_t x_off, const void* Wt, const float* bias,
+                      void* Y, float* gn_part, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* scratch, void* stream) {
   UnetConvParams p{};
   p.Wt = Wt; p.bias = bias; p.Y = Y; p.gn_part = gn_part; p.B = B; p.H = H; p.W = W; p.Cout = Cout;
-  if (Cin == 3) {  // X: fp32 NCHW [B,3,H,W]; scratch: B*H*W*32 16-bit elements; Wt [Cout][32], k = (ky*3+kx)*3 + c
+  if (Cin == 3) {  // scratch: B*H*W*32 16-bit elements; Wt [Cout][32], k = (ky*3+kx)*3 + c
     if (scratch == nullptr) return DPTX_E_INVALID;
-    const hipError_t r = launch_unet_im2col3(dtype, X, DPTX_IO_FP32, scratch, B, H, W, (hipStream_t)stream);
+    const hipError_t r = launch_unet_im2col3(dtype, X, io, scratch, B, H, W, (hipStream_t)stream);
     if (r != hipSuccess) return urc(r);
     p.X = scratch; p.Cin = 32; p.taps = 1; p.x_pix_stride = 32; p.x_off = 0;
   } else {
     p.X = X; p.Cin = Cin; p.taps = 9; p.x_pix_stride = x_pix_stride; p.x_off = x_off;
   }
   return urc(launch_unet_conv_small(dtype, p, (hipStream_t)stream));
+}
+
+int dptx_op_unet_conv3x3(int32_t dtype, const void* X, int32_t x_pix_stride, int32_t x_off, const void* Wt, const float* bias, void* Y,
+                         float* gn_part, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* scratch, void* stream) {
+  return op_conv3x3(dtype, X, DPTX_IO_FP32, x_pix_stride, x_off, Wt, bias, Y, gn_part, B, H, W, Cin, Cout, scratch, stream);
+}
+
+// the first layer (Cin = 3) on a caller image of element type io: im2col, then the 1-tap product
+int dptx_op_unet_conv3x3_io(int32_t dtype, const void* x, int32_t io, const void* Wt, const float* bias, void* Y, float* gn_part,
+                            int32_t B, int32_t H, int32_t W, int32_t Cout, void* scratch, void* stream) {
+  if (io != DPTX_IO_FP32 && io != DPTX_IO_BF16 && io != DPTX_IO_FP16) return DPTX_E_INVALID;
+  return op_conv3x3(dtype, x, io, 0, 0, Wt, bias, Y, gn_part, B, H, W, 3, Cout, scratch, stream);
+}
+
+// a GEMM-path convolution exactly as Fwd::conv (unet_engine.hip) launches it: gemm_params_unet_conv, plain bias epilogue
+int dptx_op_unet_conv_gemm(int32_t dtype, const void* X, int32_t x_pix_stride, int32_t x_off, int64_t x_bytes, const void* Wt,
+                           const float* bias, void* Y, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, void* stream) {
+  if (dtype != DPTX_DTYPE_BF16 && dtype != DPTX_DTYPE_FP16) return DPTX_E_INVALID;
+  if (X == nullptr || Wt == nullptr || Y == nullptr || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return DPTX_E_INVALID;
+  if (x_pix_stride % 8 != 0 || x_off % 8 != 0 || x_off < 0 || x_off + Cin > x_pix_stride) return DPTX_E_INVALID;
+  if ((long long)B * H * W >= (1ll << 31) || x_bytes < (long long)B * H * W * x_pix_stride * 2) return DPTX_E_INVALID;
+  GemmParams p;
+  gemm_params_unet_conv(p, B, H, W, Cin, Cout, x_pix_stride, x_off, (long long)x_bytes);
+  p.A = X; p.W = Wt; p.C = Y; p.bias = bias;
+  return urc(launch_gemm(dtype, p, (hipStream_t)stream));
+}
+
+// last_bn + ReLU + last_conv2 with the caller's (mean, rstd) table
+int dptx_op_unet_gn_head(int32_t dtype, const void* X, const float* stats, const float* gamma, const float* beta, const float* w,
+                         const float* bias, float* y, int32_t B, int32_t HW, int32_t OC, void* stream) {
+  if (X == nullptr || stats == nullptr || gamma == nullptr || beta == nullptr || w == nullptr || bias == nullptr || y == nullptr)
+    return DPTX_E_INVALID;
+  return urc(launch_unet_gn_head(dtype, X, stats, gamma, beta, w, bias, y, B, HW, OC, (hipStream_t)stream));
 }
 
 int32_t dptx_op_unet_conv_records(int32_t H, int32_t W) { return unet_conv_tiles(H, W); }

@@ -201,9 +201,8 @@ struct Fwd {
       nrec = unet_conv_tiles(Hl, Wl);
     } else {
       GemmParams p;
-      gemm_params_conv(p, B, Hl, Wl, c.cin, c.cout, 3, 1, 1, 1, Hl, Wl, 2);
+      gemm_params_unet_conv(p, B, Hl, Wl, c.cin, c.cout, pix_stride, off, (long long)x_bytes);
       p.A = X; p.W = h->d_blob + c.w_off; p.C = buf(h->o_raw); p.bias = f32(c.b_off);
-      p.a_pix_stride = pix_stride; p.a_off = off; p.a_img_stride = (long long)Hl * Wl * pix_stride; p.a_bytes = (long long)x_bytes;
       if (classes & CLS_GEMM) note(launch_gemm(h->mode, p, st), "gemm conv");
       if (classes & CLS_PASS) note(launch_unet_gn_stats(h->mode, buf(h->o_raw), rec(), B, Hl * Wl, c.cout, st), "gn stats");
       nrec = unet_gn_chunks(Hl * Wl, c.cout);

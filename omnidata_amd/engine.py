@@ -193,6 +193,9 @@ ABI = [
     ("dptx_unet_debug_forward_classes", C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_op_unet_conv3x3", C.c_int, [_i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     ("dptx_op_unet_conv_records", _i32, [_i32, _i32]),
+    ("dptx_op_unet_conv3x3_io", C.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    ("dptx_op_unet_conv_gemm", C.c_int, [_i32, _vp, _i32, _i32, C.c_int64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ("dptx_op_unet_gn_head", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     ("dptx_op_unet_groupnorm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float,
                                          _vp, _vp]),
     ("dptx_op_unet_gn_records", _i32, [_i32, _i32]),

@@ -920,3 +920,83 @@ def guarded_f32(n, guard):
 
 def f32_guards_intact(buf, n, guard):
     return bool(torch.isnan(buf[:guard]).all()) and bool(torch.isnan(buf[guard + n:]).all())
+
+
+# ------------------------------------------------------------------ the UNet's head (last_bn + ReLU + last_conv2), element by element
+# unet_gn_head_kernel (csrc/unet.hip) on a caller-supplied (mean, rstd) table: the operands of one case, the fp64 reference with
+# its derived bound, and the kernel's arithmetic in fp32 on any device (the model tests/test_unet_bound_host.py mutates).
+UNET_HEAD_OC = (1, 3, 4)
+UNET_HEAD_HW = (1, 255, 257, 64 * 64)
+
+
+def unet_head_operands(dtype, B, HW, OC, seed=0):
+    """X [B, HW, 16] of nhwc_with_group_stats (groups = 8: every (image, pair of channels) has statistics of its own) rounded
+    to the 16-bit type; stats [B, 8, 2] = (mean, rstd) of the stored values per (image, group) computed in fp64 (eps 1e-5) and
+    rounded to fp32; gamma in [0.5, 1.5], beta in [-0.3, 0.3], w [OC, 16] ~ N(0, 1) 2^f_o / 4 and bias [OC] ~ N(0, 1) 2^f_o in
+    fp32 (f_o = (5 o mod 7) - 3: every output channel a scale of its own).  CPU tensors."""
+    X = nhwc_with_group_stats(B, HW, 16, groups=8, seed=500 + seed).to(TDT[dtype])
+    xg = X.double().reshape(B, HW, 8, 2).transpose(1, 2).reshape(B, 8, -1)
+    mean, var = xg.mean(-1), xg.var(-1, unbiased=False)
+    stats = torch.stack([mean, 1.0 / torch.sqrt(var + 1e-5)], -1).float().contiguous()
+    g = torch.Generator().manual_seed(600 + seed)
+    gamma = (0.5 + torch.rand(16, generator=g)).float()
+    beta = (0.6 * torch.rand(16, generator=g) - 0.3).float()
+    so = torch.exp2(_col_exp(OC)).float()
+    w = (torch.randn(OC, 16, generator=g) * so[:, None] * 0.25).float().contiguous()
+    bias = (torch.randn(OC, generator=g) * so).float()
+    return X, stats, gamma, beta, w, bias
+
+
+def unet_head_ref64(X, stats, gamma, beta, w, bias):
+    """(y, bound) in fp64, y [B, OC, HW]: y_o = bias_o + sum_j w_oj relu(x_j a_j + c_j) with a_j = rstd gamma_j and
+    c_j = beta_j - mean a_j, of the fp32 table values as given (the kernel reads those, not the statistics of X).
+
+    Bound, u = 2^-24, to first order in u.  The kernel rounds a_j once (a product), c_j once (one fused multiply-add of the
+    ROUNDED a_j: its error is u |mean a_j| from a_j plus u |c_j| of its own), and the pre-activation once (one fused
+    multiply-add: u |x_j a_j| from a_j, the error of c_j, and u |x_j a_j + c_j| <= u (|x_j a_j| + |c_j|) of its own):
+      |f^_j - f_j| <= u T_j,  T_j = 2 |x_j a_j| + 2 |c_j| + |mean a_j|      (ReLU is 1-Lipschitz and changes nothing).
+    The 16-term product is a chain of 16 fused multiply-adds that starts at the bias: every term passes through at most 16
+    roundings, (1 + u)^16 - 1 < 17 u.  So |err| <= u (17 (|bias| + sum_j |w_j| f_j) + sum_j |w_j| T_j).  No measured constant."""
+    u = 2.0 ** -24
+    B, HW, _ = X.shape
+    x = X.double()
+    mean = stats[..., 0].double().repeat_interleave(2, 1).view(B, 1, 16)
+    rstd = stats[..., 1].double().repeat_interleave(2, 1).view(B, 1, 16)
+    a = rstd * gamma.double()
+    c = beta.double() - mean * a
+    f = torch.relu(x * a + c)                                              # [B, HW, 16]
+    T = 2.0 * (x * a).abs() + 2.0 * c.abs() + (mean * a).abs()
+    wd, bd = w.double(), bias.double()
+    y = f @ wd.t() + bd
+    bound = u * (17.0 * (bd.abs() + f @ wd.abs().t()) + T @ wd.abs().t())
+    return y.transpose(1, 2).contiguous(), bound.transpose(1, 2).contiguous()
+
+
+def _fma32(a, b, c):
+    """fl32(a b + c) of fp32 tensors: the product of two fp32 numbers is exact in fp64, the sum is rounded to fp64 and then to
+    fp32 (a double rounding differs from the fused result in about one element in 2^29, by one ulp)"""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def unet_head_model32(X, stats, gamma, beta, w, bias, mutant=None, dtype=None):
+    """The kernel's arithmetic in fp32, in its order -> y [B, OC, HW] fp32.  mutant: 'round16' (the normalised values rounded
+    to the 16-bit type `dtype` before the 1x1), 'beta_shift' (beta of channel j + 1 used for channel j), 'late_relu' (the
+    ReLU behind the 1x1 instead of in front of it)."""
+    B, HW, _ = X.shape
+    x = X.float()
+    mean = stats[..., 0].repeat_interleave(2, 1).view(B, 1, 16)
+    rstd = stats[..., 1].repeat_interleave(2, 1).view(B, 1, 16)
+    a = rstd * gamma.float()
+    be = beta.float().roll(-1) if mutant == "beta_shift" else beta.float()
+    c = _fma32(-mean, a, be.view(1, 1, 16).expand(B, 1, 16))
+    f = _fma32(x, a.expand(B, HW, 16), c.expand(B, HW, 16))
+    if mutant != "late_relu":
+        f = torch.relu(f)
+    if mutant == "round16":
+        f = f.to(TDT[dtype]).float()
+    s = bias.float().view(1, 1, -1).expand(B, HW, -1)
+    for j in range(16):
+        s = _fma32(f[..., j:j + 1], w.float()[:, j].view(1, 1, -1), s)
+    if mutant == "late_relu":
+        s = torch.relu(s)
+    return s.transpose(1, 2).contiguous()

@@ -86,6 +86,8 @@ def test_invariances_bitwise(engine0):
     # 16-bit inputs are read directly: the same values give the same bits
     xh = x.half()
     assert torch.equal(e.forward(xh), e.forward(xh.float()))
+    xb = x.bfloat16()
+    assert torch.equal(e.forward(xb), e.forward(xb.float()))
 
 
 def test_forward_rejects_bad_sizes(engine0):
