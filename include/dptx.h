@@ -1000,6 +1000,14 @@ int dptx_op_conv_groupnorm_fused(int32_t dtype, const void* X, const void* Wt, c
                                  const void* R, const float* r_gamma, const float* r_beta, const float* r_records, void* Y,
                                  int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t relu, float eps,
                                  void* records_f32, void* tables_f32, int32_t passes, void* stream);
+/* The apply pass of dptx_op_conv_groupnorm alone, from caller-supplied records -- the launch the forward's gn_apply makes
+ * behind a convolution that wrote GroupNorm records: Y = act( gn(X) + R' ) of the stored 16-bit map X [B][HW][C] with the
+ * statistics of records[B][HW/32][32][2] ((sum, sum of squares) per 32-row block and group, as the convolution's epilogue
+ * leaves them), R' = nothing (R null), R, or gn_r(R) with (r_gamma, r_beta) and the records r_records of R.  Y == X allowed.
+ * HW % 32 == 0, C % 64 == 0, C <= 1024; r_gamma, r_beta and r_records come together and need R. */
+int dptx_op_groupnorm_records(int32_t dtype, const void* X, const float* gamma, const float* beta, const float* records,
+                              const void* R, const float* r_gamma, const float* r_beta, const float* r_records, void* Y,
+                              int32_t B, int32_t HW, int32_t C, int32_t relu, float eps, void* stream);
 /* bilinear x2, align_corners=True, NHWC 16-bit. */
 int dptx_op_upsample2x(int32_t dtype, const void* X, void* Y, int32_t B, int32_t H, int32_t W,
                        int32_t C, void* stream);

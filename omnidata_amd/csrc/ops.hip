@@ -204,6 +204,22 @@ int dptx_op_conv_groupnorm_fused(int32_t dtype, const void* X, const void* Wt, c
   return DPTX_OK;
 }
 
+// the apply pass alone, from caller-supplied records: what the forward's gn_apply launches behind a convolution that wrote
+// GroupNorm records (gn_params with from_gemm_records, gn_add_residual, launch_gn_apply)
+int dptx_op_groupnorm_records(int32_t dtype, const void* X, const float* gamma, const float* beta, const float* records,
+                              const void* R, const float* r_gamma, const float* r_beta, const float* r_records, void* Y, int32_t B,
+                              int32_t HW, int32_t C, int32_t relu, float eps, void* stream) {
+  if (dtype != DPTX_DTYPE_BF16 && dtype != DPTX_DTYPE_FP16 && dtype != DPTX_DTYPE_BF16X3 && dtype != DPTX_DTYPE_FP16X3)
+    return DPTX_E_INVALID;
+  if (X == nullptr || Y == nullptr || gamma == nullptr || beta == nullptr || records == nullptr) return DPTX_E_INVALID;
+  if (B < 1 || HW < 32 || HW % 32 != 0 || C < 64 || C % 64 != 0 || C > 1024) return DPTX_E_INVALID;
+  if ((r_gamma != nullptr) != (r_beta != nullptr) || (r_gamma != nullptr) != (r_records != nullptr)) return DPTX_E_INVALID;
+  if (r_gamma != nullptr && R == nullptr) return DPTX_E_INVALID;
+  GnParams g = gn_params(X, Y, gamma, beta, const_cast<float*>(records), B, HW, C, relu, eps, true);
+  gn_add_residual(g, R, r_gamma, r_beta, r_records);
+  return rc(launch_gn_apply(dtype, g, g_op_planes, (hipStream_t)stream));
+}
+
 int dptx_op_upsample2x(int32_t dtype, const void* X, void* Y, int32_t B, int32_t H, int32_t W, int32_t C, void* stream) {
   return rc(launch_upsample2x(dtype, X, Y, B, H, W, C, g_op_planes, (hipStream_t)stream));
 }

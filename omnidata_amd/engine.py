@@ -160,6 +160,7 @@ ABI = [
     ("dptx_op_conv_fp8", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp] + [_i32] * 13 + [C.c_float, _vp]),
     ("dptx_op_conv_groupnorm", C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp] + [_i32] * 12 + [C.c_float, _vp, _vp]),
     ("dptx_op_conv_groupnorm_fused", C.c_int, [_i32] + [_vp] * 9 + [_i32] * 6 + [C.c_float, _vp, _vp, _i32, _vp]),
+    ("dptx_op_groupnorm_records", C.c_int, [_i32] + [_vp] * 9 + [_i32] * 4 + [C.c_float, _vp]),
     ("dptx_op_upsample2x", C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_op_upsample2x_strip", C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     ("dptx_op_gemm_ln", C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, C.c_float, _vp]),

@@ -837,8 +837,220 @@ def pos_elem_bound(Sb, L):
     return GEMM_F32_FLOOR_FACTOR * UP_F32_FLOOR_MEASURED * 2.0 ** -24 * Sb + POS_COORD_ERR * L
 
 
+# ------------------------------------------------------------------ conv + GroupNorm records, judged element by element
+# The chain every bottleneck runs: the convolution's epilogue turns its fp32 accumulators into GroupNorm records (csrc/gemm_impl.h
+# gn_records: (sum, sum of squares) per image, 32-row block and group), gn_affine_to_lds / gn_finalize_kernel (csrc/norm.hip)
+# turn the records into the affines (a, d), and gn_apply_kernel or the C1_GN epilogue of csrc/conv1x1.hip applies them, with no
+# shortcut, a plain one, or one behind a GroupNorm of its own.  The kernels that can be compared bit for bit share this code, so
+# a mistake in it passes every such comparison; the helpers below give operands whose every (image, group) has a mean, a sigma
+# and a ratio r = |mean| / sigma of its own, fp64 references of the records, the tables and the output, and the bar on every
+# single one of them.  Everything is computed from conv_acc64 of the values the kernel reads.  Pure torch, any device.
+# tests/test_gn_records_bound_host.py measures the constants and shows on a CPU which mistakes the bars reject;
+# profiles/gn_records_elements.md has the figures.
+
+GNREC_U = 2.0 ** -24
+# Summation and cancellation constants of the statistics: the largest ratio of the fp32 model of
+# tests/test_gn_records_bound_host.py -- gn_records' order (16 registers in sequence with fmaf for the squares, lane ^ 32, lane ^
+# 1 .. cpg / 2), fp64 across the records in 8 slices, mean and rstd rounded to fp32 -- run on the fp64 accumulators rounded to
+# fp32, to the fp64 reference, over GNREC_CASES and GNREC_APPLY_HOST x the four modes:
+#   c_s   |s^ - s| / (u sum |v|)            of a record's sum
+#   c_q   |q^ - q| / (u sum v^2)            of a record's sum of squares
+#   c_a   |d rstd| / rstd / (u (1 + r^2))   one-pass variance: E[x^2] - mean^2 cancels 1 + r^2 to 1
+#   c_m   |d mean| / (u (1 + r) sigma)
+# Measured against the reference, never against a kernel; test_record_constants_are_what_the_bounds_use re-measures them.  The
+# bars use GEMM_F32_FLOOR_FACTOR times these: the GPU's accumulators differ from the rounded fp64 ones within the GEMM bar, so
+# every partial sum rounds differently.
+GNREC_CS_MEASURED = 2.8
+GNREC_CQ_MEASURED = 3.5
+GNREC_CA_MEASURED = 2.5
+GNREC_CM_MEASURED = 2.5
+# (B, H, W, Cin, Cout, k, stride): every (Cin, Cout, k, stride) class of the ResNetV2 stages' convolutions, at B = 3 with
+# 8 x 12 outputs (three records per image; M = 288: a block's waves straddle images) -- the stride-2 classes on 16 x 16 (two
+# records) --, and B = 1 with 4 x 8 (one record).  3 x 3: TF-SAME padding, (1, 1) at stride 1 and (0, 1) at stride 2.
+GNREC_CASES = ((3, 8, 12, 64, 64, 1, 1), (3, 8, 12, 256, 64, 1, 1), (3, 8, 12, 256, 128, 1, 1), (3, 8, 12, 512, 128, 1, 1),
+               (3, 8, 12, 512, 256, 1, 1), (3, 8, 12, 1024, 256, 1, 1), (3, 8, 12, 64, 256, 1, 1), (3, 8, 12, 128, 512, 1, 1),
+               (3, 8, 12, 256, 1024, 1, 1), (3, 16, 16, 256, 512, 1, 2), (3, 16, 16, 512, 1024, 1, 2),
+               (3, 8, 12, 64, 64, 3, 1), (3, 8, 12, 128, 128, 3, 1), (3, 8, 12, 256, 256, 3, 1), (3, 16, 16, 128, 128, 3, 2),
+               (3, 16, 16, 256, 256, 3, 2), (1, 4, 8, 64, 64, 1, 1), (1, 4, 8, 64, 256, 1, 1), (1, 4, 8, 256, 1024, 1, 1))
+# (B, HW, C) of the apply pass alone on the CPU: HW = 2304 has 72 records, nine per slice of gn_affine_to_lds
+GNREC_APPLY_HOST = ((2, 2304, 64), (1, 96, 1024), (2, 288, 64))
+
+
+def conv_gn_geometry(case):
+    """(pad, Ho, Wo) of a GNREC_CASES entry: TF-SAME, pad (1, 1) for 3 x 3 at stride 1, (0, 1) at stride 2, none for 1 x 1"""
+    B, H, W, Cin, Cout, k, stride = case
+    return (1 if (k == 3 and stride == 1) else 0), H // stride, W // stride
+
+
+def conv_gn_operands(B, H, W, Cin, Cout, k, stride=1, seed=0):
+    """X [B, H, W, Cin], Wt [Cout, k, k, Cin], gamma [Cout], beta [Cout], R [B, H / stride, W / stride, Cout] in fp64 (CPU),
+    deterministic in `seed`, such that every (image, group) of conv(X, Wt) has a mean, a sigma and r = |mean| / sigma of its own:
+      X[b, :, :, 0] = c_b = 2^((b mod 3) - 1) (1 - (b mod 3) / 4), a constant per image; the other channels 2^((b mod 3) - 1)
+      N(0, 1) (for B <= 3 that is the scale 2^(b - 1) per image);
+      Wt[n, :, :, 1:] = K^-1/2 2^((5 g) % 7 - 3) N(0, 1), g = n / cpg the group: sigma[b, g] ~ 2^((b mod 3) - 1) 2^((5 g) % 7 - 3);
+      Wt[n, centre, centre, 0] = +-rho_g 2^((5 g) % 7 - 3) with rho_g = (0, 1.5, 8, 28)[g % 4] and the sign of (-1)^(g / 2), zero
+      at every other tap: the centre tap lies inside the image wherever the output does, so zero padding does not move the
+      mean at the border, which is c_b times that weight -- r[b, g] ~ rho_g (1, 3/4, 1/2)[b mod 3];
+      gamma[c], beta[c] = 2^((5 c mod 7) - 3) N(0, 1): a scale per channel, either sign;
+      R from the scaled_conv_operands family: a scale per pixel and per channel.
+    |X| < 2 * 6, |conv| < 16 (28 + 6), |R| < 2^9 * 6, |gamma| 6 + |beta| + |R| < 60000: inside fp16.  r is measured by
+    conv_gn_stats64 on the fp64 accumulators; assert_r_coverage holds every case to the coverage it needs."""
+    g = torch.Generator().manual_seed(7000 + seed)
+    cpg, K = Cout // 32, k * k * Cin
+    bm = torch.arange(B) % 3
+    sb = torch.exp2((bm - 1).double())
+    X = torch.randn(B, H, W, Cin, generator=g, dtype=torch.float64) * sb.view(B, 1, 1, 1)
+    X[..., 0] = (sb * (1.0 - 0.25 * bm.double())).view(B, 1, 1)
+    gi = torch.arange(32)
+    sg = torch.exp2(((5 * gi) % 7 - 3).double())
+    rho = torch.tensor([0.0, 1.5, 8.0, 28.0], dtype=torch.float64)[gi % 4] * torch.where((gi // 2) % 2 == 0, 1.0, -1.0).double()
+    Wt = torch.randn(Cout, k, k, Cin, generator=g, dtype=torch.float64) * sg.repeat_interleave(cpg).view(-1, 1, 1, 1) * K ** -0.5
+    Wt[..., 0] = 0.0
+    Wt[:, k // 2, k // 2, 0] = (rho * sg).repeat_interleave(cpg)
+    sc = torch.exp2(_col_exp(Cout))
+    gamma = torch.randn(Cout, generator=g, dtype=torch.float64) * sc
+    beta = torch.randn(Cout, generator=g, dtype=torch.float64) * sc
+    R = scaled_conv_operands(B, H // stride, W // stride, 8, Cout, 1, seed)[3]
+    return X, Wt, gamma, beta, R
+
+
+def conv_gn_stats64(mode, acc, Sacc, eps=1e-5):
+    """The fp64 references of the records and of the statistics, with their bars, from conv_acc64's (acc, Sacc) [B, Ho, Wo, C]
+    of the values the kernel reads.  v = acc, S = Sacc, E = gemm_elem_bound(mode, v, S, 0, c_fp32=True) = F S (+ u16^2 S in the
+    plane modes), the bar of one fp32 accumulator; u = 2^-24; sums run over the 32 rows x cpg channels of a record, mean_g over
+    an (image, group); c_* = GEMM_F32_FLOOR_FACTOR x GNREC_C*_MEASURED.  Returns a dict of
+      v [B, HW, C], E
+      rec [B, HW / 32, 32, 2] = (s, q) = (sum v, sum v^2)
+      rec_bar                 = (sum E + c_s u sum |v|,  2 sum |v| E + c_q u sum v^2)
+      mean, var [B, 32] (biased, two-pass), sigma = sqrt(var + eps), r = |mean| / sigma
+      mean_bar  = mean_g(E) + c_m u (1 + r) sigma
+      rstd_rel  = (mean_g(|v| E) + |mean| mean_g(E)) / (var + eps) + c_a u (1 + r^2): the accumulators' error moves the second
+                  moment by 2 mean_g(|v| E) and mean^2 by 2 |mean| mean_g(E), and d rstd / rstd = d var / (2 (var + eps))."""
+    acc, Sacc = acc.double(), Sacc.double()
+    B, C = acc.shape[0], acc.shape[-1]
+    cpg = C // 32
+    v, S = acc.reshape(B, -1, C), Sacc.reshape(B, -1, C)
+    HW = v.shape[1]
+    assert HW % 32 == 0
+    E = gemm_elem_bound(mode, v, S, 0, c_fp32=True)
+    u = GNREC_U
+    cs, cq, ca, cm = (GEMM_F32_FLOOR_FACTOR * c for c in (GNREC_CS_MEASURED, GNREC_CQ_MEASURED, GNREC_CA_MEASURED, GNREC_CM_MEASURED))
+
+    def blk(t):
+        return t.reshape(B, HW // 32, 32, 32, cpg).sum((2, 4))
+
+    s, q = blk(v), blk(v * v)
+    s_bar = blk(E) + cs * u * blk(v.abs())
+    q_bar = 2.0 * blk(v.abs() * E) + cq * u * q
+    n = float(HW * cpg)
+    mean = s.sum(1) / n
+    var = ((v.reshape(B, HW, 32, cpg) - mean.view(B, 1, 32, 1)) ** 2).sum((1, 3)) / n
+    sigma = torch.sqrt(var + eps)
+    r = mean.abs() / sigma
+    mE, mvE = blk(E).sum(1) / n, blk(v.abs() * E).sum(1) / n
+    return dict(v=v, E=E, rec=torch.stack([s, q], -1), rec_bar=torch.stack([s_bar, q_bar], -1), mean=mean, var=var, sigma=sigma,
+                r=r, mean_bar=mE + cm * u * (1.0 + r) * sigma, rstd_rel=(mvE + mean.abs() * mE) / (var + eps) + ca * u * (1.0 + r * r))
+
+
+def assert_r_coverage(st):
+    """the coverage a conv + GroupNorm case must have: a group that does not cancel (r <= 0.1), one that cancels 1 + r^2 >= 577
+    to 1 (r >= 24), and none beyond what the operands are built for (r <= 40)"""
+    r = st["r"]
+    assert float(r.min()) <= 0.1 and float(r.max()) >= 24.0 and float(r.max()) <= 40.0, (float(r.min()), float(r.max()))
+
+
+def gn_tables_ref64(st, gamma, beta):
+    """The affines of a GroupNorm from conv_gn_stats64's statistics -- those of the fp64 ACCUMULATORS, which is what the
+    records hold, not of the stored (rounded) map --: a = gamma rstd, d = beta - mean a [B, C] in fp64, with their bars
+      a_bar = |a| (rstd_rel + u)                                 rstd_rel of conv_gn_stats64; u: a = rstd gamma is rounded
+      d_bar = |a| mean_bar + |mean| a_bar + u (|mean| |a| + |beta|)   the last term: d = fma(-a, mean, beta) is rounded once
+    Returns a dict of a, d, a_bar, d_bar, and per channel mean, |beta|, a_stat = |a| rstd_rel, m_stat = |a| mean_bar (what the
+    statistics alone contribute to an output: gn_records_out_ref64)."""
+    B = st["mean"].shape[0]
+    C = gamma.numel()
+    cpg = C // 32
+    gamma, beta = gamma.double().view(1, C).to(st["mean"].device), beta.double().view(1, C).to(st["mean"].device)
+    rep = lambda t: t.repeat_interleave(cpg, 1)
+    mean, rstd, rel, mbar = rep(st["mean"]), rep(1.0 / st["sigma"]), rep(st["rstd_rel"]), rep(st["mean_bar"])
+    a = gamma * rstd
+    d = beta - mean * a
+    a_bar = a.abs() * (rel + GNREC_U)
+    d_bar = a.abs() * mbar + mean.abs() * a_bar + GNREC_U * (mean.abs() * a.abs() + beta.abs())
+    return dict(a=a, d=d, a_bar=a_bar, d_bar=d_bar, mean=mean, beta=beta.abs().expand(B, C), a_stat=a.abs() * rel, m_stat=a.abs() * mbar)
+
+
+def gn_records_out_ref64(mode, x, tab, R=None, rtab=None, relu=0):
+    """fp64 (y, bound) [B, HW, C] of the apply pass: y = relu(x a + d [+ R | + R ra + rd]) of the STORED raw map x (hi + lo in
+    the plane modes; gemm_elem_bound judges it against the accumulators) and shortcut R, with the tables of gn_tables_ref64.
+      bound = gn_elem_bound(mode, y, T) + W
+      T = |x| |a| + |mean| |a| + |beta|  [+ |R|  |  + |R| |ra| + |mean_r| |ra| + |beta_r|]      as gn_ref64, extended by the shortcut
+      W = |x - mean| |a| rstd_rel + |a| mean_bar  [+ |R - mean_r| |ra| rstd_rel_r + |ra| mean_bar_r]
+    W is what the statistics contribute, y = (x - mean) a + beta: |x - mean| |a| c_a u (1 + r^2) of the one-pass variance, and
+    next to it the parts the table bars carry as well -- the accumulators' error in the moments and the error of the mean.
+    The roundings of a, d and of the two fused multiply-adds are relative to terms of T and lie in gn_elem_bound's fp32 floor."""
+    x = x.double()
+    B, HW, C = x.shape
+    t = {k: v.view(B, 1, C) for k, v in tab.items()}
+    y = x * t["a"] + t["d"]
+    T = x.abs() * t["a"].abs() + t["mean"].abs() * t["a"].abs() + t["beta"]
+    Wd = (x - t["mean"]).abs() * t["a_stat"] + t["m_stat"]
+    if R is not None:
+        R = R.double().view(B, HW, C)
+        if rtab is None:
+            y, T = y + R, T + R.abs()
+        else:
+            s = {k: v.view(B, 1, C) for k, v in rtab.items()}
+            y = y + R * s["a"] + s["d"]
+            T = T + R.abs() * s["a"].abs() + s["mean"].abs() * s["a"].abs() + s["beta"]
+            Wd = Wd + (R - s["mean"]).abs() * s["a_stat"] + s["m_stat"]
+    y = torch.relu(y) if relu else y
+    return y, gn_elem_bound(mode, y, T) + Wd
+
+
+def gn_map_operands(B, HW, C, seed=0):
+    """x [B, HW, C], gamma [C], beta [C], R [B, HW, C] in fp64 (CPU) for the apply pass alone: a raw map with the statistics
+    conv_gn_operands gives a convolution's output -- x[b, p, c] = 2^((b mod 3) - 1) 2^((5 g) % 7 - 3) ((1, 3/4, 1/2)[b mod 3]
+    rho_g + N(0, 1)), rho_g = +-(0, 1.5, 8, 28)[g % 4] -- and gamma, beta, R of the same families."""
+    g = torch.Generator().manual_seed(7500 + seed)
+    cpg = C // 32
+    bm = torch.arange(B) % 3
+    gi = torch.arange(32)
+    sb = torch.exp2((bm - 1).double()).view(B, 1, 1, 1)
+    sg = torch.exp2(((5 * gi) % 7 - 3).double()).view(1, 1, 32, 1)
+    rho = (torch.tensor([0.0, 1.5, 8.0, 28.0], dtype=torch.float64)[gi % 4] * torch.where((gi // 2) % 2 == 0, 1.0, -1.0).double())
+    z = torch.randn(B, HW, 32, cpg, generator=g, dtype=torch.float64).clamp(-5.0, 5.0)
+    x = sb * sg * ((1.0 - 0.25 * bm.double()).view(B, 1, 1, 1) * rho.view(1, 1, 32, 1) + z)
+    sc = torch.exp2(_col_exp(C))
+    gamma = torch.randn(C, generator=g, dtype=torch.float64) * sc
+    beta = torch.randn(C, generator=g, dtype=torch.float64) * sc
+    R = scaled_gemm_operands(B * HW, C, 8, seed)[3].view(B, HW, C)
+    return x.reshape(B, HW, C), gamma, beta, R
+
+
+def records_of(x, cpg_groups=32):
+    """fp32 records [B, HW / 32, 32, 2] of the values x [B, HW, C], computed in fp64 and rounded: what a perfect convolution
+    epilogue would have left for the apply pass"""
+    x = x.double()
+    B, HW, C = x.shape
+    t = x.reshape(B, HW // 32, 32, cpg_groups, C // cpg_groups)
+    return torch.stack([t.sum((2, 4)), (t * t).sum((2, 4))], -1).float().contiguous()
+
+
+def stats_of_records(rec, HW, cpg, eps=1e-5):
+    """conv_gn_stats64's statistics dict from given fp32 records [B, nrec, 32, 2] taken as exact: the apply pass alone.  Its
+    bars hold the summation terms only: fp64 across the records leaves the rounding of mean and rstd to fp32 (half a u each;
+    mean_bar = u |mean|, rstd_rel = u) and the cancellation of E[x^2] - mean^2 in fp64, 2^-53 (1 + r^2), which is nothing."""
+    rec = rec.double()
+    n = float(HW * cpg)
+    mean = rec[..., 0].sum(1) / n
+    var = (rec[..., 1].sum(1) / n - mean * mean).clamp_min(0.0)
+    sigma = torch.sqrt(var + eps)
+    r = mean.abs() / sigma
+    return dict(mean=mean, var=var, sigma=sigma, r=r, mean_bar=GNREC_U * mean.abs(), rstd_rel=GNREC_U + 0.0 * r)
+
+
 # ------------------------------------------------------------------ outputs behind guards
-SENTINEL = 0xFFC1 - 0x10000  # int16 view of 0xFFC1: a NaN in bf16 and in fp16, which no kernel under test stores
+SENTINEL =0xFFC1 - 0x10000  # int16 view of 0xFFC1: a NaN in bf16 and in fp16, which no kernel under test stores
 
 
 class debug_flags:

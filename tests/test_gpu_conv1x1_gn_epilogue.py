@@ -110,6 +110,26 @@ def test_fused_equals_unfused_bitwise(dtype, case):
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 @pytest.mark.parametrize("case", CASES)
+def test_fused_downsample_form_equals_the_apply_pass_bitwise(dtype, case):
+    """the shortcut behind a GroupNorm of its own (the first block of a stage): the fold against the schedule it replaces
+    there -- conv3 and the downsample convolution on the tiled kernels, then dptx_op_groupnorm_records, the apply pass the
+    forward launches on their raw maps and records"""
+    lib = load_library()
+    B, H, W, Cin, Cout = case
+    _, _, g, b, _, _, g2, b2 = operands(dtype, case)
+    raw, _, rec = run_unfused(dtype, case, 8, 0, 0)
+    R, _, r_rec = run_unfused(dtype, case, 8, 0, 0, second=True)
+    for relu in (0, 1):
+        Y = torch.full_like(raw, float("nan"))
+        rc = lib.dptx_op_groupnorm_records(DTYPES[dtype], ptr(raw), ptr(g), ptr(b), ptr(rec), ptr(R), ptr(g2), ptr(b2), ptr(r_rec), ptr(Y),
+                                           B, H * W, Cout, relu, 1e-5, stream())
+        assert rc == 0
+        torch.cuda.synchronize()
+        assert torch.equal(Y, run_fused(dtype, case, 2, relu)[0]), relu
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("case", CASES)
 def test_stats_pass_writes_the_records_and_nothing_else(dtype, case):
     Y, rec, _ = run_fused(dtype, case, 0, 0, passes=1, sentinel=3.0)
     old = run_unfused(dtype, case, 16, 0, 0)                             # the storing form of the same kernel
@@ -142,7 +162,7 @@ def test_finalize_gives_the_affines_of_the_records(dtype, case):
 def test_fused_against_fp32(dtype, case):
     """The bound and the form of test_gpu_conv1x1_stream.py::test_stream_conv_groupnorm_against_fp32: group_norm's fp32
     statistics of the fp32 convolution applied to the rounded map.  Also with the shortcut behind a GroupNorm of its own (the
-    first block of a stage), for which no unfused op exists: its bitwise check is the whole forward's, below."""
+    first block of a stage); its bitwise check against the apply pass is test_fused_downsample_form_equals_the_apply_pass_bitwise."""
     B, H, W, Cin, Cout = case
     X, Wt, g, b, R, W2, g2, b2 = operands(dtype, case)
 
